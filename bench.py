@@ -6,9 +6,15 @@ batch of synthetic VTRDyn frames already resident in HBM (BASELINE config 3:
 1234 + rank) into a ring of buffer sets larger than the 256 MiB Infinity Cache
 so every timed step reads cold HBM.  Frames shard across ranks with no
 data-path collective ("scaling": "weak"); the RCCL broadcast of the solver
-constants happens at setup and the DOF gather after the timed region.
+constants happens at setup and the DOF gather (--full) after the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, the launch
+configuration).  ``--dump-outputs DIR`` also writes the DOFs of the last timed step as .npy.  ``--full`` adds
+everything else the line can carry: the box probe around the timed region and, after it, the kernel's own launch
+time and the roofline, the golden checks, the multi-rank DOF gather, BASELINE configs 2 and 5, the other input
+layout, the parity summary and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -44,9 +50,19 @@ def parse():
                     help="input layout of the timed frames: SoA component planes as the device producer emits them "
                          "(default, north_star), or the reference's AoS rows; the other one is reported as a "
                          "secondary line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the DOFs the last timed step computed as DIR/dof.npy (float32; DIR/dof_rank<r>.npy "
+                         "per rank with --gpus N > 1; a fixed seeded sample of the rows where all would exceed 60 MiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: box probe, kernel launch time and roofline, "
+                         "golden checks, multi-rank DOF gather, configs 2 and 5, the other layout, parity summary, "
+                         "CPU baseline")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port() -> int:
@@ -594,9 +610,26 @@ def comm_info(world, backend):
     return info
 
 
-def rank_flow(world, rank, backend, B, steps, warmup, ring):
+DUMP_MAX_BYTES = 60 * 2**20    # --dump-outputs: all ranks' files together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, world, rank, dof):
+    """--dump-outputs: this rank's DOFs of the last timed step, (B, 30) float32, as DIR/dof.npy (DIR/dof_rank<r>.npy
+    when there are several ranks).  Above this rank's share of DUMP_MAX_BYTES the file holds a fixed sample of the
+    rows (seed 1234, ascending row order), the same rows in every run."""
+    a = np.ascontiguousarray(dof.detach().cpu().numpy(), dtype=np.float32)
+    rows = max(1, DUMP_MAX_BYTES // world // (a.shape[1] * 4))
+    if a.shape[0] > rows:
+        a = a[np.sort(np.random.default_rng(1234).choice(a.shape[0], rows, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "dof.npy" if world == 1 else f"dof_rank{rank}.npy"), a)
+
+
+def rank_flow(world, rank, backend, B, steps, warmup, ring, full=False, dump=None):
     """One rank of the bench: setup broadcast -> own shard of B frames generated locally (seed
-    1234 + rank) -> K timed solves between barriers -> max over ranks -> untimed DOF gather to rank 0."""
+    1234 + rank) -> K timed solves between barriers -> max over ranks; `dump` writes the last step's DOFs
+    (dump_outputs).  With `full`: the box probe around the timed region, the kernel's own launch time, every rank's
+    golden check and the untimed DOF gather to rank 0."""
     from rtg import shard
     setup = None
     if rank == 0:
@@ -613,7 +646,7 @@ def rank_flow(world, rank, backend, B, steps, warmup, ring):
         b, l, r_ = backend.synth(topo, B, 1234 + rank, r * B)
         sets.append((b, l, r_, backend.new_dof(B)))
     backend.sync()
-    probe = getattr(backend, "probe", None)   # the box's clock and bandwidth, measured before the timed region
+    probe = getattr(backend, "probe", None) if full else None   # clock and bandwidth, before the timed region
     box = {"before": probe()} if probe is not None else None
     for i in range(warmup):
         b, l, r_, d = sets[i % ring]
@@ -635,11 +668,19 @@ def rank_flow(world, rank, backend, B, steps, warmup, ring):
     barrier(world, backend)
     wall = time.perf_counter() - t0
     gpu_step_ms = backend.elapsed_ms() / max(1, steps)
+    if dump is not None:   # before anything else writes a DOF buffer again
+        dump_outputs(dump, world, rank, sets[(steps - 1) % ring][3])
+    if world > 1:   # the bench clock is the slowest rank's
+        wall = shard.max_over_ranks(wall, backend.comm_device)
+    out = {"wall": wall, "gpu_step_ms": gpu_step_ms, "frames": world * B * steps, "sets": sets, "topo": topo,
+           "solver": solver, "zl": lt, "zg": zg, "parents": parents, "devices": devices,
+           "comm": comm_info(world, backend)}
+    if not full:
+        return out
     launch = getattr(backend, "launch_ms", None)
     kern_ms = launch(solver, sets) if launch is not None else gpu_step_ms
     kern_ms_rank = kern_ms
-    if world > 1:   # the bench clock and the kernel clock are both the slowest rank's
-        wall = shard.max_over_ranks(wall, backend.comm_device)
+    if world > 1:   # the kernel clock is the slowest rank's too
         kern_ms = shard.max_over_ranks(kern_ms, backend.comm_device)
     # every rank checks its own device solver against the reference goldens (after the timed region)
     gold = backend.golden_check(solver)
@@ -651,9 +692,7 @@ def rank_flow(world, rank, backend, B, steps, warmup, ring):
                      "kern_ms": v[2]} for r, v in enumerate(vals)]
     if box is not None:
         box["after"] = probe()
-    out = {"wall": wall, "kern_ms": kern_ms, "gpu_step_ms": gpu_step_ms, "frames": world * B * steps, "sets": sets, "topo": topo,
-           "solver": solver, "zl": lt, "zg": zg, "parents": parents, "golden_per_rank": per_rank, "box": box,
-           "devices": devices, "comm": comm_info(world, backend)}
+    out.update(kern_ms=kern_ms, golden_per_rank=per_rank, box=box)
     if world > 1:   # final DOF gather to rank 0 (untimed region, reported separately)
         d = sets[(steps - 1) % ring][3]
         backend.sync()
@@ -680,14 +719,11 @@ def main():
     backend = backend_cls(local, args.layout)
     bytes_per_set = B * (63 + 60 + 60 + 30) * 4
     ring = args.ring or max(2, int(np.ceil(2 * 256 * 2**20 / bytes_per_set)))
-    res = rank_flow(world, rank, backend, B, args.steps, args.warmup, ring)
-    wall, kern_ms = res["wall"], res["kern_ms"]
+    res = rank_flow(world, rank, backend, B, args.steps, args.warmup, ring, full=args.full, dump=args.dump_outputs)
+    wall = res["wall"]
     value = res["frames"] / wall
     ms_per_step = wall * 1e3 / args.steps
-    stream = backend.stream
     if rank == 0:
-        achieved = BYTES_PER_FRAME * B / (kern_ms * 1e-3) / 1e9
-        rec = pmc_record(B, args.layout)
         line = {
             "metric": METRIC, "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
@@ -698,66 +734,84 @@ def main():
                        "launch": "one HIP graph of the K solves" if getattr(backend, "graph", None) is not None
                        else (f"K plain launches, step i on stream i % {backend.nstreams}" if backend.nstreams > 1
                              else "K plain launches")},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": rec["traffic_bytes"] if rec else None,
-                         "kernel": f"k_solve_sides<FULL_BODY_POS, {args.layout.upper()}>", "kernel_ms": kern_ms,
-                         "kernel_ms_source": "event pair around 10 single-stream launches right after the timed region",
-                         "gpu_ms_per_step": res["gpu_step_ms"],
-                         # the same bytes over the timed region's per-step GPU time (steps overlap on two streams)
-                         "achieved_per_step": BYTES_PER_FRAME * B / (res["gpu_step_ms"] * 1e-3) / 1e9,
-                         "frac_per_step": BYTES_PER_FRAME * B / (res["gpu_step_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "bytes_per_frame": BYTES_PER_FRAME,
-                         "traffic_unit": "bytes/launch (rocprofv3 FETCH_SIZE x calibration + WRITE_SIZE)",
-                         "traffic_detail": {k: rec[k] for k in ("fetch_size_raw", "fetch_correction", "fetch_bytes",
-                                                                "write_bytes", "angle_table_fetch_bytes") if k in rec}
-                         if rec else None,
-                         "compute": compute_roofline(rec, kern_ms)},
+            "gpu_ms_per_step": res["gpu_step_ms"], "full": args.full,
         }
         line["settle"] = getattr(backend, "settle", None)
-        line["golden_per_rank"] = res["golden_per_rank"]
         line["devices"] = res["devices"]   # one entry per rank: distinct PCI addresses (checked in rank_flow)
         line["comm"] = res["comm"]
-        line["box"] = res["box"]
-        if "gather_ms" in res:
-            line["gather_ms"] = res["gather_ms"]
-        from rtg import ops
-        aos = ops.synth_full_body(res["topo"], min(B, 65536), seed=1234 + rank)   # rows for config 2 / the CPU leg
-        if world == 1:
-            solver, sets = res["solver"], res["sets"]
-            try:
-                line["secondary"] = secondary_configs(solver, [t[:4096].contiguous() for t in aos], stream)
-            except Exception as e:  # noqa: BLE001
-                line["secondary"] = {"error": repr(e)}
-            other = "aos" if args.layout == "soa" else "soa"
-            try:
-                del sets[:]
-                line["secondary"][f"config3_{other}_layout"] = layout_line(solver, res["topo"], B, rank, ring,
-                                                                           args.steps, stream, other)
-            except Exception as e:  # noqa: BLE001
-                line["secondary"][f"config3_{other}_layout"] = {"error": repr(e)}
-        try:
-            line["parity_vs_reference"] = parity_vs_reference()
-        except Exception as e:  # noqa: BLE001
-            line["parity_vs_reference"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
-            b, l, r_ = aos
-            line["cpu_baseline"] = cpu_baseline(b.cpu().numpy(), l.cpu().numpy(), r_.cpu().numpy(),
-                                                np.asarray(res["zl"], np.float32), np.asarray(res["zg"], np.float32),
-                                                args.cpu_seconds)
+        if args.dump_outputs is not None:
+            line["outputs"] = args.dump_outputs
+        if args.full:
+            full_report(line, args, res, backend, world, rank, B, ring)
         print(json.dumps(line), flush=True)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
 
 
+def full_report(line, args, res, backend, world, rank, B, ring):
+    """--full, rank 0: what the line carries beside the headline figure -- the roofline of the kernel's own launch
+    time, the golden checks, the box probe, configs 2 and 5, the other input layout, the parity summary and the CPU
+    baseline."""
+    kern_ms = res["kern_ms"]
+    stream = backend.stream
+    achieved = BYTES_PER_FRAME * B / (kern_ms * 1e-3) / 1e9
+    rec = pmc_record(B, args.layout)
+    line["roofline"] = {
+        "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS, "traffic": rec["traffic_bytes"] if rec else None,
+        "kernel": f"k_solve_sides<FULL_BODY_POS, {args.layout.upper()}>", "kernel_ms": kern_ms,
+        "kernel_ms_source": "event pair around 10 single-stream launches right after the timed region",
+        "gpu_ms_per_step": res["gpu_step_ms"],
+        # the same bytes over the timed region's per-step GPU time (steps overlap on two streams)
+        "achieved_per_step": BYTES_PER_FRAME * B / (res["gpu_step_ms"] * 1e-3) / 1e9,
+        "frac_per_step": BYTES_PER_FRAME * B / (res["gpu_step_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+        "bytes_per_frame": BYTES_PER_FRAME,
+        "traffic_unit": "bytes/launch (rocprofv3 FETCH_SIZE x calibration + WRITE_SIZE)",
+        "traffic_detail": {k: rec[k] for k in ("fetch_size_raw", "fetch_correction", "fetch_bytes",
+                                               "write_bytes", "angle_table_fetch_bytes") if k in rec}
+        if rec else None,
+        "compute": compute_roofline(rec, kern_ms)}
+    line["golden_per_rank"] = res["golden_per_rank"]
+    line["box"] = res["box"]
+    if "gather_ms" in res:
+        line["gather_ms"] = res["gather_ms"]
+    from rtg import ops
+    aos = ops.synth_full_body(res["topo"], min(B, 65536), seed=1234 + rank)   # rows for config 2 / the CPU leg
+    if world == 1:
+        solver, sets = res["solver"], res["sets"]
+        try:
+            line["secondary"] = secondary_configs(solver, [t[:4096].contiguous() for t in aos], stream)
+        except Exception as e:  # noqa: BLE001
+            line["secondary"] = {"error": repr(e)}
+        other = "aos" if args.layout == "soa" else "soa"
+        try:
+            del sets[:]
+            line["secondary"][f"config3_{other}_layout"] = layout_line(solver, res["topo"], B, rank, ring,
+                                                                       args.steps, stream, other)
+        except Exception as e:  # noqa: BLE001
+            line["secondary"][f"config3_{other}_layout"] = {"error": repr(e)}
+    try:
+        line["parity_vs_reference"] = parity_vs_reference()
+    except Exception as e:  # noqa: BLE001
+        line["parity_vs_reference"] = {"error": repr(e)}
+    if world == 1 and not args.no_cpu_baseline:
+        b, l, r_ = aos
+        line["cpu_baseline"] = cpu_baseline(b.cpu().numpy(), l.cpu().numpy(), r_.cpu().numpy(),
+                                            np.asarray(res["zl"], np.float32), np.asarray(res["zg"], np.float32),
+                                            args.cpu_seconds)
+
+
 def host_main(args, backend, world, rank):
     """The launch/collective flow with a stand-in backend (tests): same rank_flow, a reduced line."""
-    res = rank_flow(world, rank, backend, args.batch, args.steps, args.warmup, max(2, args.ring))
+    res = rank_flow(world, rank, backend, args.batch, args.steps, args.warmup, max(2, args.ring), full=args.full,
+                    dump=args.dump_outputs)
     if rank == 0:
         line = {"metric": METRIC, "value": res["frames"] / res["wall"], "unit": "frames/s", "n_gpus": world,
-                "steps": args.steps, "warmup": args.warmup, "backend": type(backend).__name__,
-                "kern_ms": res["kern_ms"], "golden_per_rank": res["golden_per_rank"], "devices": res["devices"],
-                "comm": res["comm"]}
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["wall"] * 1e3 / args.steps,
+                "backend": type(backend).__name__, "devices": res["devices"], "comm": res["comm"]}
+        if args.full:
+            line.update(kern_ms=res["kern_ms"], golden_per_rank=res["golden_per_rank"])
         if "gathered" in res:
             line["gathered_sha1"] = hashlib.sha1(res["gathered"].numpy().tobytes()).hexdigest()
         print(json.dumps(line), flush=True)

@@ -284,7 +284,8 @@ def test_bench_device_path_two_ranks_on_one_gpu():
     env.update(RTG_BENCH_BACKEND="bench_shared_gpu_backend:SharedGpuGlooBackend", RTG_BENCH_SETTLE_MS="20",
                PYTHONPATH=os.pathsep.join([os.path.dirname(os.path.abspath(__file__)), repo, env.get("PYTHONPATH", "")]))
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-                        "--batch", "65536", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=240)
+                        "--batch", "65536", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                       timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["parallelism"] == "dp2"

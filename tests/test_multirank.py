@@ -142,7 +142,7 @@ def _bench_flow(rank, world):
             raise AssertionError("rank > 0 read a local asset")
         for name in ("parents", "local_translation", "tree_quat"):
             setattr(assets, name, _no_assets)
-    res = bench.rank_flow(world, rank, HostBackend(), B=23, steps=3, warmup=1, ring=2)
+    res = bench.rank_flow(world, rank, HostBackend(), B=23, steps=3, warmup=1, ring=2, full=True)   # with the gather
     g = res.get("gathered")
     return {"gathered": None if g is None else g.numpy(), "wall": res["wall"], "frames": res["frames"],
             "zg": np.asarray(res["zg"]), "parents": np.asarray(res["parents"])}
@@ -203,7 +203,7 @@ def test_bench_gpus_flag_spawns_ranks_world2():
     import json
     import oracle as orc
     from rtg import assets, synth
-    r = _bench_cmd("--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "23", "--ring", "2")
+    r = _bench_cmd("--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "23", "--ring", "2", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -224,6 +224,48 @@ def test_bench_gpus_flag_spawns_ranks_world2():
     assert [d["rank"] for d in line["devices"]] == [0, 1]
     assert len({d["pci"] for d in line["devices"]}) == 2
     assert line["comm"]["backend"] == "gloo" and line["comm"]["world"] == 2
+
+
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain run (no --full) prints the headline fields alone -- no golden check, no gather -- and
+    `--dump-outputs DIR` writes each rank's DOFs of the last timed step as float32 .npy: the oracle's DOFs of that
+    rank's seeded shard."""
+    import json
+    import oracle as orc
+    from rtg import assets, synth
+    r = _bench_cmd("--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "23", "--ring", "2",
+                   "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["steps"] == 3 and line["value"] > 0
+    assert line["ms_per_step"] == pytest.approx(2 * 23 / line["value"] * 1e3)
+    assert not {"golden_per_rank", "gathered_sha1", "kern_ms"} & set(line)
+    zp = np.load(os.path.join(os.path.dirname(__file__), "golden", "zero_pose.npz"))
+    assert sorted(os.listdir(tmp_path / "out")) == ["dof_rank0.npy", "dof_rank1.npy"]
+    for rank in (0, 1):   # the last timed step used ring set (3 - 1) % 2 = 0: frame offset 0
+        b, l, rr = synth.synth_full_body_inputs(23, seed=(1234 + rank) * 1000)
+        want = orc.full_body_pos(assets.local_translation("vtrdyn_full"), zp["vtrdyn_full_global_t"], b, l, rr, True,
+                                 want_rot=False)[0]
+        got = np.load(tmp_path / "out" / f"dof_rank{rank}.npy")
+        assert got.dtype == np.float32
+        np.testing.assert_array_equal(got, want)
+
+
+def test_dump_outputs_samples_fixed_rows_above_the_size_limit(tmp_path, monkeypatch):
+    import bench
+    import torch
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 30 * 4)
+    dof = torch.arange(64 * 30, dtype=torch.float32).reshape(64, 30)
+    bench.dump_outputs(str(tmp_path / "a"), 1, 0, dof)
+    bench.dump_outputs(str(tmp_path / "b"), 1, 0, dof)
+    a, b = np.load(tmp_path / "a" / "dof.npy"), np.load(tmp_path / "b" / "dof.npy")
+    assert a.shape == (10, 30) and a.dtype == np.float32
+    np.testing.assert_array_equal(a, b)
+    rows = (a[:, 0] / 30).astype(int)
+    assert (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(a, dof.numpy()[rows])
 
 
 def test_bench_refuses_two_ranks_on_one_device():

@@ -148,39 +148,83 @@ def _torch_vml():
         return None
 
 
+def _recorded_vml():
+    """The goldens' VML as vector functions with MKL VML's signature, replayed from tests/golden/vml_recorded.npz
+    (tools/record_vml.py): VML's bits depend on the CPU that MKL dispatches for, and the goldens are an AVX-512 Intel
+    host's, so the VML of the host a test runs on is in general another one.  The file holds every input of the
+    attribution tests' calls at which that VML is not correctly rounded, with its result; at every other input it
+    returned the correctly rounded value, which is (float)f((double)x), the oracle's own.  Returns the four callbacks
+    (acos, sin, cos, sqrt; keep them referenced while they are installed)."""
+    import ctypes
+    import math
+    rec = golden("vml_recorded")
+    proto = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                             ctypes.c_longlong)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+
+    def make(name, f):
+        table = dict(zip(rec[f"{name}_x"].tolist(), rec[f"{name}_y"].tolist()))
+
+        def fn(n, a, r, mode):
+            ab, rb = ctypes.cast(a, u32p), ctypes.cast(r, u32p)
+            for i in range(n):
+                y = table.get(ab[i])
+                if y is not None:
+                    rb[i] = y
+                    continue
+                try:
+                    r[i] = f(a[i])   # double -> float: round to nearest
+                except ValueError:   # outside the domain: C's NaN
+                    r[i] = math.nan
+        return proto(fn)
+    return [make("acos", math.acos), make("sin", math.sin), make("cos", math.cos), make("sqrt", math.sqrt)]
+
+
+def _as_ptrs(fns):
+    import ctypes
+    return [ctypes.cast(f, ctypes.c_void_p) for f in fns]
+
+
+def _goldens_host():
+    """Whether this host's own torch VML is the goldens' (MKL on an AVX-512 Intel CPU)."""
+    cpu = open("/proc/cpuinfo").read()
+    return _torch_vml() is not None and "avx512f" in cpu and "GenuineIntel" in cpu
+
+
 def test_vml_attribution():
     """Attribution of the remaining residual: with torch's own VML acos / sin / cos / sqrt routed into the oracle's
     eight VML call sites (a test-only hook), every solver golden is reproduced BIT FOR BIT -- the oracle is the
     reference's arithmetic exactly, except that it rounds those four functions correctly where MKL VML does not.
     tools/vml_attrib.py attributes each over-1e-5 frame to the single VML call that causes it
     (profiles/r05/vml_attrib.md).  VML's bits depend on the host CPU's dispatch; the goldens were made on the build
-    container's AVX-512 Xeon."""
+    container's AVX-512 Xeon, so the VML routed in is that host's, replayed from its record (_recorded_vml) -- and,
+    where this host's own VML is the same one, the live one as well."""
     import ctypes
-    fns = _torch_vml()
-    if fns is None or "avx512f" not in open("/proc/cpuinfo").read():
-        pytest.skip("torch's VML or an AVX-512 host (the goldens' ISA) is not available")
     lib = orc.lib()
-    lib.oracle_set_vml(*fns[:3], ctypes.c_longlong(0x140102))   # VML_HA | VML_FTZDAZ_OFF | VML_ERRMODE_IGNORE
-    lib.oracle_set_vml_sqrt(fns[3])
-    try:
-        got = {name: _run(name) for name in BOUNDS}
-    finally:
-        lib.oracle_set_vml(None, None, None, ctypes.c_longlong(0))
-        lib.oracle_set_vml_sqrt(None)
-    for name, (dof, d) in got.items():
-        np.testing.assert_array_equal(dof, d["dof"], err_msg=name)
+    recorded = _recorded_vml()
+    for fns in [_as_ptrs(recorded)] + ([_torch_vml()] if _goldens_host() else []):
+        lib.oracle_set_threads(1)   # the replay is Python: one caller at a time
+        lib.oracle_set_vml(*fns[:3], ctypes.c_longlong(0x140102))   # VML_HA | VML_FTZDAZ_OFF | VML_ERRMODE_IGNORE
+        lib.oracle_set_vml_sqrt(fns[3])
+        try:
+            got = {name: _run(name) for name in BOUNDS}
+        finally:
+            lib.oracle_set_vml(None, None, None, ctypes.c_longlong(0))
+            lib.oracle_set_vml_sqrt(None)
+            lib.oracle_set_threads(os.cpu_count() or 1)
+        for name, (dof, d) in got.items():
+            np.testing.assert_array_equal(dof, d["dof"], err_msg=name)
 
 
 def test_vml_attribution_one_call_per_frame():
     """Every solver-golden frame over 1e-5 is moved there by ONE VML call: with VML's value at that call alone (and
     correctly rounded everywhere else) the frame is within 1e-5 (tools/vml_attrib.py, profiles/r05/vml_attrib.json).
     The calls sit at five different sites, on inputs spread over their whole domains -- no narrow-domain table can
-    restate them."""
+    restate them.  VML is the goldens' host's, replayed from its record (_recorded_vml)."""
     import ctypes
     import json
-    fns = _torch_vml()
-    if fns is None or "avx512f" not in open("/proc/cpuinfo").read():
-        pytest.skip("torch's VML or an AVX-512 host (the goldens' ISA) is not available")
+    recorded = _recorded_vml()
+    fns = _as_ptrs(recorded)
     rep = json.load(open(os.path.join(REPO, "profiles", "r05", "vml_attrib.json")))
     lib = orc.lib()
     lib.oracle_set_threads(1)
@@ -237,10 +281,14 @@ def _run(name):
 
 def _run_frames(name, idx):
     """The oracle's DOFs of the golden frames idx (oracle_vml_log / oracle_set_vml_call count calls from here)."""
+    orc.lib().oracle_vml_log(None, 0)   # restarts the call count
+    return _solve_frames(name, idx)
+
+
+def _solve_frames(name, idx):
     from rtg import assets
     zp = golden("zero_pose")
     d = golden(name)
-    orc.lib().oracle_vml_log(None, 0)   # restarts the call count
     if name.startswith("full_body_pos"):
         return orc.full_body_pos(zp["vtrdyn_full_local_t"], zp["vtrdyn_full_global_t"], d["body"][idx], d["lh"][idx],
                                  d["rh"][idx], bool(d["precise_gripper"]), want_rot=False)[0]

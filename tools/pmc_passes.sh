@@ -1,17 +1,18 @@
 #!/usr/bin/env bash
 # PMC passes over a short bench run, one rocprofv3 run per pass (gfx950 slot limits:
-# <= 8 SQ counters per pass).  Output: gpurun_out/pmc_<tag>_<pass>/...
+# <= 8 SQ counters per pass).  Output: $RTG_PROFILE_OUT/pmc_<tag>_<pass>/... (default profile_out/)
 # usage: tools/pmc_passes.sh <tag> [pass ...]   (passes: sq valu misc icache; default all)
 set -eu
 tag=${1:-r01}
 shift || true
 passes=${*:-sq valu misc}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+out=${RTG_PROFILE_OUT:-profile_out}
+mkdir -p "$out"
 run() {
   name=$1; shift
-  timeout -s KILL 120 rocprofv3 --pmc "$@" -d gpurun_out/pmc_${tag}_$name -o $name --output-format csv \
-    -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline > gpurun_out/pmc_${tag}_$name.log 2>&1
+  timeout -s KILL 120 rocprofv3 --pmc "$@" -d "$out/pmc_${tag}_$name" -o $name --output-format csv \
+    -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > "$out/pmc_${tag}_$name.log" 2>&1
 }
 for p in $passes; do
   case $p in

@@ -11,7 +11,7 @@ tag=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof_$tag
 mkdir -p $out
-B="python bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+B="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 # the PMC passes count bytes and instructions, which the clock does not change: no clock-settle phase there
 export RTG_BENCH_SETTLE_MS=0
 pmc() {   # pmc <name> <lib or -> <counters...>
@@ -20,9 +20,9 @@ pmc() {   # pmc <name> <lib or -> <counters...>
   RTG_ALLOW_MEASUREMENT_BUILD=1 RTG_LIB=${env_lib:-$PWD/humanoid-real-time-retarget_amd/librtg_hip.so} timeout -s KILL 120 \
     rocprofv3 --pmc "$@" -d $out/$name -o $name --output-format csv -- $B > $out/$name.log 2>&1
 }
-RTG_BENCH_SETTLE_MS=200 timeout -k 10 300 python bench.py > $out/bench.log 2>&1
+RTG_BENCH_SETTLE_MS=200 timeout -k 10 300 python bench.py --full > $out/bench.log 2>&1
 RTG_BENCH_SETTLE_MS=200 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/trace -o trace --output-format csv \
-  -- python bench.py --steps 20 --no-cpu-baseline > $out/trace.log 2>&1
+  -- python bench.py --full --steps 20 --no-cpu-baseline > $out/trace.log 2>&1
 python tools/trace_summary.py $out/trace/trace_kernel_trace.csv 12 10 > $out/trace_by_grid.txt 2>&1 || true
 pmc fetch - FETCH_SIZE
 pmc write - WRITE_SIZE
