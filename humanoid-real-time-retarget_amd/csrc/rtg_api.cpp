@@ -6,6 +6,7 @@
 #include <immintrin.h>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -406,6 +407,10 @@ int rtg_solver_create(int kind, const float *zl, const float *zg, const int32_t 
         if (!zg) return fail(RTG_ERR_INVALID_ARGUMENT, "FULL_BODY_POS needs the zero-pose global translation");
         // full_body_pos_retargeter.py:69, :139, :162, :78/:86/:99/:107, :184
         C.Zt[0] = v3(zl, 11); C.Zt[1] = v3(zl, 36); C.Zt[2] = v3(zl, 34);
+        // the zero-column torso fit (torso_quat_x0): from Zt itself; -0 qualifies (the column's sign reaches no output)
+        C.torso_x0 = 1;
+        for (int j = 0; j < 3; ++j)
+            if (!(C.Zt[j].x == 0.0f && std::fabs(C.Zt[j].y) <= 0x1p60f && std::fabs(C.Zt[j].z) <= 0x1p60f)) C.torso_x0 = 0;
         const int li[5] = {16, 20, 24, 28, 32}, ri[5] = {41, 45, 49, 53, 56}, gi[5] = {18, 22, 26, 30, 33};
         for (int t = 0; t < 5; ++t) {
             C.Zl[t] = v3(zl, li[t]);

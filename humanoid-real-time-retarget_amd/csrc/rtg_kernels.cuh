@@ -40,6 +40,7 @@ struct SolverConsts {
     float grip_d[5];  // zero-pose x distances of the 5 finger tips to the wrist
     float orig;       // their mean (gripper denominator), filled by k_solver_prep
     int32_t par[4];   // BODY_ROT: parents of joints 18, 14, 19, 15
+    int32_t torso_x0; // FULL_BODY_POS: every Zt[j].x is +-0 and |Zt| <= 2^60 (torso_quat_x0, rtg_math.cuh)
     const uint32_t *ang_tab;   // exp-map angle table (kAngTabWords words, device), owned by the solver handle
     uint32_t *err;             // host-mapped error word of the solver handle: a wave hand-over that timed out ORs
                                // RTG_DEVERR_HANDOVER_TIMEOUT in (rtg_retarget_f32 reports it on the next call)

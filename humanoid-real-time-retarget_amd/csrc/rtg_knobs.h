@@ -67,14 +67,11 @@
 #ifndef RTG_EXP_NO_TABLE
 #define RTG_EXP_NO_TABLE 0
 #endif
-#ifndef RTG_EXP_LARTG_RCP64
-#define RTG_EXP_LARTG_RCP64 0   // A/B knob (same values): SLARTG / SLASV2 quotients by rcp64 + mulr_k<2> (round 4's form)
-#endif
-#ifndef RTG_EXP_SQRT64
-#define RTG_EXP_SQRT64 0   // A/B knob (same values): cr_sqrt as round 4's v_sqrt_f64 + Newton
-#endif
-#ifndef RTG_EXP_SQRT_CALL
-#define RTG_EXP_SQRT_CALL 0   // A/B knob (same values): cr_sqrt's x < 2^-96 / inf / NaN behind a call (round 5's first form)
+#ifndef RTG_TORSO_X0
+#define RTG_TORSO_X0 1   // k_solve_sides FULL_BODY_POS: the torso fit of a zero pose whose torso vectors have x = 0 runs
+                         // la_gesdd3's fixed path for a zero first column alone (la_gesdd3_x0); 0: the general fit
+                         // (A/B knob, same values: SoA 93.2-94.5 vs 95.3-96.6 us in one session, medians 94.6 vs 95.0 in a
+                         // second; 8 rounds pooled 94.3 vs 95.6 mean; profiles/r07/ab_headline*.log)
 #endif
 #ifndef RTG_EXP_ACOS_LIBM
 #define RTG_EXP_ACOS_LIBM 0   // A/B knob (same values): cr_acos as round 4's libm f64 acos

@@ -30,47 +30,21 @@ struct V { float x, y, z; };
 
 // ---------------------------------------------------------------- helpers
 RTG_DEV float ieee_sqrtf(float x) { return __builtin_sqrtf(x); }   // IEEE sqrt (correctly rounded build)
-// Correctly rounded f32 sqrt in 6 instructions: v_sqrt_f64 (not accurate enough alone: it misses on 4 % of
-// inputs) plus one Newton correction gives ~2^-100, and sqrt of an f32 is never within 2^-51 of an f32
-// midpoint, so the single rounding is exact.  0 / inf / NaN / negative: the residual is 0 or NaN and the raw
-// v_sqrt_f64 value (IEEE for those) is kept.  The rare-input path of cr_sqrt below.
-RTG_DEV float cr_sqrt64(float x)
-{
-    const double d = (double)x;
-    const double y = __builtin_amdgcn_sqrt(d);
-    const double r = __builtin_fma(-y, y, d);
-    const double y1 = __builtin_fma(r, 0.5 * __builtin_amdgcn_rcp(y), y);
-    return (float)((r == 0.0 || r != r) ? y : y1);
-}
 // Correctly rounded f32 sqrt in f32 arithmetic (round 5): v_sqrt_f32 is within 1 ulp for x >= 2^-96, and of the
 // candidates s - ulp, s, s + ulp the signs of the exact residuals x - (s - ulp) s and x - (s + ulp) s (one fma each)
 // pick the correctly rounded one -- the sequence LLVM emits for a correctly rounded f32 sqrt.  +-0 comes out of the
 // same sequence exactly (v_sqrt_f32(+-0) = +-0 and neither residual test moves it: quat_from_rotation_matrix clamps
 // negative estimates to 0, so zeros are common there); x below 2^-96 (denormals, negatives) is scaled by 2^64 first
-// (below; RTG_EXP_SQRT_CALL keeps the first form, cr_sqrt64 behind one rare-case branch).  No f64 instruction (cr_sqrt64:
-// three f64 ops and two quarter-rate f64 transcendentals).  Proven equal to __builtin_sqrtf on all 2^32 inputs by
-// tools/check_fastmath.hip [1] (run by tests/test_gpu_parity.py).
-__device__ __attribute__((noinline)) float cr_sqrt64_call(float x) { return cr_sqrt64(x); }
+// (below).  No f64 instruction (round 4's v_sqrt_f64 + Newton form: three f64 ops and two quarter-rate f64
+// transcendentals).  Proven equal to __builtin_sqrtf on all 2^32 inputs by tools/check_fastmath.hip [1] (run by
+// tests/test_gpu_parity.py).
 RTG_DEV float cr_sqrt(float x)
 {
-#if RTG_EXP_SQRT64   // A/B knob (same values): round 4's f64 form everywhere
-    return cr_sqrt64(x);
-#endif
-#if RTG_EXP_SQRT_CALL   // A/B knob (same values): the round-5 first form, x < 2^-96 / inf / NaN behind a call
-    float s = __builtin_amdgcn_sqrtf(x);
-    const float sdn = __uint_as_float(__float_as_uint(s) - 1u), sup = __uint_as_float(__float_as_uint(s) + 1u);
-    const float rdn = __builtin_fmaf(-sdn, s, x), rup = __builtin_fmaf(-sup, s, x);
-    s = rdn <= 0.0f ? sdn : s;
-    s = rup > 0.0f ? sup : s;
-    if (!(RTG_EXP_NO_RARE & 1) && __builtin_expect(!((x >= 0x1p-96f && x <= 3.40282347e38f) || x == 0.0f), 0))
-        s = cr_sqrt64_call(x);
-    return s;
-#else
     // branch-free: x < 2^-96 (tiny and denormal positives; negatives and -0, which the scaling keeps negative / -0
     // and the sequence turns into NaN / -0) is scaled by 2^64 into the range where v_sqrt_f32 is within an ulp and
     // the result scaled back by 2^-32 (both exact: sqrt(2^-149 2^64) = 2^-42.5 and the result stays normal).  +-0,
     // inf and NaN come out of the sequence itself (v_sqrt_f32 returns them exactly; every residual test reads
-    // false on them).  The branch it replaces was a call (cr_sqrt64) at each of ~150 inlined sites of the side
+    // false on them).  The branch it replaces was a call (the f64 form) at each of ~150 inlined sites of the side
     // kernel: each site's call set-up and call-clobbered registers cost more than the 4 instructions here.
     const bool tiny = x < 0x1p-96f;
     const float xs = tiny ? x * 0x1p64f : x;
@@ -80,7 +54,6 @@ RTG_DEV float cr_sqrt(float x)
     s = rdn <= 0.0f ? sdn : s;
     s = rup > 0.0f ? sup : s;
     return tiny ? s * 0x1p-32f : s;
-#endif
 }
 // Rounding test for an f64 approximation y of a value whose f32 rounding is wanted: true when the bits f32 rounding
 // drops (29 of them, for an f32-normal |y|) are not within D f64 ulps of the midpoint 2^28, i.e. every value within
@@ -1008,14 +981,7 @@ RTG_DEV void la_lartg(float f, float g, float &c, float &s, float &r)   // SLART
     // outputs behind ONE rare-case branch -- the same operations per case as the reference's cascade
     {
         const float d = la_sqrt(f * f + g * g);
-#if RTG_EXP_LARTG_RCP64   // A/B knob (round 5): the two quotients through rcp64 + mulr_k<2> (same values)
-        const Rcp rd = rcp64(d);
-        const float num[2] = {f1, g};
-        float quo[2];
-        mulr_k<2>(num, rd, quo);
-#else
         const float quo[2] = {fdiv(f1, d), fdiv(g, d)};
-#endif
         c = quo[0];
         r = __builtin_copysignf(d, f);
         s = f < 0.0f ? -quo[1] : quo[1];   // g / r with r = +-d (RN is sign-symmetric)
@@ -1088,27 +1054,10 @@ RTG_DEV void la_lasv2(float f, float g, float h, float &ssmin, float &ssmax, flo
             if (mm == 0.0f) t = l == 0.0f ? la_sign(2.0f, ft) * la_sign(1.0f, gt) : fdiv(gt, la_sign(d, ft)) + fdiv(m, t);
             else t = (fdiv(m, s + t) + fdiv(m, r + l)) * (1.0f + a);
             const float l2 = la_sqrt(t * t + 4.0f);
-#if RTG_EXP_LARTG_RCP64
-            const Rcp rl = rcp64(l2);
-            {
-                const float num[2] = {2.0f, t};
-                float quo[2];
-                mulr_k<2>(num, rl, quo);
-                crt = quo[0];
-                srt = quo[1];
-            }
-            const Rcp ra = rcp64(a);
-            const float num[2] = {crt + srt * m, fdiv(ht, ft) * srt};
-            float quo[2];
-            mulr_k<2>(num, ra, quo);
-            clt = quo[0];
-            slt = quo[1];
-#else
             crt = fdiv(2.0f, l2);
             srt = fdiv(t, l2);
             clt = fdiv(crt + srt * m, a);
             slt = fdiv(fdiv(ht, ft) * srt, a);
-#endif
         }
     }
     if (swap) { csl = srt; snl = crt; csr = slt; snr = clt; }
@@ -1147,6 +1096,52 @@ RTG_DEV void u_rot(Svd3 &z, bool p1, float c, float s)
         z.u[k] = p1 ? z.u[k] : x;
         z.u[k + 3] = p1 ? x : y;
         z.u[k + 6] = p1 ? y : z.u[k + 6];
+    }
+}
+// the end of SBDSQR: singular values made positive, then sorted decreasing, with their VT rows / U columns
+RTG_DEV void la_bdsqr3_sort(float &d1, float &d2, float &d3, Svd3 &z)
+{
+    // singular values made positive (VT rows negated), then sorted decreasing (SBDSQR :160-190)
+    if (d1 < 0.0f) { d1 = -d1; z.vt[0] = -z.vt[0]; z.vt[3] = -z.vt[3]; z.vt[6] = -z.vt[6]; }
+    if (d2 < 0.0f) { d2 = -d2; z.vt[1] = -z.vt[1]; z.vt[4] = -z.vt[4]; z.vt[7] = -z.vt[7]; }
+    if (d3 < 0.0f) { d3 = -d3; z.vt[2] = -z.vt[2]; z.vt[5] = -z.vt[5]; z.vt[8] = -z.vt[8]; }
+    // pass 1: smallest of (d1, d2, d3), ties to the later index, moves to position 3
+    {
+        int isub = 1;
+        float mn = d1;
+        if (d2 <= mn) { isub = 2; mn = d2; }
+        if (d3 <= mn) { isub = 3; mn = d3; }
+        const bool s1 = isub == 1, s2 = isub == 2;
+        d1 = s1 ? d3 : d1;
+        d2 = s2 ? d3 : d2;
+        d3 = mn;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float v0 = z.vt[3 * k], v1 = z.vt[1 + 3 * k], v2 = z.vt[2 + 3 * k];
+            z.vt[3 * k] = s1 ? v2 : v0;
+            z.vt[1 + 3 * k] = s2 ? v2 : v1;
+            z.vt[2 + 3 * k] = s1 ? v0 : (s2 ? v1 : v2);
+            const float u0 = z.u[k], u1 = z.u[k + 3], u2 = z.u[k + 6];
+            z.u[k] = s1 ? u2 : u0;
+            z.u[k + 3] = s2 ? u2 : u1;
+            z.u[k + 6] = s1 ? u0 : (s2 ? u1 : u2);
+        }
+    }
+    // pass 2: smaller of (d1, d2), ties to d2, moves to position 2
+    {
+        const bool sw = !(d2 <= d1);
+        const float t0 = d1;
+        d1 = sw ? d2 : d1;
+        d2 = sw ? t0 : d2;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float v0 = z.vt[3 * k], v1 = z.vt[1 + 3 * k];
+            z.vt[3 * k] = sw ? v1 : v0;
+            z.vt[1 + 3 * k] = sw ? v0 : v1;
+            const float u0 = z.u[k], u1 = z.u[k + 3];
+            z.u[k] = sw ? u1 : u0;
+            z.u[k + 3] = sw ? u0 : u1;
+        }
     }
 }
 // SBDSQR('U', 3, ncvt = 3, nru = 3, ncc = 0) from U = VT = I (SBDSDC / SLASDQ), n = 3 specialised: the only
@@ -1273,83 +1268,20 @@ RTG_DEV void la_bdsqr3(float &d1, float &d2, float &d3, float e1, float e2, Svd3
         vt_rot(z, p1, cosr, sinr);
         u_rot(z, p1, cosl, sinl);
     }
-    // singular values made positive (VT rows negated), then sorted decreasing (SBDSQR :160-190)
-    if (d1 < 0.0f) { d1 = -d1; z.vt[0] = -z.vt[0]; z.vt[3] = -z.vt[3]; z.vt[6] = -z.vt[6]; }
-    if (d2 < 0.0f) { d2 = -d2; z.vt[1] = -z.vt[1]; z.vt[4] = -z.vt[4]; z.vt[7] = -z.vt[7]; }
-    if (d3 < 0.0f) { d3 = -d3; z.vt[2] = -z.vt[2]; z.vt[5] = -z.vt[5]; z.vt[8] = -z.vt[8]; }
-    // pass 1: smallest of (d1, d2, d3), ties to the later index, moves to position 3
-    {
-        int isub = 1;
-        float mn = d1;
-        if (d2 <= mn) { isub = 2; mn = d2; }
-        if (d3 <= mn) { isub = 3; mn = d3; }
-        const bool s1 = isub == 1, s2 = isub == 2;
-        d1 = s1 ? d3 : d1;
-        d2 = s2 ? d3 : d2;
-        d3 = mn;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float v0 = z.vt[3 * k], v1 = z.vt[1 + 3 * k], v2 = z.vt[2 + 3 * k];
-            z.vt[3 * k] = s1 ? v2 : v0;
-            z.vt[1 + 3 * k] = s2 ? v2 : v1;
-            z.vt[2 + 3 * k] = s1 ? v0 : (s2 ? v1 : v2);
-            const float u0 = z.u[k], u1 = z.u[k + 3], u2 = z.u[k + 6];
-            z.u[k] = s1 ? u2 : u0;
-            z.u[k + 3] = s2 ? u2 : u1;
-            z.u[k + 6] = s1 ? u0 : (s2 ? u1 : u2);
-        }
-    }
-    // pass 2: smaller of (d1, d2), ties to d2, moves to position 2
-    {
-        const bool sw = !(d2 <= d1);
-        const float t0 = d1;
-        d1 = sw ? d2 : d1;
-        d2 = sw ? t0 : d2;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float v0 = z.vt[3 * k], v1 = z.vt[1 + 3 * k];
-            z.vt[3 * k] = sw ? v1 : v0;
-            z.vt[1 + 3 * k] = sw ? v0 : v1;
-            const float u0 = z.u[k], u1 = z.u[k + 3];
-            z.u[k] = sw ? u1 : u0;
-            z.u[k + 3] = sw ? u0 : u1;
-        }
-    }
+    la_bdsqr3_sort(d1, d2, d3, z);
 }
 // Stage marks for the timestamp measurement builds (RTG_EXP_TIMESTAMPS): hook(k) at a stage boundary, a no-op otherwise.
 // cal_joint_quat: 0 A formed, 1 rotation done; la_gesdd3: 10 bidiagonal form (SGEBD2) done, 11 SBDSQR done.
 struct NoHook {
     RTG_DEV void operator()(int) const {}
 };
-// SGESDD(JOBZ='A') of a 3x3 (column-major a, overwritten): U and VT (column-major) in z
-template <typename Hook = NoHook>
-RTG_DEV void la_gesdd3(float a[9], Svd3 &z, const Hook &hook = Hook{})
+// SGEBD2 after H_0: G_0 from the right (v = (1, a6)), then i = 1: H_1 from the left (v = (1, a5)) on column 2;
+// G_1 = I (one-element reflector), i = 2: H_2 = I
+RTG_DEV void la_gebd2_rest(float a[9], float &tp0, float &tq1, float &e1, float &d2, float &e2, float &d3)
 {
-    const float smlnum = 9.09494702e-13f, bignum = 1.0f / smlnum;   // sqrt(slamch('S')) / slamch('P') = 2^-40
-    float anrm = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) anrm = fmaxf(anrm, fabsf(a[i]));
-    if (__builtin_expect((anrm > 0.0f && anrm < smlnum) || anrm > bignum, 0)) {
-        const float mul = anrm < smlnum ? fdiv(smlnum, anrm) : fdiv(bignum, anrm);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) a[i] *= mul;
-    }
-    // SGEBD2, i = 0: H_0 from the left (v = (1, a1, a2)), G_0 from the right (v = (1, a6))
-    const float tq0 = la_larfg<2>(a[0], a[1], a[2]);
-    const float d1 = a[0];
-    if (tq0 != 0.0f) {
-#pragma unroll
-        for (int j = 1; j < 3; ++j) {
-            const float w = a[3 * j] + (a[1 + 3 * j] * a[1] + a[2 + 3 * j] * a[2]);
-            const float tw = -(tq0 * w);
-            a[3 * j] = __builtin_fmaf(1.0f, tw, a[3 * j]);
-            a[1 + 3 * j] = __builtin_fmaf(a[1], tw, a[1 + 3 * j]);
-            a[2 + 3 * j] = __builtin_fmaf(a[2], tw, a[2 + 3 * j]);
-        }
-    }
     float dum = 0.0f;
-    const float tp0 = la_larfg<1>(a[3], a[6], dum);
-    const float e1 = a[3];
+    tp0 = la_larfg<1>(a[3], a[6], dum);
+    e1 = a[3];
     if (tp0 != 0.0f) {
         const float tv1 = -(tp0 * 1.0f), tv2 = -(tp0 * a[6]);
 #pragma unroll
@@ -1360,23 +1292,20 @@ RTG_DEV void la_gesdd3(float a[9], Svd3 &z, const Hook &hook = Hook{})
         }
     }
     // i = 1: H_1 from the left (v = (1, a5)) on column 2; G_1 = I (one-element reflector)
-    const float tq1 = la_larfg<1>(a[4], a[5], dum);
-    const float d2 = a[4];
+    tq1 = la_larfg<1>(a[4], a[5], dum);
+    d2 = a[4];
     if (tq1 != 0.0f) {
         const float w = a[7] + a[8] * a[5];
         const float tw = -(tq1 * w);
         a[7] = __builtin_fmaf(1.0f, tw, a[7]);
         a[8] = __builtin_fmaf(a[5], tw, a[8]);
     }
-    const float e2 = a[7];
-    const float d3 = a[8];   // i = 2: H_2 = I
-    hook(10);
-    // SBDSDC('U','I') -> SLASDQ -> SBDSQR with U = VT = I
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { z.u[i] = (i % 4 == 0) ? 1.0f : 0.0f; z.vt[i] = z.u[i]; }
-    float s1 = d1, s2 = d2, s3 = d3;
-    la_bdsqr3(s1, s2, s3, e1, e2, z);
-    hook(11);
+    e2 = a[7];
+    d3 = a[8];   // i = 2: H_2 = I
+}
+// SORMBR of the 3x3 SGESDD: U := H_0 H_1 U, VT := VT G_0^T
+RTG_DEV void la_ormbr3(const float a[9], float tq0, float tq1, float tp0, Svd3 &z)
+{
     // SORMBR('Q','L','N'): U := H_0 H_1 U (H_1 first), the unit row fused as fma(-tau, w, c)
     if (tq1 != 0.0f) {
 #pragma unroll
@@ -1408,23 +1337,116 @@ RTG_DEV void la_gesdd3(float a[9], Svd3 &z, const Hook &hook = Hook{})
         }
     }
 }
+// SGESDD(JOBZ='A') of a 3x3 (column-major a, overwritten): U and VT (column-major) in z
+template <typename Hook = NoHook>
+RTG_DEV void la_gesdd3(float a[9], Svd3 &z, const Hook &hook = Hook{})
+{
+    const float smlnum = 9.09494702e-13f, bignum = 1.0f / smlnum;   // sqrt(slamch('S')) / slamch('P') = 2^-40
+    float anrm = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) anrm = fmaxf(anrm, fabsf(a[i]));
+    if (__builtin_expect((anrm > 0.0f && anrm < smlnum) || anrm > bignum, 0)) {
+        const float mul = anrm < smlnum ? fdiv(smlnum, anrm) : fdiv(bignum, anrm);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) a[i] *= mul;
+    }
+    // SGEBD2, i = 0: H_0 from the left (v = (1, a1, a2)), G_0 from the right (v = (1, a6))
+    const float tq0 = la_larfg<2>(a[0], a[1], a[2]);
+    const float d1 = a[0];
+    if (tq0 != 0.0f) {
+#pragma unroll
+        for (int j = 1; j < 3; ++j) {
+            const float w = a[3 * j] + (a[1 + 3 * j] * a[1] + a[2 + 3 * j] * a[2]);
+            const float tw = -(tq0 * w);
+            a[3 * j] = __builtin_fmaf(1.0f, tw, a[3 * j]);
+            a[1 + 3 * j] = __builtin_fmaf(a[1], tw, a[1 + 3 * j]);
+            a[2 + 3 * j] = __builtin_fmaf(a[2], tw, a[2 + 3 * j]);
+        }
+    }
+    float tp0, tq1, e1, d2, e2, d3;
+    la_gebd2_rest(a, tp0, tq1, e1, d2, e2, d3);
+    hook(10);
+    // SBDSDC('U','I') -> SLASDQ -> SBDSQR with U = VT = I
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { z.u[i] = (i % 4 == 0) ? 1.0f : 0.0f; z.vt[i] = z.u[i]; }
+    float s1 = d1, s2 = d2, s3 = d3;
+    la_bdsqr3(s1, s2, s3, e1, e2, z);
+    hook(11);
+    la_ormbr3(a, tq0, tq1, tp0, z);
+}
+// ---- SGESDD of a 3x3 whose first column is +-0 (a[0..2], not read): the FULL_BODY_POS torso fit, whose zero-pose
+// vectors all have x = 0, so column 0 of A = M^T Z is +-0 for finite M.  la_gesdd3 takes one fixed path on such a
+// matrix, through branches it treats as rare; this runs that path alone -- the same operations on the same operands,
+// minus those whose result is known:
+//   * H_0: SLARFG(3, +-0, (+-0, +-0)) has xnorm = 0 and returns tau = 0 after two SLAPY2 (two divisions, two square
+//     roots); H_0 = I, d1 = a[0] = +-0, and columns 1..2 go on unchanged.
+//   * SBDSQR: sminoa = |d1| = 0, so thresh = max(tol 0, 18 unfl) = 18 unfl.  With |e2| > thresh, |e1| > thresh and
+//     d3 != 0 the block is (1, 3) and |d1| = 0 < |d3| chases bottom to top: (D1, D2, D3; E1, E2) = (d3, d2, +-0; e2, e1).
+//     The convergence tests: |E2| <= tol |D3| = 0 is false (|e1| > thresh); |E1| <= tol |D1| must be false (tested);
+//     mu2 = |D2| RN(|D1| / (|D1| + |E1|)) <= |D2| (the quotient is <= 1 and RN is monotone), so |E2| > tol |D2| (tested)
+//     makes |E2| <= tol mu2 false; mu3 = |D3| q = 0 q = 0 for the finite q, so smin = 0, 3 tol (0 / smax) = 0 <= eps
+//     and the shift is 0.  The zero-shift sweep's fourth SLARTG has g = D3 cs = +-0 (cs finite): c = 1, s = +0, r = f
+//     -- after its common path's square root and two divisions.  Then D3 = (+-0 cc) 1 = +-0, E2 = +-0 (+0) -> +0 by the
+//     threshold test.  Back in (d, e) order e1 = 0, e2 = bs r: the next pass either drops e2 (|e2| <= thresh: m = 2,
+//     then |e1| = 0 ends it with no block) or splits at e1 = 0 into the 2x2 block (2, 3) -- per lane, as la_bdsqr3's
+//     blk.  The rotations act on U = VT = I with the pair index known (vt_rot / u_rot's selects fold away).
+//   * d1 stays +-0 to the end and its sign is never read: d1 < 0 is false for -0, the sort compares values, and
+//     only U and VT leave the routine.  So the sign of the zero column (the signs of M's entries, or a -0 in the
+//     zero pose) cannot reach an output.
+// Everything is finite on this path: the caller tests M (and bounds Z), SGESDD's rescaling then holds |a| <= 2^40,
+// and SLARFG / SLARTG / SLASV2 return finite values for such inputs.  The assumptions are tested per lane and
+// voted per wave: on a miss of ANY active lane the function returns false before z is written and the whole wave
+// runs la_gesdd3 -- never a divergent second copy.  `fin`: this lane's M is finite and small enough (caller).
+template <typename Hook = NoHook>
+RTG_DEV bool la_gesdd3_x0(float a[9], bool fin, Svd3 &z, const Hook &hook = Hook{})
+{
+    const float smlnum = 9.09494702e-13f, bignum = 1.0f / smlnum;
+    const float eps = 5.96046448e-08f, tol = 10.0f * eps, unfl = 1.17549435e-38f;
+    float anrm = 0.0f;
+#pragma unroll
+    for (int i = 3; i < 9; ++i) anrm = fmaxf(anrm, fabsf(a[i]));
+    if (__builtin_expect((anrm > 0.0f && anrm < smlnum) || anrm > bignum, 0)) {
+        const float mul = anrm < smlnum ? fdiv(smlnum, anrm) : fdiv(bignum, anrm);
+#pragma unroll
+        for (int i = 3; i < 9; ++i) a[i] *= mul;
+    }
+    float tp0, tq1, e1, d2, e2, d3;
+    la_gebd2_rest(a, tp0, tq1, e1, d2, e2, d3);
+    hook(10);
+    const float thresh = 6.0f * (3.0f * (3.0f * unfl));
+    const bool ok = fin && fabsf(e2) > thresh && fabsf(e1) > thresh && fabsf(d3) > 0.0f &&
+                    !(fabsf(e2) <= tol * fabsf(d3)) && fabsf(e1) > tol * fabsf(d2);
+    if (__builtin_amdgcn_ballot_w64(!ok) != 0) return false;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { z.u[i] = (i % 4 == 0) ? 1.0f : 0.0f; z.vt[i] = z.u[i]; }
+    // the zero-shift sweep on (d3, d2, +-0; e2, e1); its fourth rotation is (1, +0) and D2 = its f
+    float ac, as, bc, bs, cc, cs, r, s3;
+    la_lartg(d3, e2, ac, as, r);
+    la_lartg(r, d2 * as, bc, bs, s3);
+    la_lartg(d2 * ac, e1, cc, cs, r);
+    float s1 = 0.0f, s2 = bc * r;
+    e2 = bs * r;
+    vt_rot(z, true, bc, -bs);
+    vt_rot(z, false, 1.0f, -0.0f);
+    u_rot(z, true, ac, -as);
+    u_rot(z, false, cc, -cs);
+    if (!(fabsf(e2) <= thresh)) {   // 2x2 block (2, 3)
+        float sigmn, sigmx, sinr, cosr, sinl, cosl;
+        la_lasv2(s2, e2, s3, sigmn, sigmx, sinr, cosr, sinl, cosl);
+        s2 = sigmx;
+        s3 = sigmn;
+        vt_rot(z, true, cosr, sinr);
+        u_rot(z, true, cosl, sinl);
+    }
+    la_bdsqr3_sort(s1, s2, s3, z);
+    hook(11);
+    la_ormbr3(a, 0.0f, tq1, tp0, z);
+    return true;
+}
 // transform3d.py:40-45: R = U Vt ((p0 + p1) + p2, torch's bmm order); det(R) < 0 -> Vt[-1,:] *= -1; R = U Vt.
 // A and R row-major.  det only decides a sign (|det| = 1 up to rounding), taken in float64.
-template <typename Hook = NoHook>
-RTG_DEV void kabsch_rot(const float A[9], float R[9], const Hook &hook = Hook{})
+RTG_DEV void kabsch_of_svd(Svd3 &z, float R[9])
 {
-#if RTG_EXP_STUB_SVD
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0f : A[i] * 1e-3f;
-    return;
-#endif
-    float a[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) a[i + 3 * k] = A[i * 3 + k];
-    Svd3 z;
-    la_gesdd3(a, z, hook);
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -1443,6 +1465,23 @@ RTG_DEV void kabsch_rot(const float A[9], float R[9], const Hook &hook = Hook{})
             for (int k = 0; k < 3; ++k)
                 R[i * 3 + k] = (z.u[i] * z.vt[3 * k] + z.u[i + 3] * z.vt[1 + 3 * k]) + z.u[i + 6] * z.vt[2 + 3 * k];
     }
+}
+template <typename Hook = NoHook>
+RTG_DEV void kabsch_rot(const float A[9], float R[9], const Hook &hook = Hook{})
+{
+#if RTG_EXP_STUB_SVD
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0f : A[i] * 1e-3f;
+    return;
+#endif
+    float a[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a[i + 3 * k] = A[i * 3 + k];
+    Svd3 z;
+    la_gesdd3(a, z, hook);
+    kabsch_of_svd(z, R);
 }
 
 // cal_joint_quat (transform3d.py:31-50): A = M^T Z by einsum (sequential in j, no FMA).  `hook(k)` marks the
@@ -1482,6 +1521,42 @@ RTG_DEV Q joint_quat_of_A(const float (&A)[9], const Hook &hook = Hook{}, Tab ta
     kabsch_rot(A, R, hook);
     hook(1);
     return qfrom_rotmat(R, tab);
+}
+// The torso fit when every zero vector has x = 0 (SolverConsts::torso_x0): A without the zero column's products,
+// then la_gesdd3_x0.  Returns false, wave-uniformly, when some active lane is off that path (non-finite or huge M --
+// form_joint_A then sees the NaN of inf * 0 in column 0 -- or one of la_gesdd3_x0's tests); the caller then runs
+// form_joint_A + joint_quat_of_A for the whole wave.  On true no A entry is NaN: |M| < 2^60 and |Z| <= 2^60 (host)
+// bound every product by 2^120 and every sum by 2^122.
+template <typename Hook = NoHook, typename Tab = NoTab>
+RTG_DEV bool torso_quat_x0(const V (&Z)[3], const V (&M)[3], Q &q, const Hook &hook = Hook{}, Tab tab = Tab{})
+{
+    float a[9];   // column-major: a[i + 3 k] = A[i][k]
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) sum += fabsf(i == 0 ? M[j].x : (i == 1 ? M[j].y : M[j].z));
+#pragma unroll
+        for (int k = 1; k < 3; ++k) {
+            float acc = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float mi = i == 0 ? M[j].x : (i == 1 ? M[j].y : M[j].z);
+                const float pr = mi * (k == 1 ? Z[j].y : Z[j].z);
+                acc = j == 0 ? pr : acc + pr;   // form_joint_A's order
+            }
+            a[i + 3 * k] = acc;
+        }
+        a[i] = 0.0f;
+    }
+    hook(0);
+    Svd3 z;
+    if (!la_gesdd3_x0(a, sum < 0x1p60f, z, hook)) return false;
+    float R[9];
+    kabsch_of_svd(z, R);
+    hook(1);
+    q = qfrom_rotmat(R, tab);
+    return true;
 }
 template <int N, typename Hook = NoHook, typename Tab = NoTab>
 RTG_DEV Q cal_joint_quat(const V (&Z)[N], const V (&M)[N], bool &svd_nan, const Hook &hook = Hook{}, Tab tab = Tab{})

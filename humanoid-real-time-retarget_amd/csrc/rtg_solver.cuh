@@ -613,13 +613,21 @@ __global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(S
         // RTG_SIDES_SHARED_FIT: each wave's first fit (left: torso, right: right wrist) forms its A, then both run ONE
         // inlined copy of the SVD's code (the same operations on the same A as cal_joint_quat)
         constexpr bool kSharedFit = RTG_SIDES_SHARED_FIT >= (SOA ? 1 : 2);
+        // RTG_TORSO_X0: a zero pose whose torso vectors have x = 0 (C.torso_x0) takes the zero-column fit; a wave with
+        // a lane off its path gets false back and runs the general fit (wave-uniform either way)
+        constexpr bool kTorsoX0 = RTG_TORSO_X0 && !RTG_EXP_STUB_SVD;
         if (live) {
             if constexpr (kSharedFit) {
                 float A[9];
+                Q q = qident();
+                bool general = true;
                 if (!side) {
                     const V b10 = b.p3(10);
                     const V Mt[3] = {vsub(b.p3(17), b10), vsub(b.p3(13), b10), vsub(b.p3(11), b10)};
-                    fit1_nan = form_joint_A<3>(C.Zt, Mt, A);
+                    if constexpr (kTorsoX0) {
+                        if (C.torso_x0) general = !torso_quat_x0(C.Zt, Mt, q, hook1, tabF);
+                    }
+                    if (general) fit1_nan = form_joint_A<3>(C.Zt, Mt, A);
                 } else {
                     apL = load_arm<0>(b);
                     apR = load_arm<1>(b);
@@ -630,7 +638,7 @@ __global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(S
                                     vsub(H.p3(17), h0)};
                     fit1_nan = form_joint_A<5>(C.Zr, M, A);
                 }
-                const Q q = joint_quat_of_A(A, hook1, tabF);
+                if (general) q = joint_quat_of_A(A, hook1, tabF);
                 if (!side) {
                     R10 = q;
                     storso[r] = make_float4(R10.x, R10.y, R10.z, R10.w);
@@ -640,7 +648,15 @@ __global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(S
             } else {
                 bool nan = false;
                 if (!side) {
-                    R10 = fbp_torso(C, b, nan, hook1, tabF);
+                    bool general = true;
+                    if constexpr (kTorsoX0) {
+                        if (C.torso_x0) {
+                            const V b10 = b.p3(10);
+                            const V Mt[3] = {vsub(b.p3(17), b10), vsub(b.p3(13), b10), vsub(b.p3(11), b10)};
+                            general = !torso_quat_x0(C.Zt, Mt, R10, hook1, tabF);
+                        }
+                    }
+                    if (general) R10 = fbp_torso(C, b, nan, hook1, tabF);
                     storso[r] = make_float4(R10.x, R10.y, R10.z, R10.w);
                     fit1_nan = nan;
                 } else {
