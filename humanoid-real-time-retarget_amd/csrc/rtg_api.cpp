@@ -790,6 +790,20 @@ int rtg_box_probe(double *out, int32_t n_out, rtg_stream_t stream)
     return rc;
 }
 
+// ---------------------------------------------------------------- side-kernel residency
+int rtg_side_kernel_residency(int kind, int precise_gripper, int layout, int32_t *blocks_per_cu)
+{
+    if (!blocks_per_cu) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_side_kernel_residency: blocks_per_cu is NULL");
+    if (kind < RTG_SOLVER_FULL_BODY_POS || kind > RTG_SOLVER_BODY_ROT)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_side_kernel_residency: bad solver kind %d", kind);
+    if (layout != RTG_LAYOUT_AOS && layout != RTG_LAYOUT_SOA)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_side_kernel_residency: bad layout %d", layout);
+    int n = 0;
+    RTG_TRY(side_kernel_residency(kind, precise_gripper != 0, layout, &n), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
+    *blocks_per_cu = n;
+    return RTG_OK;
+}
+
 // ---------------------------------------------------------------- synthetic input
 int rtg_synth_full_body_f32(rtg_topology_t t, uint64_t seed, int64_t off, int64_t B, int layout, float *body,
                             float *lh, float *rh, float *body_rot, rtg_stream_t stream)

@@ -75,6 +75,9 @@ hipError_t launch_frame_server(int precise, const SolverConsts &C, const float *
 hipError_t launch_retarget(int kind, int precise, const SolverConsts &C, const float *in0, const float *in1,
                            const float *in2, const float *in3, int64_t B, int layout, float *dof, float *local_rot,
                            float *body_rot, hipStream_t s);
+// resident blocks per CU of the k_solve_sides instantiation that launch_retarget picks for a batch beyond the small-batch
+// kernels (hipOccupancyMaxActiveBlocksPerMultiprocessor)
+hipError_t side_kernel_residency(int kind, int precise, int layout, int *blocks_per_cu);
 hipError_t launch_fk(const TopoView &T, bool state, const float *lr, const float *rt, int64_t B, float *gr, float *gp,
                      hipStream_t s);
 hipError_t launch_local_rotation(const TopoView &T, bool state, const float *g, int64_t B, float *l, hipStream_t s);

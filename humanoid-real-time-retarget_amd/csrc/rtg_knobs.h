@@ -7,7 +7,9 @@
 
 // ---- used by rtg_solver.cuh
 #ifndef RTG_SIDES_TILES
-#define RTG_SIDES_TILES 2   // 64-frame tiles (two waves each) per k_solve_sides block
+#define RTG_SIDES_TILES 2   // 64-frame tiles (two waves each) per k_solve_sides block (round 8 sweep at five waves per
+                            // SIMD: 1 tile 96.4-98.6 us per lone SoA launch against 93.8-94.7 for the parent in the same
+                            // session, bench.py 3.77-3.79 G frames/s against 3.71-3.84 with 2; profiles/r08/)
 #endif
 #ifndef RTG_SIDES_SPLIT_READOUT
 #define RTG_SIDES_SPLIT_READOUT 0   // FULL_BODY_POS side kernel: the left wave also reads out the right chain's slots
@@ -25,8 +27,22 @@
 #define RTG_AOS_PRELOAD_TIPS 1   // AoS inputs: the gripper's hand points loaded with the wrist fit's (125 VGPRs, still
                                  // 4 waves/SIMD; AoS 111.2 vs 113.5 us, SoA unchanged, profiles/r06/arms2/)
 #endif
-#ifndef RTG_SIDES_WAVES
-#define RTG_SIDES_WAVES 1   // min waves per SIMD for the side kernel (1: the compiler picks; measured best)
+#ifndef RTG_SIDES_SOA_WAVES
+#define RTG_SIDES_SOA_WAVES 5   // k_solve_sides FULL_BODY_POS, SoA inputs: min waves per SIMD asked of the compiler (1: it
+                                // picks, 4 at 101 VGPRs; 5: 96 VGPRs, 16 B/lane of spills, and the 31,024-B LDS lets
+                                // five blocks share a CU).  The other instantiations (AoS, other kinds) always get 1.
+                                // bench.py (steps on two streams) 3.90-3.95 vs 3.73-3.74 G frames/s with 1 and 3.70-3.75
+                                // for the parent; a lone launch 92.8-94.6 vs 93.3-94.5 vs 93.0-94.4 us: 2048 blocks fill
+                                // 1280 slots 1.6 times, so only overlapping launches gain (profiles/r08/ab_*.log)
+#endif
+#ifndef RTG_SIDES_UNIFORM_WAVE
+#define RTG_SIDES_UNIFORM_WAVE 3   // k_solve_sides: the wave index (so the side and the tile) read through readfirstlane, a
+                                   // bit mask: 1 FULL_BODY_POS SoA, 2 FULL_BODY_POS AoS, 4 the other kinds.  The compiler
+                                   // then keeps the side in an SGPR and branches on it with scalar branches, where it had
+                                   // kept it and three values derived from it in VGPRs (spilled at 96 VGPRs: 32 -> 16
+                                   // B/lane).  At five waves bench.py 3.90-3.95 vs 3.80-3.87 G frames/s without, a lone SoA
+                                   // launch 92.8-94.6 vs 94.3-96.3 us, AoS 104.3-105.2 vs 104.8-106.7; the other kinds
+                                   // were not measured with it (profiles/r08/ab_*.log, build new_u0)
 #endif
 #ifndef RTG_QUAD8_MAX_B
 #define RTG_QUAD8_MAX_B 2048   // 2 <= B <= this: k_fbp_quad with 8 frames per block (one block per CU up to 2048)

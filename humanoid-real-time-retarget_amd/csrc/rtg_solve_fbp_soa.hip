@@ -12,4 +12,10 @@ hipError_t launch_fbp_soa(int precise, const SolverConsts &C, const float *in0, 
                : launch_kind<RTG_SOLVER_FULL_BODY_POS, false, true>(C, in0, in1, in2, nullptr, B, dof, local_rot, body_rot, s);
 }
 
+hipError_t residency_fbp_soa(int precise, int *blocks_per_cu)
+{
+    return precise ? side_residency<RTG_SOLVER_FULL_BODY_POS, true, true>(blocks_per_cu)
+                   : side_residency<RTG_SOLVER_FULL_BODY_POS, false, true>(blocks_per_cu);
+}
+
 }  // namespace rtg

@@ -63,4 +63,25 @@ hipError_t launch_retarget(int kind, int precise, const SolverConsts &C, const f
     }
 }
 
+template <int KIND>
+static hipError_t residency_other(int layout, int *blocks_per_cu)
+{
+    return layout == RTG_LAYOUT_SOA ? side_residency<KIND, false, true>(blocks_per_cu)
+                                    : side_residency<KIND, false, false>(blocks_per_cu);
+}
+
+hipError_t side_kernel_residency(int kind, int precise, int layout, int *blocks_per_cu)
+{
+    switch (kind) {
+    case RTG_SOLVER_FULL_BODY_POS:
+        return layout == RTG_LAYOUT_SOA ? residency_fbp_soa(precise, blocks_per_cu) : residency_fbp_aos(precise, blocks_per_cu);
+    case RTG_SOLVER_UPPER_BODY:
+        return residency_other<RTG_SOLVER_UPPER_BODY>(layout, blocks_per_cu);
+    case RTG_SOLVER_FULL_BODY_ROT:
+        return residency_other<RTG_SOLVER_FULL_BODY_ROT>(layout, blocks_per_cu);
+    default:
+        return residency_other<RTG_SOLVER_BODY_ROT>(layout, blocks_per_cu);
+    }
+}
+
 }  // namespace rtg

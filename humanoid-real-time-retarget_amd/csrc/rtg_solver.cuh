@@ -93,10 +93,12 @@ struct Emit {
     static RTG_DEV void wait_words() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 };
 
-RTG_DEV void emit_fixed_links(const Emit &E, bool write_lr = true)
+// k0: the first fixed DOF written (k_solve_sides keeps a hand-over slot in the row's first dwords and zeroes them itself)
+RTG_DEV void emit_fixed_links(const Emit &E, bool write_lr = true, int k0 = 0)
 {
 #pragma unroll
-    for (int k = 0; k < 11; ++k) E.row[k] = 0.0f;
+    for (int k = 0; k < 11; ++k)
+        if (k >= k0) E.row[k] = 0.0f;
     E.row[29] = 0.0f;
     if (E.lr && write_lr) {
 #pragma unroll
@@ -534,18 +536,37 @@ RTG_DEV void lds_wait(int *flag, uint32_t *err)
     if ((threadIdx.x & 63) == 0) report_device_error(err, RTG_DEVERR_HANDOVER_TIMEOUT);
 }
 
+// The hand-over slot of a frame (FULL_BODY_POS: R10 left -> right wave, then the left chain right -> left; UPPER_BODY:
+// R10 left -> right) is the first four dwords of the frame's own DOF row: DOFs 0-3 are fixed zeros, which the slot's
+// last reader writes once it has read (the same lane: its LDS operations execute in order), so the row is whole
+// before the tile is stored.  The row pitch is odd: four b32 accesses, conflict-free, not one b128.
+constexpr int kSlotDwords = 4;
+RTG_DEV void slot_put(float *row, Q q) { row[0] = q.x; row[1] = q.y; row[2] = q.z; row[3] = q.w; }
+RTG_DEV Q slot_get(const float *row) { return Q{row[0], row[1], row[2], row[3]}; }
+RTG_DEV void slot_clear(float *row) { row[0] = 0.0f; row[1] = 0.0f; row[2] = 0.0f; row[3] = 0.0f; }
+
+// min waves per SIMD asked of the compiler: RTG_SIDES_SOA_WAVES for FULL_BODY_POS on SoA inputs, else the compiler picks
+template <int KIND, bool SOA>
+constexpr int side_min_waves() { return KIND == RTG_SOLVER_FULL_BODY_POS && SOA ? RTG_SIDES_SOA_WAVES : 1; }
+// LDS budget of the SoA FULL_BODY_POS instantiation: five 256-thread blocks per CU (160 KiB / 5 = 32768 B) whether LDS
+// is granted in 256-byte or 1280-byte units
+constexpr int kSideLdsBudgetSoa = 32000 * kSideTiles / 2;
+
 template <int KIND, bool PRECISE, bool SOA>
-__global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(SolverConsts C, const float *__restrict__ in0,
+__global__ __launch_bounds__(kSideThreads, (side_min_waves<KIND, SOA>())) void k_solve_sides(
+                                                     SolverConsts C, const float *__restrict__ in0,
                                                      const float *__restrict__ in1, const float *__restrict__ in2,
                                                      const float *__restrict__ in3, int64_t B,
                                                      float *__restrict__ dof, float *__restrict__ local_rot,
                                                      float *__restrict__ body_rot)
 {
     __shared__ float sdof[kSideFrames * kDofStride];
-    __shared__ float4 storso[kSideFrames];   // FULL_BODY_POS: R10 left -> right wave, then the left chain right -> left
     __shared__ float2 sst[kSideTiles * 14 * 64];   // exp-map stash, [tile][slot][lane]
     __shared__ uint8_t sstat[2][kSideFrames];   // each side's frame-status bits (kSt*)
-    const int w = threadIdx.x >> 6, side = w & 1, lane = threadIdx.x & 63;
+    // the wave index is the same in every lane; RTG_SIDES_UNIFORM_WAVE says so to the compiler (an SGPR, scalar branches)
+    constexpr bool kUniformWave = (RTG_SIDES_UNIFORM_WAVE & (KIND != RTG_SOLVER_FULL_BODY_POS ? 4 : (SOA ? 1 : 2))) != 0;
+    const int w = kUniformWave ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x >> 6);
+    const int side = w & 1, lane = threadIdx.x & 63;
     const int r = (w >> 1) * 64 + lane;   // tile row
     const int64_t f0 = (int64_t)blockIdx.x * kSideFrames, f = f0 + r;
     const bool live = f < B;
@@ -595,6 +616,8 @@ __global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(S
         constexpr int kTab = SOA ? RTG_SIDES_UNIT_TAB : RTG_SIDES_UNIT_TAB_AOS;
         __shared__ UnitEnt sut[2 * kUnitTabK + 1];
         if constexpr (kTab != 0) unit_tab_fill(sut, (int)threadIdx.x);
+        static_assert(!SOA || sizeof(sdof) + sizeof(sst) + sizeof(sstat) + sizeof(sflag) + sizeof(sut) <= kSideLdsBudgetSoa,
+                      "the SoA FULL_BODY_POS side kernel's LDS no longer lets five blocks share a CU");
         const auto tabF = TabSel<(kTab & 1) != 0>::get(sut);
         const auto tabA = TabSel<(kTab & 2) != 0>::get(sut);
         const auto tabE = TabSel<(kTab & 4) != 0>::get(sut);
@@ -641,7 +664,7 @@ __global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(S
                 if (general) q = joint_quat_of_A(A, hook1, tabF);
                 if (!side) {
                     R10 = q;
-                    storso[r] = make_float4(R10.x, R10.y, R10.z, R10.w);
+                    slot_put(E.row, R10);
                 } else {
                     W = q;
                 }
@@ -657,7 +680,7 @@ __global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(S
                         }
                     }
                     if (general) R10 = fbp_torso(C, b, nan, hook1, tabF);
-                    storso[r] = make_float4(R10.x, R10.y, R10.z, R10.w);
+                    slot_put(E.row, R10);
                     fit1_nan = nan;
                 } else {
                     apL = load_arm<0>(b);
@@ -670,7 +693,7 @@ __global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(S
         }
         TS(3);
         if (!side) {
-            // R10 of this tile is in storso.  RTG_EXP_SKIP_SIGNAL (measurement knob): block 0's first tile never
+            // R10 of this tile is in the rows' slots.  RTG_EXP_SKIP_SIGNAL (measurement knob): block 0's first tile never
             // raises it, so its right wave times out -- the error-word report is tested on that build
             if (!(RTG_EXP_SKIP_SIGNAL && blockIdx.x == 0 && w == 0)) lds_signal(&fl[0]);
         } else {
@@ -682,28 +705,26 @@ __global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(S
 #if RTG_SIDES_ARMS2
             // both arm chains in one instruction stream (fbp_arms2), then both hand-overs
             if (live) {
-                const float4 t = storso[r];   // read R10 before the same lane overwrites the slot with the chain
-                R10 = Q{t.x, t.y, t.z, t.w};
+                R10 = slot_get(E.row);   // read R10 before the same lane overwrites the slot with the chain
                 Q cl;
                 fbp_arms2(C, apL, apR, R10, E, cl, chain, tabA);
-                storso[r] = make_float4(cl.x, cl.y, cl.z, cl.w);
+                slot_put(E.row, cl);
             }
             if (wds) Emit::wait_words();   // the left chain's table words (slots 0-3) have landed in LDS
             lds_signal(&fl[1]);   // the left chain and its exp-map slots 0-3 are in LDS
             if (RTG_SIDES_SPLIT_READOUT) lds_signal(&fl[3]);   // the right chain's exp-map slots 7-10 are in LDS
 #else
             if (live) {
-                const float4 t = storso[r];   // read R10 before the same lane overwrites the slot with the chain
-                R10 = Q{t.x, t.y, t.z, t.w};
+                R10 = slot_get(E.row);   // read R10 before the same lane overwrites the slot with the chain
                 const Q cl = fbp_arm<0>(C, apL, R10, E);
-                storso[r] = make_float4(cl.x, cl.y, cl.z, cl.w);
+                slot_put(E.row, cl);
             }
             lds_signal(&fl[1]);   // the left chain and its exp-map slots 0-3 are in LDS
             if (live) chain = fbp_arm<1>(C, apR, R10, E);
             if (RTG_SIDES_SPLIT_READOUT) lds_signal(&fl[3]);   // the right chain's exp-map slots 7-10 are in LDS
 #endif
         } else if (live) {
-            emit_fixed_links(E);
+            emit_fixed_links(E, true, kSlotDwords);   // the slot's dwords stay the right wave's until the chain is read
             bool nan = false;
             if (kPreTips) tpre = load_tips(view(in1, 60));
             W = fbp_wrist_fit<0>(C, view(in1, 60), nan, hook2, tabF);
@@ -718,8 +739,9 @@ __global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(S
             if (side) {
                 euler_refused = fbp_side_after_arm<PRECISE, 1>(C, tp, R10, chain, W, E, brow, tabE);
             } else {
-                const float4 c = storso[r];
-                euler_refused = fbp_side_after_arm<PRECISE, 0>(C, tp, R10, Q{c.x, c.y, c.z, c.w}, W, E, brow, tabE);
+                const Q c = slot_get(E.row);   // the left chain; this lane was the slot's last reader: now its zeros
+                slot_clear(E.row);
+                euler_refused = fbp_side_after_arm<PRECISE, 0>(C, tp, R10, c, W, E, brow, tabE);
             }
         }
         TS(7);
@@ -788,17 +810,17 @@ __global__ __launch_bounds__(kSideThreads, RTG_SIDES_WAVES) void k_solve_sides(S
             if (live && !side) {
                 bool nan = false;
                 R10 = upper_torso(C, b, nan);
-                storso[r] = make_float4(R10.x, R10.y, R10.z, R10.w);
+                slot_put(E.row, R10);
                 st |= nan ? kStTorsoSvd : 0u;
             }
             __syncthreads();
             if (live) {
                 if (side) {
-                    const float4 t = storso[r];
-                    R10 = Q{t.x, t.y, t.z, t.w};
+                    R10 = slot_get(E.row);   // this lane is the slot's only reader: now its zeros
+                    slot_clear(E.row);
                     solve_upper_side<1>(C, b, R10, E, tab);
                 } else {
-                    emit_fixed_links(E);
+                    emit_fixed_links(E, true, kSlotDwords);
                     solve_upper_side<0>(C, b, R10, E, tab);
                 }
             }
@@ -1638,6 +1660,15 @@ static hipError_t launch_kind(const SolverConsts &C, const float *in0, const flo
                        in1, in2, in3, B, dof, local_rot, body_rot);
     return hipGetLastError();
 }
+
+// Blocks of k_solve_sides<KIND, PRECISE, SOA> that the runtime keeps resident per CU (rtg.h rtg_side_kernel_residency)
+template <int KIND, bool PRECISE, bool SOA>
+static hipError_t side_residency(int *blocks_per_cu)
+{
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_solve_sides<KIND, PRECISE, SOA>, kSideThreads, 0);
+}
+hipError_t residency_fbp_aos(int precise, int *blocks_per_cu);
+hipError_t residency_fbp_soa(int precise, int *blocks_per_cu);
 
 // FULL_BODY_POS launches, one TU per input layout
 hipError_t launch_fbp_aos(int precise, const SolverConsts &C, const float *in0, const float *in1, const float *in2,

@@ -133,6 +133,7 @@ SIGNATURES = {
     "rtg_synth_full_body_f32": (c_int, [c_void_p, c_uint64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),
     "rtg_box_probe": (c_int, [POINTER(ctypes.c_double), c_int32, c_void_p]),
+    "rtg_side_kernel_residency": (c_int, [c_int, c_int, c_int, POINTER(c_int32)]),
 }
 PROBE_FIELDS = 6   # rtg.h RTG_PROBE_FIELDS
 

@@ -511,6 +511,14 @@ def quat_as_euler(q, seq: str, degrees: bool = False):
     return out
 
 
+def side_kernel_residency(kind: int, precise_gripper: bool = False, layout: str = "aos") -> int:
+    """rtg_side_kernel_residency (rtg.h): workgroups of the solver kind's throughput kernel resident per compute unit."""
+    require_gpu()
+    n = ctypes.c_int32(0)
+    check(lib().rtg_side_kernel_residency(int(kind), int(bool(precise_gripper)), layout_code(layout), ctypes.byref(n)))
+    return int(n.value)
+
+
 def box_probe() -> dict:
     """rtg_box_probe (rtg.h): the current GPU's shader clock under load, f32 FMA rate and HBM copy bandwidth,
     measured now -- recorded beside every bench line so throughput from different boxes can be compared."""

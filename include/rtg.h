@@ -384,6 +384,15 @@ int rtg_synth_full_body_f32(rtg_topology_t topo, uint64_t seed, int64_t frame_of
 #define RTG_PROBE_FIELDS 6
 int rtg_box_probe(double *out, int32_t n_out, rtg_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Side-kernel residency (diagnostics, no reference counterpart): how many workgroups of the throughput kernel that
+ * rtg_retarget_f32 launches for this solver kind / gripper mode / input layout at a large batch the runtime keeps
+ * resident on one compute unit (hipOccupancyMaxActiveBlocksPerMultiprocessor for its block size).  A workgroup is
+ * RTG_SIDES_TILES x 128 threads (rtg_build_info), so with two tiles the figure is also the waves per SIMD.  Launches
+ * nothing.
+ * ---------------------------------------------------------------------- */
+int rtg_side_kernel_residency(int kind, int precise_gripper, int layout, int32_t *blocks_per_cu);
+
 #ifdef __cplusplus
 }
 #endif
