@@ -338,9 +338,62 @@ int rtg_dof_fk_f32(rtg_dof_model_t m, const float *dof, const float *root_rot, c
     if (B == 0) return RTG_OK;
     if ((m->topo->J > 1 && !dof) || !root_rot || !root_t || !g_rot || !g_pos)
         return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_dof_fk_f32: NULL buffer");
+    if (m->topo->J == 1) dof = root_rot;   // no angles: the kernel's unconditional first-element load gets readable memory
     const DofView D{m->d_axis, m->d_lower, m->d_upper};
     RTG_TRY(launch_dof_fk(m->topo->view(), D, clip != 0, dof, root_rot, root_t, B, g_rot, g_pos, as_stream(stream)),
             "k_dof_fk");
+    return RTG_OK;
+}
+
+// ---------------------------------------------------------------- gradients of the kinematics
+// the argument checks both backward entry points share (everything that needs no handle first)
+static int check_fk_backward(const char *fn, int64_t B, const void *grad_g_rot, const void *grad_g_pos, bool any_out)
+{
+    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)B);
+    if (B == 0) return RTG_OK;   // empty buffers have no address to give
+    if (!grad_g_rot && !grad_g_pos)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: both upstream gradients are NULL", fn);
+    if (!any_out) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: every output is NULL", fn);
+    return RTG_OK;
+}
+
+int rtg_dof_fk_backward_f32(rtg_dof_model_t m, const float *dof, const float *g_rot, const float *grad_g_rot,
+                            const float *grad_g_pos, int64_t B, int clip, float *grad_dof, float *grad_root_rot,
+                            float *grad_root_t, rtg_stream_t stream)
+{
+    int rc = check_fk_backward("rtg_dof_fk_backward_f32", B, grad_g_rot, grad_g_pos,
+                               grad_dof || grad_root_rot || grad_root_t);
+    if (rc != RTG_OK) return rc;
+    if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_dof_fk_backward_f32: NULL model");
+    if (clip && !m->has_limits)
+        return fail(RTG_ERR_INVALID_ARGUMENT,
+                    "rtg_dof_fk_backward_f32: clip_angles requested but the model has no DOF limits");
+    if (B == 0) return RTG_OK;
+    const int J = m->topo->J;
+    if ((J > 1 && !dof) || !g_rot) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_dof_fk_backward_f32: NULL buffer");
+    if (J == 1) {   // no angles: the kernel's unconditional first-element load gets readable memory
+        dof = g_rot;
+        grad_dof = nullptr;
+    }
+    const DofView D{m->d_axis, m->d_lower, m->d_upper};
+    RTG_TRY(launch_fk_backward(m->topo->view(), &D, clip != 0, dof, g_rot, grad_g_rot, grad_g_pos, B, grad_dof,
+                               grad_root_rot, grad_root_t, as_stream(stream)),
+            "k_fk_bwd<dof>");
+    return RTG_OK;
+}
+
+int rtg_fk_backward_f32(rtg_topology_t t, const float *local_rot, const float *g_rot, const float *grad_g_rot,
+                        const float *grad_g_pos, int64_t B, float *grad_local_rot, float *grad_root_t,
+                        rtg_stream_t stream)
+{
+    int rc = check_fk_backward("rtg_fk_backward_f32", B, grad_g_rot, grad_g_pos, grad_local_rot || grad_root_t);
+    if (rc != RTG_OK) return rc;
+    if (!t) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_fk_backward_f32: NULL topology");
+    if (B == 0) return RTG_OK;
+    if (!local_rot || !g_rot) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_fk_backward_f32: NULL buffer");
+    RTG_TRY(launch_fk_backward(t->view(), nullptr, false, local_rot, g_rot, grad_g_rot, grad_g_pos, B, grad_local_rot,
+                               nullptr, grad_root_t, as_stream(stream)),
+            "k_fk_bwd");
     return RTG_OK;
 }
 

@@ -2,6 +2,7 @@
 // hu_forward_model.py:17-33) and their launchers.  Every topology of J <= kGroupMaxJ joints (all shipped skeletons)
 // runs the lane-group kernels below; larger trees fall back to the lane walks (one frame per thread).
 #include "rtg_device.cuh"
+#include "rtg_fk_group.cuh"
 
 #include <algorithm>
 #include <type_traits>
@@ -123,27 +124,6 @@ __global__ __launch_bounds__(256) void k_dof_fk_walk(TopoView T, DofView D, cons
     }
 }
 
-// A lane-group tile is one wave, so ordering its LDS traffic needs no block
-// barrier: a wave's LDS instructions execute in issue order, and the
-// wavefront-scope fence + wave_barrier only stop the compiler from moving
-// memory operations across this point.  (__syncthreads would also make the
-// compiler drain every outstanding global store, s_waitcnt vmcnt(0), per step.)
-RTG_DEV void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-typedef float f4v __attribute__((ext_vector_type(4)));
-// the lane-group tiles' output pieces (whole 1 KiB wave stores): non-temporal (RTG_FK_NT_OUT): never read back here,
-// they would only evict the rows still to be read from the L2
-RTG_DEV void st_out(f4v *p, f4v v)
-{
-    if (RTG_FK_NT_OUT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-
 // the near-unit normalisation table (rtg_math.cuh) in the lane-group tiles' LDS, when any of them uses it
 constexpr bool kUnitTab = RTG_FK_UNIT_TAB || RTG_DOF_UNIT_TAB;
 constexpr size_t kUnitTabFloats = kUnitTab ? 4 * (2 * kUnitTabK + 1) : 0;
@@ -172,14 +152,6 @@ RTG_DEV Q qmul_norm_tab(Q a, Q b, const UnitEnt *tab)
 // LDS per wave: F J 28 bytes plus the schedule (Hu: 13.9 + 1.3 KiB).  Inverse FK (kinematics.py:41-63) has no chain:
 // each record's parent is read from the image and its local rotation stored straight from the lane that loaded it.
 // ----------------------------------------------------------------------------
-template <int F>
-struct Grp {
-    static_assert(F == 16 || F == 8, "lane groups of 4 or 8 lanes");
-    static constexpr int L = 64 / F;             // lanes per frame
-    static constexpr int LOG_L = F == 16 ? 2 : 3;
-    static constexpr int NR = F == 16 ? 9 : 8;   // records per lane: F J <= 64 NR (group_frames)
-};
-__host__ __device__ inline size_t pad16f(size_t nfloats) { return (nfloats + 3) & ~(size_t)3; }
 // rot [F J] float4 | pos [F J 3] float | schedule [gsteps L] GEnt | extra floats (kernel-specific tables)
 // ... | the near-unit table (kUnitTabFloats)
 __host__ __device__ inline size_t group_core_floats(int J, int F, int steps)
@@ -189,15 +161,6 @@ __host__ __device__ inline size_t group_core_floats(int J, int F, int steps)
 __host__ __device__ inline size_t group_lds_floats(int J, int F, int steps)
 {
     return group_core_floats(J, F, steps) + kUnitTabFloats;
-}
-
-// the tile's schedule into LDS (float4 copies, in flight with the tile's own loads)
-RTG_DEV void group_sched_fill(const TopoView &T, int L, GEnt *sch)
-{
-    const int n = T.gsteps * L * 2;
-    const f4v *gs = reinterpret_cast<const f4v *>(T.gsched);
-    f4v *d = reinterpret_cast<f4v *>(sch);
-    for (int i = (int)threadIdx.x; i < n; i += 64) d[i] = gs[i];
 }
 
 // The schedule's steps over the tile image (rot: global rotations written over the local ones; pos: positions, the
@@ -270,30 +233,6 @@ RTG_DEV void group_store(const f4v *rot, const float *pos, int nrec, float *__re
         for (int i = lane; i < npos; i += 64) g_pos[i] = pos[i];
     }
 }
-
-// the tile's NR records per lane, all loads in flight (unconditional: a lane past the tile re-reads record 0, so no
-// branch separates them), then -- after the caller's other loads -- into the LDS image
-template <int F>
-struct GroupRows {
-    f4v v[Grp<F>::NR];
-    RTG_DEV void load(const float *__restrict__ rows, int nrec)
-    {
-        const f4v *src = reinterpret_cast<const f4v *>(rows);
-#pragma unroll
-        for (int k = 0; k < Grp<F>::NR; ++k) {
-            const int rec = k * 64 + (int)threadIdx.x;
-            v[k] = src[rec < nrec ? rec : 0];
-        }
-    }
-    RTG_DEV void to_lds(f4v *rot, int nrec) const
-    {
-#pragma unroll
-        for (int k = 0; k < Grp<F>::NR; ++k) {
-            const int rec = k * 64 + (int)threadIdx.x;
-            if (rec < nrec) rot[rec] = v[k];
-        }
-    }
-};
 
 template <bool STATE, int F>
 RTG_DEV void fk_group_tile(const TopoView &T, const float *__restrict__ local_rot, const float *__restrict__ root_t,
@@ -561,6 +500,12 @@ int32_t fk_group_schedule(const int32_t *parents, const V *local_t, const Q *tre
     const int L = 64 / F;
     std::vector<int> h(J, 1), done(J, -1);
     for (int j = J - 1; j > 0; --j) h[parents[j]] = std::max(h[parents[j]], h[j] + 1);
+    // child links for the reverse sweep (rtg_fk_grad.hip): first child and next sibling, by index; 0xFF: none
+    std::vector<uint32_t> fc(J, 0xFF), ns(J, 0xFF);
+    for (int j = J - 1; j > 0; --j) {
+        ns[j] = fc[parents[j]];
+        fc[parents[j]] = (uint32_t)j;
+    }
     int steps = 0, placed = 0;
     std::vector<int> ready;
     while (placed < J) {
@@ -576,7 +521,8 @@ int32_t fk_group_schedule(const int32_t *parents, const V *local_t, const Q *tre
                 const int j = ready[u];
                 done[j] = steps;
                 ++placed;
-                e = GEnt{local_t[j].x, local_t[j].y, local_t[j].z, j | ((j ? parents[j] : 0xFF) << 8),
+                const uint32_t code = (uint32_t)j | ((uint32_t)(j ? parents[j] : 0xFF) << 8) | (fc[j] << 16) | (ns[j] << 24);
+                e = GEnt{local_t[j].x, local_t[j].y, local_t[j].z, (int32_t)code,
                          tree_quat[j].x, tree_quat[j].y, tree_quat[j].z, tree_quat[j].w};
             }
         }

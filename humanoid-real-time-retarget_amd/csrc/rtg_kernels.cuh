@@ -7,7 +7,9 @@ namespace rtg {
 
 // One (step, sub-lane) entry of the lane-group FK schedule (fk_group_schedule, rtg_fk.hip): at step s, sub-lane u of
 // every frame's lane group composes joint `code & 0xFF` (0xFF: idle) from its parent `(code >> 8) & 0xFF`, with that
-// joint's zero-pose local translation and tree quaternion alongside (two ds_read_b128 per step).
+// joint's zero-pose local translation and tree quaternion alongside (two ds_read_b128 per step).  The upper half of
+// `code` links the joint's children for the reverse sweep (rtg_fk_grad.hip): `(code >> 16) & 0xFF` its first child,
+// `(code >> 24) & 0xFF` its next sibling, both by ascending index, 0xFF for none; the forward kernels mask them off.
 struct alignas(16) GEnt {
     float lx, ly, lz;
     int32_t code;
@@ -84,6 +86,11 @@ hipError_t launch_local_rotation(const TopoView &T, bool state, const float *g, 
 hipError_t launch_fk_multi(FkMultiArgs &A, hipStream_t s);
 hipError_t launch_dof_fk(const TopoView &T, const DofView &D, bool clip, const float *dof, const float *root_rot,
                          const float *root_t, int64_t B, float *gr, float *gp, hipStream_t s);
+// the adjoints of launch_dof_fk / launch_fk (rtg_fk_grad.hip); lq_in: the joint angles (B,J-1) when D, else the local
+// rotations (B,J,4); lq_grad: their gradient rows; either upstream gradient and any output may be nullptr
+hipError_t launch_fk_backward(const TopoView &T, const DofView *D, bool clip, const float *lq_in, const float *g_rot,
+                              const float *grad_g_rot, const float *grad_g_pos, int64_t B, float *lq_grad,
+                              float *grad_root_rot, float *grad_root_t, hipStream_t s);
 hipError_t launch_rescale_motion(const TopoView &T, const float *motion, int64_t B, const float *dir, float *out,
                                  hipStream_t s);
 hipError_t launch_quat_between(const float *v1, const float *v2, int64_t n, float *out, float *ws, hipStream_t s);

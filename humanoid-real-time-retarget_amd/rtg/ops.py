@@ -11,6 +11,7 @@ import functools
 from typing import Sequence
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import check, lib
@@ -204,18 +205,59 @@ def quat_in_xyz_axis(q, seq: str = "xyz"):
     return out[..., 0, :], out[..., 1, :], out[..., 2, :]
 
 
-def forward_kinematics(topo: Topology, local_rot, root_t, state: bool = False):
-    """kinematics.py:13-39 (state=False) / SkeletonState FK skeleton3d.py:402-425 (state=True)."""
+def _fk_launch(topo: Topology, lr, rt, state: bool):
     J = topo.num_joints
-    lr = dev_f32(local_rot, (J, 4), "local_rot")
     lead = lr.shape[:-2]
-    rt = dev_f32(root_t, (3,), "root_t").expand(*lead, 3).contiguous()
     B = int(torch.Size(lead).numel())
     g_rot = torch.empty(tuple(lead) + (J, 4), device=lr.device, dtype=torch.float32)
     g_pos = torch.empty(tuple(lead) + (J, 3), device=lr.device, dtype=torch.float32)
     fn = lib().rtg_state_fk_f32 if state else lib().rtg_fk_f32
     check(fn(topo.handle, ptr(lr), ptr(rt), B, ptr(g_rot), ptr(g_pos), stream_handle()))
     return g_rot, g_pos
+
+
+def _cotangent(g):
+    """An upstream gradient as the kernels read it (None stays None: not read, not zero-filled)."""
+    return None if g is None else g.to(torch.float32).contiguous()
+
+
+class _FK(torch.autograd.Function):
+    """forward_kinematics(state=False) with its HIP adjoint (rtg_fk_backward_f32); the forward is the same launch."""
+
+    @staticmethod
+    def forward(ctx, topo, lr, rt):
+        ctx.set_materialize_grads(False)
+        g_rot, g_pos = _fk_launch(topo, lr, rt, False)
+        ctx.topo = topo
+        ctx.save_for_backward(lr, g_rot)
+        return g_rot, g_pos
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_g_rot, grad_g_pos):
+        need_lr, need_rt = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if (grad_g_rot is None and grad_g_pos is None) or not (need_lr or need_rt):
+            return None, None, None
+        lr, g_rot = ctx.saved_tensors
+        B = int(torch.Size(lr.shape[:-2]).numel())
+        ggr, ggp = _cotangent(grad_g_rot), _cotangent(grad_g_pos)
+        g_lr = torch.empty_like(lr) if need_lr else None
+        g_rt = torch.empty(tuple(lr.shape[:-2]) + (3,), device=lr.device, dtype=torch.float32) if need_rt else None
+        check(lib().rtg_fk_backward_f32(ctx.topo.handle, ptr(lr), ptr(g_rot), ptr(ggr), ptr(ggp), B, ptr(g_lr),
+                                        ptr(g_rt), stream_handle()))
+        return None, g_lr, g_rt
+
+
+def forward_kinematics(topo: Topology, local_rot, root_t, state: bool = False):
+    """kinematics.py:13-39 (state=False) / SkeletonState FK skeleton3d.py:402-425 (state=True).  state=False is
+    differentiable with respect to local_rot and root_t (the reference's FK is plain torch); state=True is not."""
+    J = topo.num_joints
+    lr = dev_f32(local_rot, (J, 4), "local_rot")
+    lead = lr.shape[:-2]
+    rt = dev_f32(root_t, (3,), "root_t").expand(*lead, 3).contiguous()
+    if not state and torch.is_grad_enabled() and (lr.requires_grad or rt.requires_grad):
+        return _FK.apply(topo, lr, rt)
+    return _fk_launch(topo, lr, rt, state)
 
 
 def local_rotation(topo: Topology, g_rot, state: bool = False):
@@ -246,13 +288,52 @@ def dof_forward_kinematics(model, dof, root_rot, root_t, clip: bool = False):
         rr = rr[..., 0, :]
     rr = dev_f32(rr, (4,), "motion_root_rotation").expand(*lead, 4).contiguous()
     rt = dev_f32(root_t, (3,), "motion_root_translation").expand(*lead, 3).contiguous()
+    if torch.is_grad_enabled() and (d.requires_grad or rr.requires_grad or rt.requires_grad):
+        return _DofFK.apply(model, bool(clip), d, rr, rt)
+    return _dof_fk_launch(model, bool(clip), d, rr, rt)
+
+
+def _dof_fk_launch(model, clip: bool, d, rr, rt):
+    lead = d.shape[:-1]
     B = int(torch.Size(lead).numel())
-    J = n + 1
+    J = model.num_dofs + 1
     g_rot = torch.empty(tuple(lead) + (J, 4), device=d.device, dtype=torch.float32)
     g_pos = torch.empty(tuple(lead) + (J, 3), device=d.device, dtype=torch.float32)
-    check(lib().rtg_dof_fk_f32(model.handle, ptr(d), ptr(rr), ptr(rt), B, int(bool(clip)), ptr(g_rot), ptr(g_pos),
+    check(lib().rtg_dof_fk_f32(model.handle, ptr(d), ptr(rr), ptr(rt), B, int(clip), ptr(g_rot), ptr(g_pos),
                                stream_handle()))
     return g_rot, g_pos
+
+
+class _DofFK(torch.autograd.Function):
+    """dof_forward_kinematics with its HIP adjoint (rtg_dof_fk_backward_f32); the forward is the same launch.  The
+    clip is straight-through, as in the reference (hu_forward_model.py:27-33)."""
+
+    @staticmethod
+    def forward(ctx, model, clip, d, rr, rt):
+        ctx.set_materialize_grads(False)
+        g_rot, g_pos = _dof_fk_launch(model, clip, d, rr, rt)
+        ctx.model, ctx.clip = model, clip
+        ctx.save_for_backward(d, g_rot)
+        return g_rot, g_pos
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_g_rot, grad_g_pos):
+        need_d, need_rr, need_rt = ctx.needs_input_grad[2:5]
+        if (grad_g_rot is None and grad_g_pos is None) or not (need_d or need_rr or need_rt):
+            return None, None, None, None, None
+        d, g_rot = ctx.saved_tensors
+        lead = tuple(d.shape[:-1])
+        B = int(torch.Size(lead).numel())
+        ggr, ggp = _cotangent(grad_g_rot), _cotangent(grad_g_pos)
+        g_d = torch.empty_like(d) if need_d else None
+        g_rr = torch.empty(lead + (4,), device=d.device, dtype=torch.float32) if need_rr else None
+        g_rt = torch.empty(lead + (3,), device=d.device, dtype=torch.float32) if need_rt else None
+        if d.shape[-1] == 0 and g_rr is None and g_rt is None:   # a one-joint model has no angles: nothing to compute
+            return None, None, g_d, None, None
+        check(lib().rtg_dof_fk_backward_f32(ctx.model.handle, ptr(d), ptr(g_rot), ptr(ggr), ptr(ggp), B, int(ctx.clip),
+                                            ptr(g_d), ptr(g_rr), ptr(g_rt), stream_handle()))
+        return None, None, g_d, g_rr, g_rt
 
 
 def rescale_motion(topo: Topology, motion, dir=None):

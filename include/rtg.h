@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define RTG_ABI_VERSION 4   /* 4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
+#define RTG_ABI_VERSION 5   /* 5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
+                               4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
                                   reserved), the inbox may be device memory (rtg_server_inbox_alloc), rtg_frame_server_signal;
                                3: frames the reference raises on are marked (rtg_frame_error), the solver error word, ctl[3];
                                2: the input-layout argument of rtg_retarget_f32 / rtg_ingest_vtrdyn_f32 / rtg_synth_full_body_f32 */
@@ -136,6 +137,27 @@ int rtg_dof_model_destroy(rtg_dof_model_t model);
  * local[j] = quat_from_angle_axis(a'[j-1], axis[j-1]) (:21-23), local[0] = root rotation (:24). */
 int rtg_dof_fk_f32(rtg_dof_model_t model, const float *dof, const float *root_rot, const float *root_t, int64_t B,
                    int clip, float *g_rot, float *g_pos, rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Gradients of the kinematics.  The reference's FK is plain torch, so a loss on its outputs back-propagates to the
+ * joint angles / local rotations; these are the same vector-Jacobian products as one launch each.  g_rot is the
+ * SAVED OUTPUT of the forward call on the same inputs (nothing else of the forward is kept).  grad_g_rot (B,J,4) /
+ * grad_g_pos (B,J,3) are the upstream gradients; either may be NULL (taken as zero, not read), not both.  Every
+ * output may be NULL (not written), not all.  The root rotation is taken as given (unnormalised), the normalisation
+ * of every other joint and quat_rotate's |q|^2 scaling are differentiated as torch does.  Results are bit-identical
+ * from run to run; a frame's NaN / inf stays in that frame's rows.  B == 0 is a no-op (no pointer is looked at).
+ * ---------------------------------------------------------------------- */
+/* rtg_dof_fk_f32's adjoint: dof (B,J-1) and clip as in the forward call.  The clip is straight-through
+ * (hu_forward_model.py:27-33): the local rotations are built from the clamped angles, the gradient passes unchanged.
+ * -> grad_dof (B,J-1), grad_root_rot (B,4), grad_root_t (B,3). */
+int rtg_dof_fk_backward_f32(rtg_dof_model_t model, const float *dof, const float *g_rot, const float *grad_g_rot,
+                            const float *grad_g_pos, int64_t B, int clip, float *grad_dof, float *grad_root_rot,
+                            float *grad_root_t, rtg_stream_t stream);
+/* rtg_fk_f32's adjoint (not rtg_state_fk_f32's): local_rot (B,J,4) as in the forward call (it may be non-unit).
+ * -> grad_local_rot (B,J,4) (row 0: the root rotation's gradient), grad_root_t (B,3). */
+int rtg_fk_backward_f32(rtg_topology_t topo, const float *local_rot, const float *g_rot, const float *grad_g_rot,
+                        const float *grad_g_pos, int64_t B, float *grad_local_rot, float *grad_root_t,
+                        rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * VTRDyn ingest (sim_full_body_teleop.py:92, :109-112)

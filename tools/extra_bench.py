@@ -2,7 +2,8 @@
 
   latency  -- batch-1 / small-batch retarget latency (teleop path, SURVEY §7 "Latency path"):
               kernel-only (HIP events) and end-to-end host->device->host wall time
-  fk       -- FK throughput: Hu (B=262144) and the mixed 4-topology config (4 x 65536, one launch)
+  fk       -- FK throughput: Hu (B=262144), the joint-angle model and its gradient, and the mixed 4-topology
+              config (4 x 65536, one launch)
   solvers  -- throughput of all four solver kinds at B=262144
 """
 from __future__ import annotations
@@ -188,6 +189,22 @@ def fk():
     check(f(*dof_args))
     res["hu_dof_fk_262144"] = {"ms": ms, "frames_per_s": B / (ms * 1e-3),
                                "GBs_algorithmic": (32 * 4 + 28 + 33 * 28) * B / (ms * 1e-3) / 1e9}
+    # its gradient (rtg_dof_fk_backward_f32, same model and batch, clip on): g_rot, dof and the cotangent rows read,
+    # the gradient rows written; with both cotangents and with positions only (the common loss)
+    cgr = torch.randn((B, 33, 4), device="cuda")
+    cgp = torch.randn((B, 33, 3), device="cuda")
+    gd = torch.empty((B, 32), device="cuda")
+    grr = torch.empty((B, 4), device="cuda")
+    grt = torch.empty((B, 3), device="cuda")
+    f = lib().rtg_dof_fk_backward_f32
+    for name, cot_rot, cot_bytes in (("hu_dof_fk_backward_262144", cgr, 33 * 28),
+                                     ("hu_dof_fk_backward_pos_only_262144", None, 33 * 12)):
+        bw_args = (M.handle, ptr(dof), ptr(dgr), ptr(cot_rot), ptr(cgp), B, 1, ptr(gd), ptr(grr), ptr(grt), sh)
+        ms = time_events(lambda: f(*bw_args))
+        check(f(*bw_args))
+        nb = (33 * 16 + 32 * 4 + cot_bytes + 32 * 4 + 28) * B
+        res[name] = {"ms": ms, "frames_per_s": B / (ms * 1e-3), "TBs_algorithmic": nb / (ms * 1e-3) / 1e12,
+                     "forward_ms_same_run": res["hu_dof_fk_262144"]["ms"]}
     segs = []
     nbytes = 0
     for i, n in enumerate(["hu_v5", "vtrdyn", "vtrdyn_full", "noitom"]):
