@@ -27,6 +27,8 @@ struct rtg_topology_s {
     Q *d_tree_quat = nullptr;
     GEnt *d_gsched = nullptr;   // lane-group FK schedule (J <= kGroupMaxJ), see fk_group_schedule
     int32_t gF = 0, gsteps = 0;
+    std::vector<int32_t> h_parents;   // host copies, for the plans built over this tree (rtg_retarget_plan_create)
+    std::vector<Q> h_tree_quat;
     TopoView view() const
     {
         return TopoView{d_parents, d_local_t, d_tree_quat, J, d_gsched, gF, gsteps};
@@ -40,6 +42,12 @@ struct rtg_dof_model_s {
     float *d_lower = nullptr;
     float *d_upper = nullptr;
     bool has_limits = false;
+};
+
+// SkeletonState.retarget_to: the view (layout, R, scale, roots) and the device blob it points into.
+struct rtg_retarget_plan_s {
+    RetargetView view{};
+    float *d_blob = nullptr;
 };
 
 struct rtg_solver_s {
@@ -159,6 +167,8 @@ int rtg_topology_create(const int32_t *parents, const float *local_t, const floa
             t->gsteps = steps;
         }
     }
+    t->h_parents.assign(parents, parents + J);
+    t->h_tree_quat.assign(tq, tq + J);
     delete[] tq;
     if (rc != RTG_OK) {
         (void)hipFree(t->d_parents);
@@ -394,6 +404,141 @@ int rtg_fk_backward_f32(rtg_topology_t t, const float *local_rot, const float *g
     RTG_TRY(launch_fk_backward(t->view(), nullptr, false, local_rot, g_rot, grad_g_rot, grad_g_pos, B, grad_local_rot,
                                nullptr, grad_root_t, as_stream(stream)),
             "k_fk_bwd");
+    return RTG_OK;
+}
+
+// ---------------------------------------------------------------- SkeletonState.retarget_to
+int rtg_retarget_plan_tables(const int32_t *src_parents, int32_t Js, const int32_t *tgt_parents, int32_t Jt,
+                             const int32_t *src_joint, const int32_t *tgt_joint, int32_t K, int32_t *kept_src,
+                             int32_t *src_reduced_parents, int32_t *kept_tgt, int32_t *tgt_reduced_parents,
+                             int32_t *perm, int32_t *src_of)
+{
+    if (!src_parents || !tgt_parents)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_plan_tables: NULL parents");
+    for (int side = 0; side < 2; ++side) {   // the trees rtg_topology_create accepts
+        const int32_t *p = side ? tgt_parents : src_parents;
+        const int J = side ? Jt : Js;
+        if (J >= 1 && p[0] != -1)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_plan_tables: joint 0 must be the root");
+        for (int j = 1; j < J; ++j)
+            if (p[j] < 0 || p[j] >= j)
+                return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_plan_tables: parents[%d]=%d is not < %d", j, p[j], j);
+    }
+    RetargetTables T;
+    std::string err;
+    if (!retarget_tables(src_parents, Js, tgt_parents, Jt, src_joint, tgt_joint, K, T, err))
+        return fail(Js > kGroupMaxJ || Jt > kGroupMaxJ ? RTG_ERR_UNSUPPORTED : RTG_ERR_INVALID_ARGUMENT,
+                    "rtg_retarget_plan_tables: %s", err.c_str());
+    auto put = [](int32_t *dst, const std::vector<int32_t> &v) {
+        if (dst) memcpy(dst, v.data(), sizeof(int32_t) * v.size());
+    };
+    put(kept_src, T.kept_s);
+    put(src_reduced_parents, T.sred_par);
+    put(kept_tgt, T.kept_t);
+    put(tgt_reduced_parents, T.tred_par);
+    put(perm, T.perm);
+    put(src_of, T.src_of);
+    return RTG_OK;
+}
+
+int rtg_retarget_plan_create(rtg_topology_t src, rtg_topology_t tgt, const int32_t *src_joint,
+                             const int32_t *tgt_joint, int32_t K, const float *src_tpose_local_rot,
+                             const float *src_tpose_root_t, const float *tgt_tpose_local_rot,
+                             const float *tgt_tpose_root_t, const float *rotation_to_target, float scale,
+                             rtg_retarget_plan_t *out)
+{
+    const char *fn = "rtg_retarget_plan_create";
+    if (!out) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: out is NULL", fn);
+    *out = nullptr;
+    if (!src || !tgt) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL topology", fn);
+    if (!src_tpose_local_rot || !src_tpose_root_t || !tgt_tpose_local_rot || !tgt_tpose_root_t || !rotation_to_target)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL t-pose / rotation", fn);
+    const int Js = src->J, Jt = tgt->J;
+    RetargetTables T;
+    std::string err;
+    if (!retarget_tables(src->h_parents.data(), Js, tgt->h_parents.data(), Jt, src_joint, tgt_joint, K, T, err))
+        return fail(Js > kGroupMaxJ || Jt > kGroupMaxJ ? RTG_ERR_UNSUPPORTED : RTG_ERR_INVALID_ARGUMENT, "%s: %s", fn,
+                    err.c_str());
+    rtg_retarget_plan_s *p = new (std::nothrow) rtg_retarget_plan_s();
+    if (!p) return fail(RTG_ERR_OUT_OF_MEMORY, "%s: host allocation failed", fn);
+    std::vector<float> blob;
+    RetargetView &V_ = p->view;
+    retarget_blob(T, src->h_parents.data(), src->h_tree_quat.data(), tgt->h_parents.data(), tgt->h_tree_quat.data(),
+                  blob, V_);
+    V_.R = Q{rotation_to_target[0], rotation_to_target[1], rotation_to_target[2], rotation_to_target[3]};
+    V_.scale = scale;
+    V_.tgt_root = v3(tgt_tpose_root_t, 0);
+    V_.t_tp = V{0.f, 0.f, 0.f};
+    // The constants, on the device: the t-poses normalised (from_rotation_and_root_translation, :610), the source one
+    // through stages 1-6 of the kernel itself, the target one through the state FK kernel.  Scratch, in floats:
+    // src rows | src root | tgt rows | tgt root | dump (4 K + 3, padded) | tgt global rows | tgt positions | the two
+    // t-poses as given
+    const size_t o_sr = 0, o_st = o_sr + 4 * (size_t)Js, o_tr = o_st + 4, o_tt = o_tr + 4 * (size_t)Jt, o_d = o_tt + 4,
+                 o_g = o_d + 4 * (size_t)K + 4, o_p = o_g + 4 * (size_t)Jt, o_sraw = o_p + 4 * (size_t)Jt,
+                 o_traw = o_sraw + 4 * (size_t)Js, n_ws = o_traw + 4 * (size_t)Jt;
+    std::vector<float> h(n_ws, 0.0f);
+    memcpy(&h[o_sraw], src_tpose_local_rot, sizeof(float) * 4 * Js);
+    memcpy(&h[o_st], src_tpose_root_t, sizeof(float) * 3);
+    memcpy(&h[o_traw], tgt_tpose_local_rot, sizeof(float) * 4 * Jt);
+    float *ws = nullptr;
+    int rc = hip_check(hipMalloc(&ws, sizeof(float) * n_ws), "hipMalloc(plan scratch)");
+    if (rc == RTG_OK) rc = hip_check(hipMalloc(&p->d_blob, sizeof(float) * blob.size()), "hipMalloc(plan blob)");
+    if (rc == RTG_OK) rc = hip_check(hipMemcpy(ws, h.data(), sizeof(float) * n_ws, hipMemcpyHostToDevice), "hipMemcpy");
+    if (rc == RTG_OK)
+        rc = hip_check(hipMemcpy(p->d_blob, blob.data(), sizeof(float) * blob.size(), hipMemcpyHostToDevice), "hipMemcpy");
+    V_.blob = p->d_blob;
+    if (rc == RTG_OK)
+        rc = hip_check(launch_quat_op(RTG_OP_QUAT_NORMALIZE, ws + o_sraw, nullptr, nullptr, Js, ws + o_sr, nullptr),
+                       "quat_normalize(source t-pose)");
+    if (rc == RTG_OK)
+        rc = hip_check(launch_quat_op(RTG_OP_QUAT_NORMALIZE, ws + o_traw, nullptr, nullptr, Jt, ws + o_tr, nullptr),
+                       "quat_normalize(target t-pose)");
+    if (rc == RTG_OK)
+        rc = hip_check(launch_retarget_to(V_, true, ws + o_sr, ws + o_st, 1, nullptr, nullptr, ws + o_d, nullptr),
+                       "k_retarget_to(t-pose)");
+    if (rc == RTG_OK)
+        rc = hip_check(launch_fk(tgt->view(), true, ws + o_tr, ws + o_tt, 1, ws + o_g, ws + o_p, nullptr),
+                       "k_fk<state>(target t-pose)");
+    if (rc == RTG_OK) rc = hip_check(hipMemcpy(h.data(), ws, sizeof(float) * n_ws, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (rc == RTG_OK) {
+        for (int k = 0; k < K; ++k) {
+            float *cg = &blob[4 * ((size_t)V_.o_cg + k)], *tg = &blob[4 * ((size_t)V_.o_tg + k)];
+            const float *g = &h[o_d + 4 * (size_t)k], *t = &h[o_g + 4 * (size_t)T.kept_t[k]];
+            cg[0] = -g[0], cg[1] = -g[1], cg[2] = -g[2], cg[3] = g[3];   // quat_inverse = the conjugate (:214-219)
+            memcpy(tg, t, sizeof(float) * 4);
+        }
+        V_.t_tp = V{h[o_d + 4 * (size_t)K], h[o_d + 4 * (size_t)K + 1], h[o_d + 4 * (size_t)K + 2]};
+        rc = hip_check(hipMemcpy(p->d_blob, blob.data(), sizeof(float) * blob.size(), hipMemcpyHostToDevice), "hipMemcpy");
+    }
+    (void)hipFree(ws);
+    if (rc != RTG_OK) {
+        (void)hipFree(p->d_blob);
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return RTG_OK;
+}
+
+int rtg_retarget_plan_destroy(rtg_retarget_plan_t p)
+{
+    if (!p) return RTG_OK;
+    (void)hipFree(p->d_blob);
+    delete p;
+    return RTG_OK;
+}
+
+int rtg_retarget_to_f32(rtg_retarget_plan_t p, const float *src_rot, const float *src_root_t, int src_is_local,
+                        int64_t B, float *tgt_local_rot, float *tgt_root_t, rtg_stream_t stream)
+{
+    if (!p) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_to_f32: NULL plan");
+    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_to_f32: negative batch %lld", (long long)B);
+    if (B == 0) return RTG_OK;
+    if (!src_rot || !src_root_t || !tgt_local_rot || !tgt_root_t)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_to_f32: NULL buffer");
+    RTG_TRY(launch_retarget_to(p->view, src_is_local != 0, src_rot, src_root_t, B, tgt_local_rot, tgt_root_t, nullptr,
+                               as_stream(stream)),
+            "k_retarget_to");
     return RTG_OK;
 }
 

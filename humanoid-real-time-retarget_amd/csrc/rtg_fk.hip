@@ -124,15 +124,6 @@ __global__ __launch_bounds__(256) void k_dof_fk_walk(TopoView T, DofView D, cons
     }
 }
 
-// the near-unit normalisation table (rtg_math.cuh) in the lane-group tiles' LDS, when any of them uses it
-constexpr bool kUnitTab = RTG_FK_UNIT_TAB || RTG_DOF_UNIT_TAB;
-constexpr size_t kUnitTabFloats = kUnitTab ? 4 * (2 * kUnitTabK + 1) : 0;
-RTG_DEV Q qmul_norm_tab(Q a, Q b, const UnitEnt *tab)
-{
-    if (!RTG_FK_UNIT_TAB) return qmul_norm(a, b);
-    return qnormalize_t(qmul(a, b), tab);
-}
-
 // ----------------------------------------------------------------------------
 // Lane-group kinematics (round 6): a frame's joints spread over a GROUP of lanes, F frames per wave (F = 16: four
 // lanes per frame for J <= 36; F = 8: eight lanes for J <= 64), so the tile's rows move as whole coalesced pieces.

@@ -34,6 +34,15 @@ struct Grp {
     static constexpr int LOG_L = F == 16 ? 2 : 3;
     static constexpr int NR = F == 16 ? 9 : 8;   // records per lane: F J <= 64 NR (group_frames)
 };
+// the near-unit normalisation table (rtg_math.cuh) in the lane-group tiles' LDS, when any of them uses it
+constexpr bool kUnitTab = RTG_FK_UNIT_TAB || RTG_DOF_UNIT_TAB;
+constexpr size_t kUnitTabFloats = kUnitTab ? 4 * (2 * kUnitTabK + 1) : 0;
+RTG_DEV Q qmul_norm_tab(Q a, Q b, const UnitEnt *tab)
+{
+    if (!RTG_FK_UNIT_TAB) return qmul_norm(a, b);
+    return qnormalize_t(qmul(a, b), tab);
+}
+
 __host__ __device__ inline size_t pad16f(size_t nfloats) { return (nfloats + 3) & ~(size_t)3; }
 
 // the tile's schedule into LDS (float4 copies, in flight with the tile's own loads)

@@ -3,6 +3,9 @@
 #include "rtg_math.cuh"
 #include "rtg.h"
 
+#include <string>
+#include <vector>
+
 namespace rtg {
 
 // One (step, sub-lane) entry of the lane-group FK schedule (fk_group_schedule, rtg_fk.hip): at step s, sub-lane u of
@@ -91,6 +94,38 @@ hipError_t launch_dof_fk(const TopoView &T, const DofView &D, bool clip, const f
 hipError_t launch_fk_backward(const TopoView &T, const DofView *D, bool clip, const float *lq_in, const float *g_rot,
                               const float *grad_g_rot, const float *grad_g_pos, int64_t B, float *lq_grad,
                               float *grad_root_rot, float *grad_root_t, hipStream_t s);
+// SkeletonState.retarget_to (poselib skeleton3d.py:742-889) as one launch, rtg_retarget_to.hip.
+// The host tables of a mapping of K (source joint, target joint) pairs: S_red / T_red are the trees with only the
+// mapped joints kept, each hung from its nearest kept ancestor (drop_nodes_by_names, :226-259).
+struct RetargetTables {
+    int32_t Js = 0, Jt = 0, K = 0;
+    std::vector<int32_t> kept_s, kept_t;       // (K) the mapped joints of S / T, ascending: S_red / T_red's joints
+    std::vector<int32_t> sred_par, tred_par;   // (K) parents in S_red / T_red (root -1)
+    std::vector<int32_t> perm;                 // (K) index in S_red of the source joint mapped to T_red's k-th (:721-740)
+    std::vector<int32_t> src_of;               // (Jt) index in T_red of target joint j's nearest mapped ancestor-or-self
+};
+// fills `out`; on a bad mapping returns false with the reason in `err`
+bool retarget_tables(const int32_t *src_parents, int32_t Js, const int32_t *tgt_parents, int32_t Jt,
+                     const int32_t *src_joint, const int32_t *tgt_joint, int32_t K, RetargetTables &out,
+                     std::string &err);
+// The plan's device blob, in 16-byte units: both list schedules, then the per-joint tables (retarget_blob).
+struct RetargetView {
+    const float *blob;          // device
+    int32_t Js, Jt, K, F;       // F: frames per wave, group_frames(max(Js, Jt))
+    int32_t steps1, steps6;     // list-schedule steps of stage 1 (S, pruned) and stage 6 (T_red)
+    int32_t n16;                // the blob's size
+    int32_t o_sch6, o_cg, o_tg, o_ttq, o_int;   // offsets of its parts
+    Q R;                        // rotation_to_target_skeleton
+    float scale;                // f32(scale_to_target_skeleton)
+    V tgt_root, t_tp;           // the target t-pose's root translation; quat_rotate(R, source t-pose root)
+};
+// host image of the blob (constants cG / TG zeroed: filled after the t-pose pass) and the view's layout fields
+void retarget_blob(const RetargetTables &T, const int32_t *src_parents, const Q *src_tq, const int32_t *tgt_parents,
+                   const Q *tgt_tq, std::vector<float> &blob, RetargetView &view);
+// dump != nullptr: stop after stage 6 and write the K global rotations on T_red and the rotated root translation
+// (4 K + 3 floats) of frame 0 there (the t-pose pass of plan creation)
+hipError_t launch_retarget_to(const RetargetView &P, bool local_in, const float *rot, const float *root_t, int64_t B,
+                              float *out_rot, float *out_root_t, float *dump, hipStream_t s);
 hipError_t launch_rescale_motion(const TopoView &T, const float *motion, int64_t B, const float *dir, float *out,
                                  hipStream_t s);
 hipError_t launch_quat_between(const float *v1, const float *v2, int64_t n, float *out, float *ws, hipStream_t s);

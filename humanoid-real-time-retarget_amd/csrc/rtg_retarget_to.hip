@@ -1,0 +1,326 @@
+// rtg_retarget_to.hip -- SkeletonState.retarget_to (poselib skeleton3d.py:742-889) as ONE launch on the lane groups of
+// rtg_fk_group.cuh, and the host tables / schedules of its plan.
+//
+// With S the source tree (Js joints), T the target tree (Jt), K mapped (source, target) pairs, S_red / T_red the trees
+// with only the mapped joints kept (drop_nodes_by_names, :226-259), R = rotation_to_target_skeleton and s the scale,
+// a frame goes through (every from_rotation_and_root_translation of the reference normalises; those stay):
+//   1. Gs = the source state's global rotations: state FK over S with S's tree quaternions (:402-425) for a local
+//      state, on a list schedule pruned to the mapped joints' ancestors; the rows as stored for a global state;
+//   2. g = normalize(Gs[kept])                                                       (_transfer_to, :676-683)
+//   3. l_k = qmul_norm(normalize(conj(identity)), qmul_norm(conj(g_parent), g_k)) over S_red, root copied (:460-484)
+//   4. permute to T_red's order, normalize                                           (_remapped_to, :721-740)
+//   5. l_0 = qmul_norm(R, l_0), normalize; t' = quat_rotate(R, root_t)               (:848-855)
+//   6. state FK of l over T_red with identity tree quaternions -> G                  (:868, through :402-425)
+//   7. n = qmul_norm(qmul_norm(G, conj(G_tp)), TG)                                   (:868-869)
+//   8. o_j = normalize(n[src_of[j]]) for T's Jt joints                               (:876-886)
+//   9. inverse FK over T with T's tree quaternions, normalize: the output rows       (.local_repr(), :636-650)
+//  10. root = tgt_tpose_root + (t' - t'_tp) f32(s)                                   (:858, :885)
+// G_tp (stages 1-6 of the source t-pose) and TG (the target t-pose's global rotations at the mapped joints) are the
+// plan's constants, evaluated on the device at plan creation (rtg_api.cpp) by this kernel and the FK kernel.
+//
+// A tile is one wave and F frames (group_frames(max(Js, Jt))), 64 / F lanes per frame.  The source rows come in as
+// coalesced 1 KiB pieces into an LDS image, all loads in flight; stages 1 and 6 run the schedules' steps on the
+// frame's lane group, the other stages have no chain and spread their (frame, joint) items over the wave; the output
+// rows leave as whole-wave non-temporal stores.  LDS: image [F Js] | reduced rows [F K] (float4 each: the stage-3..6
+// rows overlay the image, dead after stage 2; stage 8's rows are stage 7's, indexed through src_of) | the plan's
+// blob (schedules, constants, index tables) | the near-unit table.  Each joint is composed by the device functions the
+// FK kernels use (qmul_norm through the near-unit table, qnormalize, qrotate) with the reference's operands in the
+// reference's order, so the bits do not depend on the schedule or on which lane does what.
+#include "rtg_device.cuh"
+#include "rtg_fk_group.cuh"
+
+#include <algorithm>
+
+namespace rtg {
+
+RTG_DEV Q qnorm_tab(Q q, const UnitEnt *tab)
+{
+    if (!RTG_FK_UNIT_TAB) return qnormalize(q);
+    return qnormalize_t(q, tab);
+}
+RTG_DEV Q q_of(f4v v) { return Q{v.x, v.y, v.z, v.w}; }
+RTG_DEV f4v v_of(Q q) { return f4v{q.x, q.y, q.z, q.w}; }
+
+// a list schedule's steps on the rotations alone: joint j's row becomes qmul_norm(parent's global row,
+// qmul_norm(tree quaternion, row)) (:416-422); the root's row is its global rotation already and has no entry
+template <int F>
+RTG_DEV void rot_compose(f4v *img, int stride, const GEnt *sch, int steps, int nfr, const UnitEnt *utab)
+{
+    using G = Grp<F>;
+    const int lane = (int)threadIdx.x;
+    const int fr = lane >> G::LOG_L, sub = lane & (G::L - 1);
+    const bool live = fr < nfr;
+    const int base = fr * stride;
+    for (int s = 0; s < steps; ++s) {
+        const GEnt e = sch[s * G::L + sub];
+        const int j = e.code & 0xFF, p = (e.code >> 8) & 0xFF;
+        if (live && j != 0xFF) {
+            const Q lq = qmul_norm_tab(Q{e.qx, e.qy, e.qz, e.qw}, q_of(img[base + j]), utab);
+            img[base + j] = v_of(qmul_norm_tab(q_of(img[base + p]), lq, utab));
+        }
+        wave_sync();   // this step's rows before the next step's parent reads (other lanes)
+    }
+}
+
+__host__ __device__ inline size_t retarget_lds_floats(const RetargetView &P)
+{
+    return 4 * ((size_t)P.F * P.Js + (size_t)P.F * P.K + (size_t)P.n16) + kUnitTabFloats;
+}
+
+template <bool LOCAL_IN, int F>
+__global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const float *__restrict__ src_rot,
+                                                       const float *__restrict__ src_root_t, int64_t B,
+                                                       float *__restrict__ out_rot, float *__restrict__ out_root_t,
+                                                       float *__restrict__ dump)
+{
+    extern __shared__ __attribute__((aligned(16))) float rt_lds[];
+    using G = Grp<F>;
+    const int lane = (int)threadIdx.x;
+    const int Js = P.Js, Jt = P.Jt, K = P.K;
+    const int64_t f0 = (int64_t)blockIdx.x * F;
+    const int nfr = (int)((B - f0) < F ? (B - f0) : F);
+    f4v *img = reinterpret_cast<f4v *>(rt_lds);
+    f4v *red = img + F * Js;
+    f4v *tab = red + F * K;
+    const GEnt *sch1 = reinterpret_cast<const GEnt *>(tab);
+    const GEnt *sch6 = reinterpret_cast<const GEnt *>(tab + P.o_sch6);
+    const f4v *cg = tab + P.o_cg, *tg = tab + P.o_tg, *ttqn = tab + P.o_ttq;
+    const int *kept = reinterpret_cast<const int *>(tab + P.o_int);
+    const int *spar = kept + K, *perm = spar + K, *src_of = perm + K, *tpar = src_of + Jt;
+    UnitEnt *utab = reinterpret_cast<UnitEnt *>(tab + P.n16);
+
+    // the tile's rows and root translations, all loads in flight; the plan's blob and the near-unit table meanwhile
+    GroupRows<F> rows;
+    rows.load(src_rot + f0 * Js * 4, nfr * Js);
+    const float *rp = src_root_t + (f0 + (lane < nfr ? lane : 0)) * 3;
+    const V root{rp[0], rp[1], rp[2]};
+    {
+        const f4v *gb = reinterpret_cast<const f4v *>(P.blob);
+        for (int i = lane; i < P.n16; i += 64) {
+            f4v v = gb[i];
+            if (i >= P.o_ttq && i < P.o_ttq + Jt) v = v_of(qnormalize(qconj(q_of(v))));   // :477-478, once per joint
+            tab[i] = v;
+        }
+    }
+    if (kUnitTab) unit_tab_fill(utab, lane);
+    rows.to_lds(img, nfr * Js);
+    wave_sync();
+
+    if (LOCAL_IN) rot_compose<F>(img, Js, sch1, P.steps1, nfr, utab);   // stage 1
+
+    const int nk = nfr * K;
+    const float rK = 1.0f / (float)K;   // i / K as ((i + 1/2) / K) truncated: exact for i < 2^12, K <= 64
+    for (int i = lane; i < nk; i += 64) {   // stage 2
+        const int fr = (int)(((float)i + 0.5f) * rK), k = i - fr * K;
+        red[i] = v_of(qnorm_tab(q_of(img[fr * Js + kept[k]]), utab));
+    }
+    wave_sync();   // the image is dead from here: rows [F K] of it take stages 3-6
+    const Q cid = qnormalize(qconj(qident()));   // S_red's tree quaternions are identities (:259, :477-481)
+    for (int i = lane; i < nk; i += 64) {   // stages 3-5
+        const int fr = (int)(((float)i + 0.5f) * rK), k = i - fr * K;
+        const int ks = perm[k];
+        const Q g = q_of(red[fr * K + ks]);
+        Q l = g;   // S_red's root copied (:470)
+        if (ks > 0) {
+            l = qmul_norm_tab(qconj(q_of(red[fr * K + spar[ks]])), g, utab);
+            l = qmul_norm_tab(cid, l, utab);
+        }
+        l = qnorm_tab(l, utab);                          // :735-740
+        if (k == 0) l = qmul_norm_tab(P.R, l, utab);     // :849
+        img[i] = v_of(qnorm_tab(l, utab));               // :850-855
+    }
+    const V tr = qrotate(P.R, root);                     // :853
+    wave_sync();
+
+    rot_compose<F>(img, K, sch6, P.steps6, nfr, utab);   // stage 6
+
+    if (dump) {   // plan creation's t-pose pass (B = 1): G and t' of frame 0, nothing else
+        f4v *dg = reinterpret_cast<f4v *>(dump);
+        for (int i = lane; i < K; i += 64) dg[i] = img[i];
+        if (lane == 0) {
+            dump[4 * K] = tr.x;
+            dump[4 * K + 1] = tr.y;
+            dump[4 * K + 2] = tr.z;
+        }
+        return;
+    }
+
+    for (int i = lane; i < nk; i += 64) {   // stage 7, and stage 8's normalisation (the same for every j it serves)
+        const int fr = (int)(((float)i + 0.5f) * rK), k = i - fr * K;
+        const Q d = qmul_norm_tab(q_of(img[i]), q_of(cg[k]), utab);
+        const Q n = qmul_norm_tab(d, q_of(tg[k]), utab);
+        red[i] = v_of(qnorm_tab(n, utab));
+    }
+    wave_sync();
+
+    if (lane < nfr) {   // stage 10
+        float *o = out_root_t + (f0 + lane) * 3;
+        o[0] = P.tgt_root.x + (tr.x - P.t_tp.x) * P.scale;
+        o[1] = P.tgt_root.y + (tr.y - P.t_tp.y) * P.scale;
+        o[2] = P.tgt_root.z + (tr.z - P.t_tp.z) * P.scale;
+    }
+    const int nrec = nfr * Jt;
+    const float rJ = 1.0f / (float)Jt;
+    f4v *dst = reinterpret_cast<f4v *>(out_rot + f0 * Jt * 4);
+#pragma unroll 3
+    for (int k = 0; k < G::NR; ++k) {   // stages 8-9, record-ordered: whole-wave stores
+        const int rec = k * 64 + lane;
+        if (rec < nrec) {
+            const int fr = (int)(((float)rec + 0.5f) * rJ), j = rec - fr * Jt;
+            const Q o = q_of(red[fr * K + src_of[j]]);
+            Q q = o;   // T's root copied (:470)
+            if (j > 0) {
+                q = qmul_norm_tab(qconj(q_of(red[fr * K + src_of[tpar[j]]])), o, utab);
+                q = qmul_norm_tab(q_of(ttqn[j]), q, utab);
+            }
+            st_out(dst + rec, v_of(qnorm_tab(q, utab)));   // :645-650
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- host
+static void reduce_tree(const int32_t *parents, int32_t J, const std::vector<char> &keep, std::vector<int32_t> &kept,
+                        std::vector<int32_t> &red_par)
+{
+    std::vector<int32_t> new_index(J, -1);
+    for (int j = 0; j < J; ++j) {
+        if (!keep[j]) continue;
+        int p = parents[j];
+        while (p != -1 && !keep[p]) p = parents[p];
+        new_index[j] = (int32_t)kept.size();
+        kept.push_back(j);
+        red_par.push_back(p == -1 ? -1 : new_index[p]);
+    }
+}
+
+bool retarget_tables(const int32_t *sp, int32_t Js, const int32_t *tp, int32_t Jt, const int32_t *sj,
+                     const int32_t *tj, int32_t K, RetargetTables &out, std::string &err)
+{
+    char buf[160];
+    if (Js < 1 || Jt < 1 || Js > kGroupMaxJ || Jt > kGroupMaxJ) {
+        snprintf(buf, sizeof buf, "retarget_to serves trees of 1..%d joints (source %d, target %d)", kGroupMaxJ, Js, Jt);
+        err = buf;
+        return false;
+    }
+    if (K < 1 || !sj || !tj) {
+        err = "the joint mapping is empty";
+        return false;
+    }
+    std::vector<char> ks(Js, 0), kt(Jt, 0);
+    std::vector<int32_t> src_for(Jt, -1);
+    for (int i = 0; i < K; ++i) {
+        if (sj[i] < 0 || sj[i] >= Js || tj[i] < 0 || tj[i] >= Jt) {
+            snprintf(buf, sizeof buf, "mapping pair %d = (%d, %d) is out of range (source %d, target %d joints)", i,
+                     sj[i], tj[i], Js, Jt);
+            err = buf;
+            return false;
+        }
+        if (ks[sj[i]] || kt[tj[i]]) {   // :729: the reduced trees would not have K joints each
+            err = "the joint mapping is not consistent with the skeleton trees";
+            return false;
+        }
+        ks[sj[i]] = kt[tj[i]] = 1;
+        src_for[tj[i]] = sj[i];
+    }
+    if (!ks[0] || !kt[0]) {
+        err = "the root node cannot be dropped";   // :243
+        return false;
+    }
+    out = RetargetTables{};
+    out.Js = Js, out.Jt = Jt, out.K = K;
+    reduce_tree(sp, Js, ks, out.kept_s, out.sred_par);
+    reduce_tree(tp, Jt, kt, out.kept_t, out.tred_par);
+    std::vector<int32_t> s_index(Js, -1), t_index(Jt, -1);
+    for (int k = 0; k < K; ++k) s_index[out.kept_s[k]] = k, t_index[out.kept_t[k]] = k;
+    out.perm.resize(K);
+    for (int k = 0; k < K; ++k) out.perm[k] = s_index[src_for[out.kept_t[k]]];
+    out.src_of.resize(Jt);
+    for (int j = 0; j < Jt; ++j) {
+        int a = j;
+        while (!kt[a]) a = tp[a];   // ends at the root, which is mapped
+        out.src_of[j] = t_index[a];
+    }
+    return true;
+}
+
+// List schedule of the joints j > 0 with inc[j] (an ancestor-closed set) on L lanes: a joint is ready once its parent's
+// step is past (the root needs none); each step takes up to L ready joints, longest remaining chain first, ties by
+// index (fk_group_schedule's rule).  Returns the step count.
+static int list_schedule(const int32_t *par, int J, const std::vector<char> &inc, int L, const Q *tq,
+                         std::vector<GEnt> &out)
+{
+    std::vector<int> h(J, 1), done(J, -2);
+    done[0] = -1;
+    int todo = 0;
+    for (int j = J - 1; j > 0; --j)
+        if (inc[j]) {
+            h[par[j]] = std::max(h[par[j]], h[j] + 1);
+            ++todo;
+        }
+    int steps = 0, placed = 0;
+    std::vector<int> ready;
+    while (placed < todo) {
+        ready.clear();
+        for (int j = 1; j < J; ++j)
+            if (inc[j] && done[j] == -2 && done[par[j]] != -2 && done[par[j]] < steps) ready.push_back(j);
+        std::stable_sort(ready.begin(), ready.end(), [&](int a, int b) { return h[a] > h[b]; });
+        for (int u = 0; u < L; ++u) {
+            GEnt e{0.f, 0.f, 0.f, 0xFFFF, 0.f, 0.f, 0.f, 1.f};
+            if (u < (int)ready.size()) {
+                const int j = ready[u];
+                done[j] = steps;
+                ++placed;
+                e = GEnt{0.f, 0.f, 0.f, (int32_t)((uint32_t)j | ((uint32_t)par[j] << 8)), tq[j].x, tq[j].y, tq[j].z, tq[j].w};
+            }
+            out.push_back(e);
+        }
+        ++steps;
+    }
+    return steps;
+}
+
+void retarget_blob(const RetargetTables &T, const int32_t *sp, const Q *stq, const int32_t *tp, const Q *ttq,
+                   std::vector<float> &blob, RetargetView &V_)
+{
+    const int Js = T.Js, Jt = T.Jt, K = T.K;
+    const int F = group_frames(std::max(Js, Jt)), L = 64 / F;
+    std::vector<char> inc(Js, 0);   // stage 1: the mapped joints' ancestors
+    for (int k = 0; k < K; ++k)
+        for (int a = T.kept_s[k]; a != -1 && !inc[a]; a = sp[a]) inc[a] = 1;
+    std::vector<GEnt> s1, s6;
+    const int steps1 = list_schedule(sp, Js, inc, L, stq, s1);
+    const std::vector<Q> ident(K, Q{0.f, 0.f, 0.f, 1.f});
+    const int steps6 = list_schedule(T.tred_par.data(), K, std::vector<char>(K, 1), L, ident.data(), s6);
+    V_.Js = Js, V_.Jt = Jt, V_.K = K, V_.F = F, V_.steps1 = steps1, V_.steps6 = steps6;
+    V_.o_sch6 = 2 * (int)s1.size();
+    V_.o_cg = V_.o_sch6 + 2 * (int)s6.size();
+    V_.o_tg = V_.o_cg + K;
+    V_.o_ttq = V_.o_tg + K;
+    V_.o_int = V_.o_ttq + Jt;
+    const int nint = 3 * K + 2 * Jt;
+    V_.n16 = V_.o_int + (nint + 3) / 4;
+    blob.assign((size_t)4 * V_.n16, 0.0f);
+    if (!s1.empty()) memcpy(blob.data(), s1.data(), sizeof(GEnt) * s1.size());
+    if (!s6.empty()) memcpy(blob.data() + 4 * V_.o_sch6, s6.data(), sizeof(GEnt) * s6.size());
+    memcpy(blob.data() + 4 * V_.o_ttq, ttq, sizeof(Q) * Jt);
+    int32_t *ip = reinterpret_cast<int32_t *>(blob.data() + 4 * V_.o_int);
+    for (int k = 0; k < K; ++k) ip[k] = T.kept_s[k], ip[K + k] = T.sred_par[k] < 0 ? 0 : T.sred_par[k], ip[2 * K + k] = T.perm[k];
+    for (int j = 0; j < Jt; ++j) ip[3 * K + j] = T.src_of[j], ip[3 * K + Jt + j] = tp[j] < 0 ? 0 : tp[j];
+}
+
+hipError_t launch_retarget_to(const RetargetView &P, bool local_in, const float *rot, const float *root_t, int64_t B,
+                              float *out_rot, float *out_root_t, float *dump, hipStream_t s)
+{
+    const size_t lds = sizeof(float) * retarget_lds_floats(P);
+    const dim3 g(grid_for(B, P.F)), b(64);
+    if (P.F == 16) {
+        if (local_in) hipLaunchKernelGGL((k_retarget_to<true, 16>), g, b, lds, s, P, rot, root_t, B, out_rot, out_root_t, dump);
+        else hipLaunchKernelGGL((k_retarget_to<false, 16>), g, b, lds, s, P, rot, root_t, B, out_rot, out_root_t, dump);
+    } else {
+        if (local_in) hipLaunchKernelGGL((k_retarget_to<true, 8>), g, b, lds, s, P, rot, root_t, B, out_rot, out_root_t, dump);
+        else hipLaunchKernelGGL((k_retarget_to<false, 8>), g, b, lds, s, P, rot, root_t, B, out_rot, out_root_t, dump);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace rtg

@@ -5,22 +5,26 @@ attribute layout (``_node_names``, ``_parent_indices``, ``_local_translation``,
 ``_quat``, ``_node_indices``; ``tensor``, ``_skeleton_tree``, ``_is_local``,
 ``_fps``), so the reference's pickled assets unpickle into these classes
 unchanged.  Forward / inverse kinematics (``global_transformation``,
-``local_rotation``) and the quaternion algebra run in librtg_hip.so.
+``local_rotation``), the quaternion algebra and ``retarget_to`` (one fused
+launch per call) run in librtg_hip.so.  ``drop_nodes_by_names`` /
+``keep_nodes_by_names`` are host code on the tree and existing device ops plus
+a torch reduction on a state; neither mutates the tree it is called on (the
+reference's does).
 
-Offline tools of the reference (``from_mjcf``, ``from_fbx``, ``drop_nodes_by_names``,
-``retarget_to``, ``compute_forward_vector``) are outside the hot path and not
-provided.
+Offline tools of the reference (``from_mjcf``, ``from_fbx``, ``crop``,
+``compute_forward_vector``) are outside the hot path and not provided
+(SURVEY.md §2 row 3).
 """
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import List
+from typing import Dict, List
 
 import numpy as np
 import torch
 
 from rtg import ops
-from rtg.bridge import as_tensor, back, topology
+from rtg.bridge import as_tensor, back, retarget_plan, topology
 from rtg.safe_pickle import load_skeleton_state_arrays
 
 from ..core.backend import Serializable
@@ -83,6 +87,37 @@ class SkeletonTree(Serializable):
     def topology(self):
         """Device-resident topology of this tree (cached by content)."""
         return topology(self.parent_indices, self.local_translation, self.quat)
+
+    def drop_nodes_by_names(self, node_names: List[str], pairwise_translation=None) -> "SkeletonTree":
+        """skeleton3d.py:226-259: the tree without ``node_names``; a kept node hangs from its nearest kept ancestor,
+        its translation the sum over the dropped links (or ``pairwise_translation[new parent, node]``).  This tree is
+        left as it is: the reference adds the dropped links into its own translations (:241), INTEGRATION.md."""
+        drop = set(node_names)
+        parents = [int(p) for p in self.parent_indices]
+        names, new_parents, rows, new_index = [], [], [], {}
+        for j, name in enumerate(self.node_names):
+            if name in drop:
+                continue
+            t = self.local_translation[j].clone()
+            p = parents[j]
+            if p != -1:
+                while p != -1 and self[p] in drop:
+                    t = t + self.local_translation[p]
+                    p = parents[p]
+                assert p != -1, "the root node cannot be dropped"
+                if pairwise_translation is not None:
+                    t = as_tensor(pairwise_translation)[p, j, :].to(t.device, t.dtype)
+            new_index[j] = len(names)
+            names.append(name)
+            new_parents.append(-1 if p == -1 else new_index[p])
+            rows.append(t)
+        lt = torch.stack(rows) if rows else torch.zeros(0, 3, dtype=self.local_translation.dtype)
+        return SkeletonTree(names, torch.as_tensor(new_parents, dtype=self.parent_indices.dtype), lt)
+
+    def keep_nodes_by_names(self, node_names: List[str], pairwise_translation=None) -> "SkeletonTree":
+        """skeleton3d.py:261-263"""
+        keep = set(node_names)
+        return self.drop_nodes_by_names([n for n in self if n not in keep], pairwise_translation)
 
     @classmethod
     def from_dict(cls, dict_repr, *args, **kwargs):
@@ -228,6 +263,80 @@ class SkeletonState(Serializable):
         return SkeletonState.from_rotation_and_root_translation(self.skeleton_tree, self.global_rotation,
                                                                 self.root_translation, is_local=False)
 
+    # -- reduced skeletons and the generic retarget (skeleton3d.py:668-934)
+    def _transfer_to(self, new_skeleton_tree: SkeletonTree):
+        """skeleton3d.py:676-683: this state's global rotations at the new tree's joints, as a global state."""
+        old = [self.skeleton_tree.index(n) for n in new_skeleton_tree]
+        return SkeletonState.from_rotation_and_root_translation(new_skeleton_tree, self.global_rotation[..., old, :],
+                                                                self.root_translation, is_local=False)
+
+    def drop_nodes_by_names(self, node_names: List[str],
+                            estimate_local_translation_from_states: bool = True) -> "SkeletonState":
+        """skeleton3d.py:685-702.  The averaged translation (:668-674) is computed only for the (new parent, node)
+        pairs the reduced tree reads -- mean over frames of quat_rotate(conj(G_parent), P_node - P_parent) -- not
+        as the reference's frames x J x J tensor."""
+        tree = self.skeleton_tree
+        new_tree = tree.drop_nodes_by_names(node_names)
+        if estimate_local_translation_from_states:
+            nodes = [tree.index(n) for n in new_tree]
+            pairs = [(nodes[int(p)], j) for j, p in zip(nodes, new_tree.parent_indices) if int(p) != -1]
+            J = tree.num_joints
+            pairwise = torch.zeros(J, J, 3, dtype=torch.float32)
+            if pairs:
+                pi, ni = [p for p, _ in pairs], [j for _, j in pairs]
+                G = self.global_rotation.reshape(-1, J, 4)
+                P = self.global_translation.reshape(-1, J, 3)
+                rel = ops.quat_rotate(ops.quat_inverse(G[:, pi]), P[:, ni] - P[:, pi])
+                pairwise[pi, ni] = rel.double().mean(dim=0).float().cpu()
+            new_tree = tree.drop_nodes_by_names(node_names, pairwise)
+        return self._transfer_to(new_tree)
+
+    def keep_nodes_by_names(self, node_names: List[str],
+                            estimate_local_translation_from_states: bool = True) -> "SkeletonState":
+        """skeleton3d.py:704-719 (it filters the tree's node names; the reference iterates the state and raises)."""
+        keep = set(node_names)
+        return self.drop_nodes_by_names([n for n in self.skeleton_tree if n not in keep],
+                                        estimate_local_translation_from_states)
+
+    def retarget_to(self, joint_mapping: Dict[str, str], source_tpose_local_rotation, source_tpose_root_translation,
+                    target_skeleton_tree: SkeletonTree, target_tpose_local_rotation, target_tpose_root_translation,
+                    rotation_to_target_skeleton, scale_to_target_skeleton: float, z_up: bool = True) -> "SkeletonState":
+        """skeleton3d.py:742-889 on the MI355X, one launch: this state's rotations relative to the source t-pose,
+        re-applied to the target t-pose over the mapped joints.  Returns a local state on ``target_skeleton_tree``.
+        The state needs exactly one leading batch dimension (the reference indexes it, :863 / :880); ``z_up`` is
+        accepted and unused, as there."""
+        if self.tensor.dim() != 2:
+            raise ValueError(f"retarget_to needs a state with exactly one batch dimension, got shape "
+                             f"{tuple(self.tensor.shape[:-1])}")
+        src, tgt = self.skeleton_tree, target_skeleton_tree
+        inv = {t: s for s, t in joint_mapping.items()}
+        # the reference's checks, in its order: the reduced source tree (:828), the reduced target tree, the counts (:729)
+        assert src[0] in joint_mapping, "the root node cannot be dropped"
+        assert tgt[0] in inv, "the root node cannot be dropped"
+        kept_s = [n for n in src if n in joint_mapping]
+        kept_t = [n for n in tgt if n in inv]
+        assert len({len(joint_mapping), len(kept_s), len(kept_t)}) == 1, \
+            "the joint mapping is not consistent with the skeleton trees"
+        plan = retarget_plan((src.parent_indices, src.local_translation, src.quat),
+                             (tgt.parent_indices, tgt.local_translation, tgt.quat),
+                             [src.index(s) for s in joint_mapping], [tgt.index(t) for t in joint_mapping.values()],
+                             source_tpose_local_rotation, source_tpose_root_translation, target_tpose_local_rotation,
+                             target_tpose_root_translation, rotation_to_target_skeleton, scale_to_target_skeleton)
+        rot, root = ops.retarget_to(plan, self.rotation, self.root_translation, self.is_local)
+        dev = self.tensor.device
+        return SkeletonState(SkeletonState._to_state_vector(back(rot, dev), back(root, dev)), tgt, True)
+
+    def retarget_to_by_tpose(self, joint_mapping: Dict[str, str], source_tpose: "SkeletonState",
+                             target_tpose: "SkeletonState", rotation_to_target_skeleton,
+                             scale_to_target_skeleton: float) -> "SkeletonState":
+        """skeleton3d.py:891-934 with the assertion it intends: both t-poses are single poses (the reference reads a
+        ``.shape`` a SkeletonState does not have and raises AttributeError)."""
+        assert source_tpose.tensor.dim() == 1 and target_tpose.tensor.dim() == 1, \
+            "the retargeting script currently doesn't support vectorized operations"
+        return self.retarget_to(joint_mapping, source_tpose.local_rotation, source_tpose.root_translation,
+                                target_tpose.skeleton_tree, target_tpose.local_rotation,
+                                target_tpose.root_translation, rotation_to_target_skeleton, scale_to_target_skeleton)
+
     def to_dict(self):
         def d(x):
             x = x.detach().cpu().numpy()
@@ -306,6 +415,26 @@ class SkeletonMotion(SkeletonState):
         dev = skeleton_state.tensor.device
         return cls.from_state_vector_and_velocity(skeleton_state.skeleton_tree, skeleton_state.tensor,
                                                   back(gv, dev), back(gav, dev), skeleton_state.is_local, fps)
+
+    def retarget_to(self, joint_mapping: Dict[str, str], source_tpose_local_rotation, source_tpose_root_translation,
+                    target_skeleton_tree: SkeletonTree, target_tpose_local_rotation, target_tpose_root_translation,
+                    rotation_to_target_skeleton, scale_to_target_skeleton: float, z_up: bool = True) -> "SkeletonMotion":
+        """skeleton3d.py:1185-1249: the retargeted states with their velocities at this motion's fps."""
+        return SkeletonMotion.from_skeleton_state(
+            super().retarget_to(joint_mapping, source_tpose_local_rotation, source_tpose_root_translation,
+                                target_skeleton_tree, target_tpose_local_rotation, target_tpose_root_translation,
+                                rotation_to_target_skeleton, scale_to_target_skeleton, z_up), self.fps)
+
+    def retarget_to_by_tpose(self, joint_mapping: Dict[str, str], source_tpose: "SkeletonState",
+                             target_tpose: "SkeletonState", rotation_to_target_skeleton,
+                             scale_to_target_skeleton: float, z_up: bool = True) -> "SkeletonMotion":
+        """skeleton3d.py:1251-1292"""
+        assert source_tpose.tensor.dim() == 1 and target_tpose.tensor.dim() == 1, \
+            "the retargeting script currently doesn't support vectorized operations"
+        return self.retarget_to(joint_mapping, source_tpose.local_rotation, source_tpose.root_translation,
+                                target_tpose.skeleton_tree, target_tpose.local_rotation,
+                                target_tpose.root_translation, rotation_to_target_skeleton, scale_to_target_skeleton,
+                                z_up)
 
     @staticmethod
     def _to_state_vector(rot, rt, vel, avel):

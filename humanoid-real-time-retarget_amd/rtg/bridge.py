@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .runtime import Topology, require_gpu
+from .runtime import RetargetPlan, Topology, require_gpu, require_gpu_rtg
 
 
 def as_tensor(x) -> torch.Tensor:
@@ -68,6 +68,28 @@ def topology(parent_indices, local_translation, tree_quat=None) -> Topology:
         topo = Topology(p, lt, tq)
         _TOPO_CACHE[k] = topo
     return topo
+
+
+_PLAN_CACHE: dict = {}
+
+
+def retarget_plan(src_tree, tgt_tree, src_joint, tgt_joint, src_tpose_local_rot, src_tpose_root_t,
+                  tgt_tpose_local_rot, tgt_tpose_root_t, rotation_to_target, scale) -> RetargetPlan:
+    """The device-resident plan of a ``retarget_to`` call, cached by content like ``topology``.  src_tree / tgt_tree:
+    (parent_indices, local_translation, quat) of the two skeleton trees; the mapping as joint index pairs; the t-poses
+    and the rotation as tensors or numpy, on the CPU or on the device."""
+    require_gpu_rtg()
+    sj, tj = _np(src_joint, np.int32), _np(tgt_joint, np.int32)
+    consts = [_np(a, np.float32) for a in (src_tpose_local_rot, src_tpose_root_t, tgt_tpose_local_rot,
+                                           tgt_tpose_root_t, rotation_to_target)]
+    sc = np.float32(scale)
+    trees = [(_np(t[0], np.int32), _np(t[1], np.float32), _np(t[2], np.float32)) for t in (src_tree, tgt_tree)]
+    k = _key(*trees[0], *trees[1], sj, tj, *consts, np.asarray(sc))
+    plan = _PLAN_CACHE.get(k)
+    if plan is None:
+        plan = RetargetPlan(topology(*trees[0]), topology(*trees[1]), sj, tj, *consts, float(sc))
+        _PLAN_CACHE[k] = plan
+    return plan
 
 
 def split_lead(t: torch.Tensor, tail: int) -> Tuple[torch.Size, torch.Tensor]:

@@ -15,7 +15,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import check, lib
-from .runtime import Topology, dev_f32, layout_code, ptr, require_gpu, stream_handle
+from .runtime import (RetargetPlan, Topology, dev_f32, layout_code, ptr, require_gpu, require_gpu_rtg,
+                      stream_handle)
 
 
 def _flat(t: torch.Tensor, tail: int) -> torch.Tensor:
@@ -269,6 +270,29 @@ def local_rotation(topo: Topology, g_rot, state: bool = False):
     fn = lib().rtg_state_local_rotation_f32 if state else lib().rtg_local_rotation_f32
     check(fn(topo.handle, ptr(g), B, ptr(out), stream_handle()))
     return out
+
+
+def retarget_to(plan: RetargetPlan, rot, root_t, is_local: bool = True):
+    """SkeletonState.retarget_to (skeleton3d.py:742-889) in one launch: the source state's rotations (B, J_s, 4) as
+    the state stores them (local or global per ``is_local``) and root translations (B, 3) -> the target state's local
+    rotations (B, J_t, 4) and root translations (B, 3).  Raises RtgError without a GPU: there is no CPU fallback."""
+    require_gpu_rtg()
+    Js, Jt = plan.num_source_joints, plan.num_target_joints
+    r = dev_f32(rot, (Js, 4), "rotation")
+    if r.dim() != 3:
+        raise ValueError(f"rotation must be (B, {Js}, 4), got {tuple(r.shape)}")
+    B = int(r.shape[0])
+    t = dev_f32(root_t, (3,), "root_translation")
+    if t.dim() > 2 or (t.dim() == 2 and t.shape[0] not in (1, B)):
+        raise ValueError(f"root_translation must broadcast to ({B}, 3), got {tuple(t.shape)}")
+    t = t.expand(B, 3).contiguous()
+    if r.device != plan.device:
+        raise ValueError(f"rotation is on {r.device}; this plan lives on {plan.device}")
+    out_rot = torch.empty((B, Jt, 4), device=r.device, dtype=torch.float32)
+    out_root = torch.empty((B, 3), device=r.device, dtype=torch.float32)
+    check(lib().rtg_retarget_to_f32(plan.handle, ptr(r), ptr(t), int(bool(is_local)), B, ptr(out_rot), ptr(out_root),
+                                    stream_handle()))
+    return out_rot, out_root
 
 
 def dof_forward_kinematics(model, dof, root_rot, root_t, clip: bool = False):

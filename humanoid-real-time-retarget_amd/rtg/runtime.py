@@ -16,6 +16,16 @@ from . import _lib
 from ._lib import check, lib
 
 
+def require_gpu_rtg() -> torch.device:
+    """require_gpu for the entry points that report every failure as an RtgError (retarget_to)."""
+    try:
+        return require_gpu()
+    except _lib.RtgError:
+        raise
+    except (RuntimeError, ImportError) as e:
+        raise _lib.RtgError(2, str(e)) from e   # RTG_ERR_DEVICE
+
+
 def require_gpu() -> torch.device:
     if not torch.cuda.is_available():
         raise RuntimeError("humanoid-real-time-retarget_amd: no HIP device visible; the retarget path runs only on "
@@ -125,6 +135,66 @@ class DofModel:
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib._lib is not None:
             _lib._lib.rtg_dof_model_destroy(h)
+            self._h = None
+
+
+def retarget_tables(src_parents, tgt_parents, src_joint, tgt_joint) -> dict:
+    """rtg_retarget_plan_tables (host only, no GPU needed): the tables of a retarget_to plan -- kept_src, kept_tgt,
+    src_reduced_parents, tgt_reduced_parents, perm (K each) and src_of (J_t) -- as int32 arrays.  A bad mapping raises
+    RtgError with the reference's assertion text."""
+    sp, tp, sj, tj = (_host_i32(a).reshape(-1) for a in (src_parents, tgt_parents, src_joint, tgt_joint))
+    if sj.shape != tj.shape:
+        raise ValueError("src_joint / tgt_joint lengths differ")
+    K, Jt = int(sj.shape[0]), int(tp.shape[0])
+    out = {k: np.zeros(max(n, 1), np.int32) for k, n in (("kept_src", K), ("src_reduced_parents", K), ("kept_tgt", K),
+                                                         ("tgt_reduced_parents", K), ("perm", K), ("src_of", Jt))}
+    ip = ctypes.POINTER(ctypes.c_int32)
+    check(lib().rtg_retarget_plan_tables(sp.ctypes.data_as(ip), int(sp.shape[0]), tp.ctypes.data_as(ip), Jt,
+                                         sj.ctypes.data_as(ip), tj.ctypes.data_as(ip), K,
+                                         *(out[k].ctypes.data_as(ip) for k in ("kept_src", "src_reduced_parents",
+                                                                               "kept_tgt", "tgt_reduced_parents",
+                                                                               "perm", "src_of"))))
+    return {k: v[:(Jt if k == "src_of" else K)] for k, v in out.items()}
+
+
+class RetargetPlan:
+    """Everything of a ``SkeletonState.retarget_to`` call that does not depend on the frame (``rtg_retarget_plan_t``):
+    the two trees, the joint mapping as index pairs, both t-poses, rotation_to_target_skeleton and the scale."""
+
+    def __init__(self, src: Topology, tgt: Topology, src_joint, tgt_joint, src_tpose_local_rot, src_tpose_root_t,
+                 tgt_tpose_local_rot, tgt_tpose_root_t, rotation_to_target, scale: float):
+        require_gpu_rtg()
+        sj, tj = _host_i32(src_joint).reshape(-1), _host_i32(tgt_joint).reshape(-1)
+        if sj.shape != tj.shape:
+            raise ValueError("src_joint / tgt_joint lengths differ")
+        arrs = []
+        for a, n, name in ((src_tpose_local_rot, src.num_joints * 4, "source t-pose rotations"),
+                           (src_tpose_root_t, 3, "source t-pose root translation"),
+                           (tgt_tpose_local_rot, tgt.num_joints * 4, "target t-pose rotations"),
+                           (tgt_tpose_root_t, 3, "target t-pose root translation"),
+                           (rotation_to_target, 4, "rotation_to_target_skeleton")):
+            a = _host_f32(a).reshape(-1)
+            if a.shape[0] != n:
+                raise ValueError(f"{name}: expected {n} values (a single pose), got {a.shape[0]}")
+            arrs.append(a)
+        ip, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        h = ctypes.c_void_p()
+        check(lib().rtg_retarget_plan_create(src.handle, tgt.handle, sj.ctypes.data_as(ip), tj.ctypes.data_as(ip),
+                                             int(sj.shape[0]), *(a.ctypes.data_as(fp) for a in arrs),
+                                             ctypes.c_float(float(scale)), ctypes.byref(h)))
+        self._h = h
+        self.src, self.tgt = src, tgt
+        self.num_source_joints, self.num_target_joints = src.num_joints, tgt.num_joints
+        self.device = torch.device("cuda", torch.cuda.current_device())   # owns the constants (rtg.h)
+
+    @property
+    def handle(self) -> ctypes.c_void_p:
+        return self._h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib._lib is not None:
+            _lib._lib.rtg_retarget_plan_destroy(h)
             self._h = None
 
 

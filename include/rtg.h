@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define RTG_ABI_VERSION 5   /* 5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
+#define RTG_ABI_VERSION 6   /* 6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
+                               5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
                                4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
                                   reserved), the inbox may be device memory (rtg_server_inbox_alloc), rtg_frame_server_signal;
                                3: frames the reference raises on are marked (rtg_frame_error), the solver error word, ctl[3];
@@ -158,6 +159,44 @@ int rtg_dof_fk_backward_f32(rtg_dof_model_t model, const float *dof, const float
 int rtg_fk_backward_f32(rtg_topology_t topo, const float *local_rot, const float *g_rot, const float *grad_g_rot,
                         const float *grad_g_pos, int64_t B, float *grad_local_rot, float *grad_root_t,
                         rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * SkeletonState.retarget_to (poselib skeleton3d.py:742-889): the generic skeleton-to-skeleton retarget, rotations
+ * relative to the source t-pose re-applied to the target t-pose, as ONE launch per call.
+ * A plan holds everything that does not depend on the frame.  src / tgt: the source and target trees (borrowed only
+ * during the call).  src_joint[K] / tgt_joint[K]: the joint mapping as index pairs (source joint -> target joint);
+ * both roots must be mapped ("the root node cannot be dropped", :243) and no joint may occur twice ("the joint
+ * mapping is not consistent with the skeleton trees", :729).  The t-poses' local rotations (J_s,4) / (J_t,4) and root
+ * translations (3) as handed to retarget_to (normalised here, as the reference does), rotation_to_target (4) and the
+ * scale: host pointers.  The constants (the source t-pose through the reduced trees, the target t-pose's global
+ * rotations) are evaluated on the current device, synchronously; use the plan on that device only.  Trees of more
+ * than 64 joints are RTG_ERR_UNSUPPORTED.  The pairwise average translation the reference computes (:826) never
+ * reaches its result and is not computed.
+ * ---------------------------------------------------------------------- */
+typedef struct rtg_retarget_plan_s *rtg_retarget_plan_t;
+int rtg_retarget_plan_create(rtg_topology_t src, rtg_topology_t tgt,
+                             const int32_t *src_joint, const int32_t *tgt_joint, int32_t K,
+                             const float *src_tpose_local_rot, const float *src_tpose_root_t,
+                             const float *tgt_tpose_local_rot, const float *tgt_tpose_root_t,
+                             const float *rotation_to_target, float scale, rtg_retarget_plan_t *out);
+int rtg_retarget_plan_destroy(rtg_retarget_plan_t plan);
+/* src_rot (B,J_s,4): the source state's rotations as the state stores them -- local (src_is_local != 0: the kernel
+ * runs the state FK with the source tree's quaternions) or global; src_root_t (B,3) -> tgt_local_rot (B,J_t,4), the
+ * local rotations of the target state, and tgt_root_t (B,3).  The rotation buffers are 16-byte aligned rows (any
+ * hipMalloc / torch tensor), the root translations any float alignment.  Never allocates or synchronises; B == 0 is
+ * a no-op.  A frame's NaN / inf stays in that frame's rows. */
+int rtg_retarget_to_f32(rtg_retarget_plan_t plan, const float *src_rot, const float *src_root_t, int src_is_local,
+                        int64_t B, float *tgt_local_rot, float *tgt_root_t, rtg_stream_t stream);
+/* The host tables a plan is built from (host only, no HIP call; for inspection and tests).  parents as for
+ * rtg_topology_create.  Every output may be NULL: kept_src / kept_tgt (K) the mapped joints ascending, i.e. the
+ * joints of the reduced trees (drop_nodes_by_names, :226-259); src_reduced_parents / tgt_reduced_parents (K) their
+ * parents there; perm (K) the index in the reduced source tree of the joint mapped to the reduced target tree's k-th
+ * (:721-740); src_of (J_t) the index in the reduced target tree of target joint j's nearest mapped ancestor-or-self
+ * (:876-880).  Same validation and messages as rtg_retarget_plan_create. */
+int rtg_retarget_plan_tables(const int32_t *src_parents, int32_t J_s, const int32_t *tgt_parents, int32_t J_t,
+                             const int32_t *src_joint, const int32_t *tgt_joint, int32_t K, int32_t *kept_src,
+                             int32_t *src_reduced_parents, int32_t *kept_tgt, int32_t *tgt_reduced_parents,
+                             int32_t *perm, int32_t *src_of);
 
 /* ------------------------------------------------------------------------
  * VTRDyn ingest (sim_full_body_teleop.py:92, :109-112)

@@ -5,6 +5,9 @@
   fk       -- FK throughput: Hu (B=262144), the joint-angle model and its gradient, and the mixed 4-topology
               config (4 x 65536, one launch)
   solvers  -- throughput of all four solver kinds at B=262144
+  retarget_to -- the fused SkeletonState.retarget_to launch (C ABI, preallocated outputs, B=262144, local input;
+              vtrdyn -> hu_v5 and vtrdyn_full -> hu) against the same result composed from the existing ops
+              (state FK, gathers, normalisations, state inverse FK, quat_mul_norm ...), interleaved rounds
 """
 from __future__ import annotations
 
@@ -294,6 +297,84 @@ def sweep():
         dof = torch.empty((B, 30), device="cuda")
         ms = time_events(lambda: S.retarget([body, lh, rh], out_dof=dof))
         res[str(B)] = {"kernel_us": ms * 1e3, "frames_per_s": B / (ms * 1e-3)}
+    return res
+
+
+def retarget_to(B=262144, rounds=4):
+    from rtg.bridge import retarget_plan
+    from rtg.runtime import ptr, retarget_tables, stream_handle
+    with open(os.path.join(G, "retarget_to_names.json")) as f:
+        names = json.load(f)
+    gold = np.load(os.path.join(G, "retarget_to.npz"))
+    res = {}
+    for tag in ("vtrdyn_hu_v5_local", "vtrdyn_full_hu"):
+        e = names[tag]
+        s, t = assets.load(e["source"]), assets.load(e["target"])
+        Js, Jt = len(e["source_names"]), len(e["target_names"])
+        sj = [e["source_names"].index(a) for a in e["mapping"]]
+        tj = [e["target_names"].index(b) for b in e["mapping"].values()]
+        sp, tp = s["parent_indices"].astype(np.int32), t["parent_indices"].astype(np.int32)
+        R, scale = gold[f"{tag}_R"], float(gold[f"{tag}_scale"].reshape(-1)[0])
+        tps, tps_t = s["tensor"][:Js * 4].reshape(Js, 4), s["tensor"][Js * 4:Js * 4 + 3]
+        tpt, tpt_t = t["tensor"][:Jt * 4].reshape(Jt, 4), t["tensor"][Jt * 4:Jt * 4 + 3]
+        plan = retarget_plan((sp, s["local_translation"], s["quat"]), (tp, t["local_translation"], t["quat"]), sj, tj,
+                             tps, tps_t, tpt, tpt_t, R, scale)
+        tb = {k: torch.as_tensor(v.astype(np.int64), device="cuda") for k, v in retarget_tables(sp, tp, sj, tj).items()}
+        K = len(sj)
+        gen = torch.Generator(device="cuda").manual_seed(3)
+        rot = torch.nn.functional.normalize(torch.randn((B, Js, 4), device="cuda", generator=gen), dim=-1)
+        root = torch.randn((B, 3), device="cuda", generator=gen)
+        out_rot = torch.empty((B, Jt, 4), device="cuda")
+        out_root = torch.empty((B, 3), device="cuda")
+
+        def fused():
+            _lib.check(_lib.lib().rtg_retarget_to_f32(plan.handle, ptr(rot), ptr(root), 1, B, ptr(out_rot),
+                                                      ptr(out_root), stream_handle()))
+
+        # the same stages on the existing kernels (DESIGN.md 5c lists them)
+        S = Topology(sp, s["local_translation"], s["quat"])
+        T = Topology(tp, t["local_translation"], t["quat"])
+        zK = np.zeros((K, 3), np.float32)
+        Sred = Topology(tb["src_reduced_parents"].cpu().numpy(), zK, None)
+        Tred = Topology(tb["tgt_reduced_parents"].cpu().numpy(), zK, None)
+        Rd = torch.as_tensor(R, device="cuda")
+        sc = torch.tensor(np.float32(scale), device="cuda")
+        tgt_root = torch.as_tensor(tpt_t.astype(np.float32), device="cuda")
+
+        def to_reduced(r, t3):
+            g = ops.quat_normalize(ops.forward_kinematics(S, r, t3, state=True)[0][:, tb["kept_src"]])
+            l = ops.quat_normalize(ops.local_rotation(Sred, g, state=True)[:, tb["perm"]])
+            l[:, 0] = ops.quat_mul_norm(Rd, l[:, 0])
+            l = ops.quat_normalize(l)
+            t2 = ops.quat_rotate(Rd, t3)
+            return ops.forward_kinematics(Tred, l, t2, state=True)[0], t2
+
+        G_tp, t_tp = to_reduced(ops.quat_normalize(torch.as_tensor(tps.astype(np.float32), device="cuda"))[None],
+                                torch.as_tensor(tps_t.astype(np.float32), device="cuda")[None])
+        cG = ops.quat_inverse(G_tp)
+        TG = ops.forward_kinematics(T, ops.quat_normalize(torch.as_tensor(tpt.astype(np.float32), device="cuda"))[None],
+                                    torch.zeros((1, 3), device="cuda"), state=True)[0][:, tb["kept_tgt"]]
+
+        def composed():
+            Gr, t2 = to_reduced(rot, root)
+            n = ops.quat_mul_norm(ops.quat_mul_norm(Gr, cG), TG)
+            o = ops.quat_normalize(n[:, tb["src_of"]])
+            return ops.quat_normalize(ops.local_rotation(T, o, state=True)), tgt_root + (t2 - t_tp) * sc
+
+        fused()
+        c_rot, c_root = composed()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(c_rot.view(torch.int32), out_rot.view(torch.int32)) and
+                    torch.equal(c_root.view(torch.int32), out_root.view(torch.int32)))
+        del c_rot, c_root
+        f_us, c_us = [], []
+        for _ in range(rounds):   # interleaved: both see the same box state
+            f_us.append(time_events(fused, reps=30, warm=3) * 1e3)
+            c_us.append(time_events(composed, reps=5, warm=1) * 1e3)
+        nbytes = Js * 16 + 12 + Jt * 16 + 12
+        res[tag] = {"B": B, "J_s": Js, "J_t": Jt, "K": K, "bytes_per_frame": nbytes, "fused_us": f_us,
+                    "composed_us": c_us, "fused_TBs": [B * nbytes / (u * 1e-6) / 1e12 for u in f_us],
+                    "composed_equals_fused_bits": same, "every_fused_faster": max(f_us) < min(c_us)}
     return res
 
 
