@@ -123,6 +123,10 @@
                                  // (134.6 -> 112.3 KB; SoA median 99.2 -> 97.9 us; AoS within noise and +1.4 % VALU, so
                                  // 1 = SoA only, 2 = AoS too; profiles/r06/shared_code/)
 #endif
+#ifndef RTG_EULER_LIBM
+#define RTG_EULER_LIBM 1   // scipy_as_euler: atan2 correctly rounded and hypot as the host libm computes it (rtg_math.cuh);
+                           // 0: the device library's, whose last bits differ from the host's in a third of the angles
+#endif
 #ifndef RTG_UPPER_UNIT_TAB
 #define RTG_UPPER_UNIT_TAB 1   // k_solve_sides UPPER_BODY: the arm maps normalise through the near-1.0f table
 #endif

@@ -1572,6 +1572,155 @@ RTG_DEV Q cal_joint_quat(const V (&Z)[N], const V (&M)[N], const Hook &hook = Ho
     return cal_joint_quat<N>(Z, M, unused, hook);
 }
 
+// ------------------------------------------------ the host libm's float64 atan2 / hypot for the Euler split
+// scipy's as_euler runs on the host libm (the reference and the oracle: glibc 2.35, x86-64).  With the device library's
+// atan2 / hypot about a third of the angles differed from it in their last bits, and an angle that cancels to ~1e-16
+// or sits on the +-pi wrap carries that bit into float32 (tests/test_gpu_other_solvers.py).  RTG_EULER_LIBM:
+//  * hypot as that libm computes it, bit for bit (libm_hypot_f64 below);
+//  * atan2 evaluated in double-double and rounded once (cr_atan2_f64).  The quotient, the reduction against a table of
+//    atan(k / 32) and r - r^3 / 3 are double-double (~2^-100); the tail of the series from r^5 on is plain double, which
+//    leaves ~2^-79 relative to the result.  So the result is the correctly rounded one unless the exact value lies
+//    within ~2^-79 of a rounding boundary (about one argument in 2^25); no fallback catches those.  Against a 300-bit
+//    evaluation 0 of 4000 results were misrounded.  glibc's own atan2 is not correctly rounded: it differs from this
+//    one on 7.4e-4 of random arguments, and that much of a difference from the oracle remains.
+// Another libm (an older or newer glibc, its FMA build of atan2, another platform's) may round differently: the
+// bit-exact comparisons with the oracle hold against the libm named here.
+struct DD { double h, l; };
+RTG_DEV DD dd_fast_sum(double a, double b) { const double s = a + b; return DD{s, b - (s - a)}; }   // |a| >= |b|
+RTG_DEV DD dd_two_sum(double a, double b)
+{
+    const double s = a + b, bb = s - a;
+    return DD{s, (a - (s - bb)) + (b - bb)};
+}
+RTG_DEV DD dd_two_prod(double a, double b) { const double p = a * b; return DD{p, __builtin_fma(a, b, -p)}; }
+RTG_DEV DD dd_add(DD a, DD b)
+{
+    const DD s = dd_two_sum(a.h, b.h), t = dd_two_sum(a.l, b.l);
+    const DD u = dd_fast_sum(s.h, s.l + t.h);
+    return dd_fast_sum(u.h, u.l + t.l);
+}
+RTG_DEV DD dd_neg(DD a) { return DD{-a.h, -a.l}; }
+RTG_DEV DD dd_mul(DD a, DD b)
+{
+    const DD p = dd_two_prod(a.h, b.h);
+    return dd_fast_sum(p.h, p.l + __builtin_fma(a.h, b.l, a.l * b.h));
+}
+RTG_DEV DD dd_div(DD a, DD b)
+{
+    // one division: q1 from the reciprocal (any approximation good to ~2^-50 will do), its remainder exact through the
+    // fma products, the second quotient digit from the same reciprocal: a / b to ~2^-100
+    const double inv = 1.0 / b.h;
+    const double q1 = a.h * inv;
+    const DD p = dd_two_prod(q1, b.h);
+    const double r = (((a.h - p.h) - p.l) + a.l) - q1 * b.l;
+    return dd_fast_sum(q1, r * inv);
+}
+// atan(k / 32), k = 0 .. 32, as double-double
+RTG_DEV DD dd_atan_tab(int k)
+{
+    static constexpr double T[33][2] = {
+    {0x0.0p+0, 0x0.0p+0},
+    {0x1.ffd55bba97625p-6, -0x1.5ec431444912cp-60},
+    {0x1.ff55bb72cfdeap-5, -0x1.c934d86d23f1dp-60},
+    {0x1.7ee182602f10fp-4, -0x1.cfb654c0c3d98p-58},
+    {0x1.fd5ba9aac2f6ep-4, -0x1.cd37686760c17p-59},
+    {0x1.3d6eee8c6626cp-3, 0x1.61a3b0ce9281bp-57},
+    {0x1.7b97b4bce5b02p-3, 0x1.347b0b4f881cap-58},
+    {0x1.b90d7529260a2p-3, 0x1.17b10d2e0e5abp-61},
+    {0x1.f5b75f92c80ddp-3, 0x1.8ab6e3cf7afbdp-57},
+    {0x1.18bf5a30bf178p-2, 0x1.30ca4748b1bf9p-57},
+    {0x1.362773707ebccp-2, -0x1.963a544b672d8p-57},
+    {0x1.530ad9951cd4ap-2, -0x1.2566480884082p-57},
+    {0x1.6f61941e4def1p-2, -0x1.c63aae6f6e918p-56},
+    {0x1.8b24d394a1b25p-2, 0x1.b6d0ba3748fa8p-56},
+    {0x1.a64eec3cc23fdp-2, -0x1.24dec1b50b7ffp-56},
+    {0x1.c0db4c94ec9f0p-2, -0x1.cc1ce70934c34p-56},
+    {0x1.dac670561bb4fp-2, 0x1.a2b7f222f65e2p-56},
+    {0x1.f40dd0b541418p-2, -0x1.a3992dc382a23p-57},
+    {0x1.0657e94db30d0p-1, -0x1.d5b495f6349e6p-56},
+    {0x1.1255d9bfbd2a9p-1, -0x1.2bdaee1c0ee35p-58},
+    {0x1.1e00babdefeb4p-1, -0x1.928df287a668fp-58},
+    {0x1.2958e59308e31p-1, -0x1.09e73b0c6c087p-56},
+    {0x1.345f01cce37bbp-1, 0x1.1021137c71102p-55},
+    {0x1.3f13fb89e96f4p-1, 0x1.ecf8b492644f0p-56},
+    {0x1.4978fa3269ee1p-1, 0x1.2419a87f2a458p-56},
+    {0x1.538f57b89061fp-1, -0x1.1bb74abda520cp-55},
+    {0x1.5d58987169b18p-1, 0x1.0028e4bc5e7cap-57},
+    {0x1.66d663923e087p-1, -0x1.6ea6febe8bbbap-56},
+    {0x1.700a7c5784634p-1, -0x1.8c34d25aadef6p-56},
+    {0x1.78f6bbd5d315ep-1, 0x1.406a089803740p-55},
+    {0x1.819d0b7158a4dp-1, -0x1.bf76229d3b917p-56},
+    {0x1.89ff5ff57f1f8p-1, -0x1.55b9a5e177a1bp-55},
+    {0x1.921fb54442d18p-1, 0x1.1a62633145c07p-55}};
+    return DD{T[k][0], T[k][1]};
+}
+RTG_DEV DD dd_atan01(DD t)   // atan of 0 <= t <= 1
+{
+    const int k = (int)__builtin_rint(t.h * 32.0);
+    DD r = t;
+    if (k != 0) {
+        const double c = (double)k * 0.03125;
+        const DD num = dd_add(t, DD{-c, 0.0});
+        const DD tc = dd_mul(t, DD{c, 0.0});
+        r = dd_div(num, dd_add(DD{1.0, 0.0}, tc));
+    }
+    // atan(r), |r| <= 1/64 + : r - r^3 / 3 in double-double, the tail r^5/5 - ... - r^19/19 in double
+    const DD r2 = dd_mul(r, r);
+    const DD third = dd_mul(dd_mul(r2, r), DD{0x1.5555555555555p-2, 0x1.5555555555555p-56});
+    const double z = r2.h;
+    double p = -1.0 / 19.0;
+    p = __builtin_fma(p, z, 1.0 / 17.0);
+    p = __builtin_fma(p, z, -1.0 / 15.0);
+    p = __builtin_fma(p, z, 1.0 / 13.0);
+    p = __builtin_fma(p, z, -1.0 / 11.0);
+    p = __builtin_fma(p, z, 1.0 / 9.0);
+    p = __builtin_fma(p, z, -1.0 / 7.0);
+    p = __builtin_fma(p, z, 1.0 / 5.0);
+    const double tail = p * (z * z) * r.h;
+    DD a = dd_add(r, dd_neg(third));
+    a = dd_add(a, DD{tail, 0.0});
+    return dd_add(dd_atan_tab(k), a);
+}
+RTG_DEV double cr_atan2_f64(double y, double x)
+{
+    const double ax = __builtin_fabs(x), ay = __builtin_fabs(y);
+    const double lo = ax < ay ? ax : ay, hi = ax < ay ? ay : ax;
+    // zeros, infinities, NaN and ratios beyond 2^+-200 (where the answer is a constant or the quotient itself): the library's
+    if (!(lo > 0.0) || !(hi < 0x1p900) || !(lo > 0x1p-900) || lo < hi * 0x1p-200) return ::atan2(y, x);
+    DD a = dd_atan01(dd_div(DD{lo, 0.0}, DD{hi, 0.0}));
+    if (ay > ax) a = dd_add(DD{0x1.921fb54442d18p+0, 0x1.1a62633145c07p-54}, dd_neg(a));
+    if (x < 0.0) a = dd_add(DD{0x1.921fb54442d18p+1, 0x1.1a62633145c07p-53}, dd_neg(a));
+    return __builtin_copysign(a.h + a.l, y);
+}
+// hypot as glibc 2.35 and later compute it where the compiler has no fused multiply-add (the x86-64 baseline build):
+// the algorithm of C. F. Borges, "An Improved Algorithm for hypot(a, b)" (arXiv:1904.09481: the plain square root,
+// then one correction step from differences that are exact in floating point), in the order of operations of the
+// non-FMA kernel of glibc's sysdeps/ieee754/dbl-64/e_hypot.c -- restated like glibc's e_atan2f.c above, because the
+// reference's values are that libm's.  Bit-identical with that libm's
+// hypot on 2e7 random arguments (host run).  It is not correctly rounded (0.45 % of random arguments), which is why a
+// correctly rounded hypot would not do.  Arguments outside [2^-500, 2^500], where libm rescales, take the library's.
+RTG_DEV double libm_hypot_f64(double x, double y)
+{
+    double ax = __builtin_fabs(x), ay = __builtin_fabs(y);
+    if (ax < ay) { const double t = ax; ax = ay; ay = t; }
+    if (!(ax < 0x1p500) || !(ay > 0x1p-500)) return ::hypot(x, y);   // inf, NaN, zeros, its scaled ranges
+    if (ay <= ax * 0x1p-54) return ax + ay;
+    double h = __builtin_sqrt(ax * ax + ay * ay), t1, t2;
+    if (h <= 2.0 * ay) {
+        const double delta = h - ay;
+        t1 = ax * (2.0 * delta - ax);
+        t2 = (delta - 2.0 * (ax - ay)) * delta;
+    } else {
+        const double delta = h - ax;
+        t1 = 2.0 * delta * (ax - 2.0 * ay);
+        t2 = (4.0 * delta - ay) * ay + delta * delta;
+    }
+    h -= (t1 + t2) / (2.0 * h);
+    return h;
+}
+RTG_DEV double euler_atan2(double y, double x) { return RTG_EULER_LIBM ? cr_atan2_f64(y, x) : ::atan2(y, x); }
+RTG_DEV double euler_hypot(double x, double y) { return RTG_EULER_LIBM ? libm_hypot_f64(x, y) : ::hypot(x, y); }
+
 // ------------------------------------------------ scipy Rotation (float64)
 // from_quat(q).as_euler(seq): quaternion method of Bernardes & Viollet (2022),
 // as scipy 1.15 implements it; seq given as axis indices + intrinsic flag.  Returns true when from_quat would
@@ -1596,11 +1745,11 @@ RTG_DEV bool scipy_as_euler(Q qf, int s0, int s1, int s2, bool extrinsic, double
     } else {
         a = q[3] - qj; b = qi + qk * sign; c = qj + q[3]; d = qk * sign - qi;
     }
-    ang[1] = 2.0 * ::atan2(::hypot(c, d), ::hypot(a, b));
+    ang[1] = 2.0 * euler_atan2(euler_hypot(c, d), euler_hypot(a, b));
     int kase = 0;
     if (fabs(ang[1]) <= 1e-7) kase = 1;
     else if (fabs(ang[1] - M_PI) <= 1e-7) kase = 2;
-    const double half_sum = ::atan2(b, a), half_diff = ::atan2(d, c);
+    const double half_sum = euler_atan2(b, a), half_diff = euler_atan2(d, c);
     if (kase == 0) {
         ang[0] = half_sum - half_diff;
         ang[2] = half_sum + half_diff;

@@ -1165,9 +1165,10 @@ RTG_DEV bool emit_euler_xyz_lanes_rt(const Emit &E, int L0, Q qf)
     const double a = q[3] - qj, b = qi + qk * sign, c = qj + q[3], d = qk * sign - qi;
     double at = 0.0;
     if (sub < 3) {
-        const double Y = sub == 0 ? ::hypot(c, d) : (sub == 1 ? b : d);
-        const double X = sub == 0 ? ::hypot(a, b) : (sub == 1 ? a : c);
-        at = ::atan2(Y, X);
+        // the same atan2 / hypot as scipy_as_euler (rtg_math.cuh RTG_EULER_LIBM): both copies of the split agree
+        const double Y = sub == 0 ? euler_hypot(c, d) : (sub == 1 ? b : d);
+        const double X = sub == 0 ? euler_hypot(a, b) : (sub == 1 ? a : c);
+        at = euler_atan2(Y, X);
     }
     double ang[3];
     ang[1] = 2.0 * gbc<G, 0>(at);

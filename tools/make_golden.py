@@ -22,6 +22,8 @@ Fixtures (all float32 unless noted):
   full_body_rot_edge.npz     elbows, near gimbal lock, collapsed / coplanar / mirrored hands, NaN / inf points,
   body_rot_edge.npz          zero and NaN quaternions): per frame the reference's outputs, or the exception it
   upper_body_edge.npz        raised (status 1 = RuntimeError from torch.linalg.svd, 2 = ValueError from scipy)
+  other_solvers_adversarial.npz  the first 8 frames of every hostile-input family of tests/other_solver_frames.py for
+                             UPPER_BODY, FULL_BODY_ROT and BODY_ROT: inputs, dof, local_rot, status, family name
 """
 from __future__ import annotations
 
@@ -655,6 +657,51 @@ def gen_body_rot_edge(ref, torch):
     return dict(global_rot=g, names=np.array(names), dof=dof, local_rot=lr, status=status, message=msgs)
 
 
+def gen_other_solvers_adversarial(ref, torch, per_family=8):
+    """The hostile-input families of tests/other_solver_frames.py (non-unit / tiny / huge / negated / gimbal-locked /
+    zero / NaN rotations, degenerate torso and arm points, the gripper threshold) through the reference's
+    HuUpperBodyFromMocapRetarget, VtrdynFullBodyRetargeter and Mocap2HuBodyRetargeter, frame by frame: the first
+    `per_family` frames of every family's whole wave, keys prefixed with the solver's name."""
+    path = list(sys.path)
+    sys.path[:0] = [os.path.join(REPO, "tests"), os.path.join(REPO, "oracle")]
+    try:
+        import other_solver_frames as osf   # builds its frames with rtg.synth (loaded above) and the C oracle
+        frames = {kind: osf.frames(kind) for kind in osf.NAMES}
+    finally:
+        sys.path[:] = path                  # tests/conftest.py puts the drop-in packages in front of the reference's
+    vz = rh.ref_zero_pose(ref, "vtrdyn")
+    full = rh.ref_zero_pose(ref, "vtrdyn_full")
+    hu = rh.ref_zero_pose(ref, "hu_v5")
+    br_mod = rh.load_body_retargeter_module(ref)
+    out = {}
+    for kind, name in osf.NAMES.items():
+        fams = [f[0] for f in osf.FAMILIES[kind]]
+        idx = np.concatenate([osf.wave(kind, f)[:per_family] for f in fams])
+        d = {k: np.ascontiguousarray(frames[kind][k][idx]) for k in osf.INPUTS[kind]}
+        if kind == osf.UPPER_BODY:
+            s = ref.upper_body.HuUpperBodyFromMocapRetarget(vz, hu)
+            call = lambda i: s.retarget_from_global_translation(torch.from_numpy(d["x"][i]))   # noqa: E731
+        elif kind == osf.FULL_BODY_ROT:
+            s = ref.full_body.VtrdynFullBodyRetargeter(full, hu)
+            call = lambda i: s.retarget(torch.from_numpy(d["body_rot"][i]), torch.from_numpy(d["body_pos"][i]), None,   # noqa: E731
+                                        torch.from_numpy(d["lh"][i]), None, torch.from_numpy(d["rh"][i]))
+        else:
+            s = br_mod.Mocap2HuBodyRetargeter(vz, hu)
+            call = lambda i: s.retarget_from_pose(torch.from_numpy(d["global_rot"][i]))   # noqa: E731
+        (lr, dof), status, msgs = _run_frames(call, len(idx), [(31, 4), (30,)])
+        out.update({f"{name}_{k}": v for k, v in d.items()})
+        if kind == osf.UPPER_BODY:   # the reference's own torso fit (retarget_solver.py:49-50), NaN where its SVD raises
+            def torso(i):
+                st = ref.transform3d.coord_transform(torch.from_numpy(d["x"][i]), dir=torch.Tensor([-1, -1, 1]))
+                return (ref.transform3d.cal_joint_quat(vz.local_translation[[17, 13, 11]].unsqueeze(0),
+                                                       (st[[17, 13, 11]] - st[[10]]).unsqueeze(0)),)
+            (kq,), _, _ = _run_frames(torso, len(idx), [(4,)])
+            out[f"{name}_kabsch_q"] = kq
+        out.update({f"{name}_dof": dof, f"{name}_local_rot": lr, f"{name}_status": status, f"{name}_message": msgs,
+                    f"{name}_family": np.array(np.repeat(fams, per_family)), f"{name}_frame": idx.astype(np.int32)})
+    return out
+
+
 def gen_kat(ref, torch):
     """retarget/rotation_test.py:95-152 restated as data: arm segments from known joint angles."""
     r3 = ref.rotation3d
@@ -712,6 +759,7 @@ def main() -> None:
         "upper_body_edge": lambda: gen_upper_body_edge(ref, torch),
         "full_body_rot_edge": lambda: gen_full_body_rot_edge(ref, torch),
         "body_rot_edge": lambda: gen_body_rot_edge(ref, torch),
+        "other_solvers_adversarial": lambda: gen_other_solvers_adversarial(ref, torch),
     }
     only = set(sys.argv[1:])
     for name, fn in jobs.items():
