@@ -654,17 +654,23 @@ def test_solver_full_size_properties(gpu, layout):
     assert torch.equal(dof, dof2)
 
 
+def _assert_bits(got, want):
+    """Bit-for-bit, every NaN reading alike: +0.0 and -0.0 differ (assert_array_equal calls them equal)."""
+    from retarget_to_ref import bits
+    np.testing.assert_array_equal(bits(_np(got) if isinstance(got, torch.Tensor) else got), bits(want))
+
+
 def test_motion_velocities_vs_oracle(gpu):
     import oracle as orc
     from rtg import ops
     m = golden("motion")
     w, _ = ops.gaussian_taps()
-    np.testing.assert_array_equal(_np(ops.motion_velocity(m["global_pos"], 1 / 30)), m["global_velocity"])
+    _assert_bits(_np(ops.motion_velocity(m["global_pos"], 1 / 30)), m["global_velocity"])
     av = _np(ops.motion_angular_velocity(m["global_rot"], 1 / 30))
-    np.testing.assert_array_equal(av, orc.angular_velocity(m["global_rot"], 1 / 30, w))
+    _assert_bits(av, orc.angular_velocity(m["global_rot"], 1 / 30, w))
     # unsmoothed variant and batched sequences
     lv = _np(ops.motion_velocity(np.stack([m["global_pos"]] * 3), 1 / 30, smooth=False))
-    np.testing.assert_array_equal(lv[1], orc.linear_velocity(m["global_pos"], 1 / 30, None))
+    _assert_bits(lv[1], orc.linear_velocity(m["global_pos"], 1 / 30, None))
 
 
 @pytest.mark.parametrize("nseq,L,J", [(1, 2, 1), (5, 37, 3), (3, 41, 31), (2, 19, 100), (7, 300, 24), (8, 130, 31),
@@ -682,12 +688,10 @@ def test_motion_velocities_row_tiles(gpu, nseq, L, J):
     q = g.standard_normal((nseq, L, J, 4)).astype(np.float32)
     q /= np.linalg.norm(q, axis=-1, keepdims=True)
     w, _ = ops.gaussian_taps()
-    np.testing.assert_array_equal(_np(ops.motion_velocity(p, 1 / 30)), orc.linear_velocity(p, 1 / 30, w))
-    np.testing.assert_array_equal(_np(ops.motion_velocity(p, 1 / 30, smooth=False)),
-                                  orc.linear_velocity(p, 1 / 30, None))
-    np.testing.assert_array_equal(_np(ops.motion_angular_velocity(q, 1 / 30)), orc.angular_velocity(q, 1 / 30, w))
-    np.testing.assert_array_equal(_np(ops.motion_angular_velocity(q, 1 / 30, smooth=False)),
-                                  orc.angular_velocity(q, 1 / 30, None))
+    _assert_bits(_np(ops.motion_velocity(p, 1 / 30)), orc.linear_velocity(p, 1 / 30, w))
+    _assert_bits(_np(ops.motion_velocity(p, 1 / 30, smooth=False)), orc.linear_velocity(p, 1 / 30, None))
+    _assert_bits(_np(ops.motion_angular_velocity(q, 1 / 30)), orc.angular_velocity(q, 1 / 30, w))
+    _assert_bits(_np(ops.motion_angular_velocity(q, 1 / 30, smooth=False)), orc.angular_velocity(q, 1 / 30, None))
 
 
 @pytest.mark.parametrize("sigma", [0.1, 0.2, 1.0, 3.5])
@@ -702,7 +706,6 @@ def test_motion_velocities_other_filter_radii(gpu, sigma):
     q /= np.linalg.norm(q, axis=-1, keepdims=True)
     w, radius = ops.gaussian_taps(sigma)
     assert radius == int(4 * sigma + 0.5)
-    np.testing.assert_array_equal(_np(ops.motion_velocity(p, 1 / 30, sigma=sigma)), orc.linear_velocity(p, 1 / 30, w))
-    np.testing.assert_array_equal(_np(ops.motion_angular_velocity(q, 1 / 30, sigma=sigma)),
-                                  orc.angular_velocity(q, 1 / 30, w))
+    _assert_bits(_np(ops.motion_velocity(p, 1 / 30, sigma=sigma)), orc.linear_velocity(p, 1 / 30, w))
+    _assert_bits(_np(ops.motion_angular_velocity(q, 1 / 30, sigma=sigma)), orc.angular_velocity(q, 1 / 30, w))
 

@@ -24,6 +24,10 @@ Fixtures (all float32 unless noted):
   upper_body_edge.npz        raised (status 1 = RuntimeError from torch.linalg.svd, 2 = ValueError from scipy)
   other_solvers_adversarial.npz  the first 8 frames of every hostile-input family of tests/other_solver_frames.py for
                              UPPER_BODY, FULL_BODY_ROT and BODY_ROT: inputs, dof, local_rot, status, family name
+  motion_adversarial.npz     the hostile rotation / position sequences of tests/kinematics_frames.py (L 40, J 8) through
+                             SkeletonMotion._compute_angular_velocity / _compute_velocity, smoothed and raw, fps 30 and 120
+  kinematics_adversarial.npz the 18 hostile quaternion families (8 frames each) on Hu v5 and VTRDyn-59 through
+                             cal_forward_kinematics / cal_local_rotation / SkeletonState FK and local_rotation
 """
 from __future__ import annotations
 
@@ -702,6 +706,67 @@ def gen_other_solvers_adversarial(ref, torch, per_family=8):
     return out
 
 
+def _kinematics_frames():
+    path = list(sys.path)
+    sys.path[:0] = [os.path.join(REPO, "tests"), os.path.join(REPO, "oracle")]
+    try:
+        import kinematics_frames as kf
+    finally:
+        sys.path[:] = path                  # tests/conftest.py puts the drop-in packages in front of the reference's
+    return kf
+
+
+def gen_motion_adversarial(ref, torch, L=40, J=8):
+    """The hostile rotation and position sequences of tests/kinematics_frames.py through the reference's
+    SkeletonMotion._compute_angular_velocity and _compute_velocity (skeleton3d.py:1126-1146), smoothed and raw, at
+    fps 30 and 120: rot_<family>, ang_<family>_<fps>_<smooth|raw>; pos_<family>, lin_<family>_<fps>_<smooth|raw>."""
+    kf = _kinematics_frames()
+    SM = ref.skeleton3d.SkeletonMotion
+    out = {"rot_families": np.array(kf.ROT_FAMILIES), "pos_families": np.array(kf.POS_FAMILIES)}
+    for fam in kf.ROT_FAMILIES:
+        r = kf.rot_sequence(fam, L, J)
+        out[f"rot_{fam}"] = r
+        for fps in (30, 120):
+            for smooth in (True, False):
+                v = SM._compute_angular_velocity(torch.from_numpy(r.copy()), 1 / fps, guassian_filter=smooth)
+                out[f"ang_{fam}_{fps}_{'smooth' if smooth else 'raw'}"] = t2n(v)
+    for fam in kf.POS_FAMILIES:
+        p = kf.pos_sequence(fam, L, J)
+        out[f"pos_{fam}"] = p
+        for fps in (30, 120):
+            for smooth in (True, False):
+                v = SM._compute_velocity(torch.from_numpy(p.copy()), 1 / fps, guassian_filter=smooth)
+                out[f"lin_{fam}_{fps}_{'smooth' if smooth else 'raw'}"] = t2n(v)
+    return out
+
+
+def gen_kinematics_adversarial(ref, torch, per_family=8):
+    """tests/kinematics_frames.py fk_rotations (the 18 hostile quaternion families, 8 frames each) on Hu v5 and
+    VTRDyn-59 through cal_forward_kinematics, cal_local_rotation and SkeletonState's FK and local_rotation, as
+    gen_kinematics records them.  The inputs are not stored: the helper rebuilds them, <name>_input_crc pins their bytes."""
+    import zlib
+    kf = _kinematics_frames()
+    out = {"families": np.array(kf.FK_FAMILIES)}
+    for name in ("hu_v5", "vtrdyn_full"):
+        tree = rh.ref_skeleton_state(ref, name).skeleton_tree
+        lr, rt, _ = kf.fk_rotations(tree.num_joints, per_family)
+        gr, gp = ref.rkm.cal_forward_kinematics(torch.from_numpy(lr), torch.from_numpy(rt), tree.parent_indices,
+                                                tree.local_translation)
+        loc = ref.rkm.cal_local_rotation(gr, tree.parent_indices)
+        sk = ref.skeleton3d.SkeletonState.from_rotation_and_root_translation(
+            tree, torch.from_numpy(lr.copy()), torch.from_numpy(rt), is_local=True)
+        out[f"{name}_input_crc"] = np.array(zlib.crc32(lr.tobytes() + rt.tobytes()), np.int64)
+        out[f"{name}_g_rot"] = t2n(gr)
+        out[f"{name}_g_pos"] = t2n(gp)
+        out[f"{name}_inv_local"] = t2n(loc)
+        out[f"{name}_state_g_rot"] = t2n(sk.global_rotation)
+        out[f"{name}_state_g_pos"] = t2n(sk.global_translation)
+        skg = ref.skeleton3d.SkeletonState.from_rotation_and_root_translation(
+            tree, torch.from_numpy(out[f"{name}_state_g_rot"].copy()), torch.from_numpy(rt), is_local=False)
+        out[f"{name}_state_local_rot"] = t2n(skg.local_rotation)
+    return out
+
+
 def gen_kat(ref, torch):
     """retarget/rotation_test.py:95-152 restated as data: arm segments from known joint angles."""
     r3 = ref.rotation3d
@@ -760,6 +825,8 @@ def main() -> None:
         "full_body_rot_edge": lambda: gen_full_body_rot_edge(ref, torch),
         "body_rot_edge": lambda: gen_body_rot_edge(ref, torch),
         "other_solvers_adversarial": lambda: gen_other_solvers_adversarial(ref, torch),
+        "motion_adversarial": lambda: gen_motion_adversarial(ref, torch),
+        "kinematics_adversarial": lambda: gen_kinematics_adversarial(ref, torch),
     }
     only = set(sys.argv[1:])
     for name, fn in jobs.items():
