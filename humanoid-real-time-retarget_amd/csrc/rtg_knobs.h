@@ -11,14 +11,6 @@
                             // SIMD: 1 tile 96.4-98.6 us per lone SoA launch against 93.8-94.7 for the parent in the same
                             // session, bench.py 3.77-3.79 G frames/s against 3.71-3.84 with 2; profiles/r08/)
 #endif
-#ifndef RTG_SIDES_SPLIT_READOUT
-#define RTG_SIDES_SPLIT_READOUT 0   // FULL_BODY_POS side kernel: the left wave also reads out the right chain's slots
-                                    // (round 5: medians 101.8 / 103.3 vs 102.9 / 104.0 us SoA; off since round 6's
-                                    // RTG_SIDES_ARMS2 shortened the right wave: 99.3 vs 100.6 us, profiles/r06/arms2/)
-#endif
-#ifndef RTG_SIDES_ARMS2
-#define RTG_SIDES_ARMS2 1   // FULL_BODY_POS side kernel: both arm chains in one instruction stream (fbp_arms2)
-#endif
 #ifndef RTG_SIDES_EARLY_WORDS
 #define RTG_SIDES_EARLY_WORDS 1   // FULL_BODY_POS side kernel, AoS inputs: each read-out's table word loaded into LDS
                                   // when its link is emitted (global_load_lds), not in the read-out's batch
@@ -89,27 +81,12 @@
                          // (A/B knob, same values: SoA 93.2-94.5 vs 95.3-96.6 us in one session, medians 94.6 vs 95.0 in a
                          // second; 8 rounds pooled 94.3 vs 95.6 mean; profiles/r07/ab_headline*.log)
 #endif
-#ifndef RTG_EXP_ACOS_LIBM
-#define RTG_EXP_ACOS_LIBM 0   // A/B knob (same values): cr_acos as round 4's libm f64 acos
-#endif
-#ifndef RTG_EXP_EULER_SCIPY
-#define RTG_EXP_EULER_SCIPY 0   // A/B knob (same values): the 'XYZ' split through the scipy restatement for every frame
-#endif
-#ifndef RTG_VEL_IEEE_DIV
-#define RTG_VEL_IEEE_DIV 0   // A/B knob (same values): the velocity tiles' quotients by dt as IEEE divisions (round 4)
-#endif
 #ifndef RTG_DOF_NT_STORE
 #define RTG_DOF_NT_STORE 1   // A/B knob (same values): the solvers' DOF rows (whole 128-B lines) as non-temporal stores
                              // (headline 101.3 vs 104.5 us SoA, 114.4 vs 117.7 AoS; profiles/r05/nt/)
 #endif
-#ifndef RTG_IN_NT_LOAD
-#define RTG_IN_NT_LOAD 0   // A/B knob (same values): the solvers' SoA input planes loaded non-temporal
-#endif
 #ifndef RTG_VEL_W
 #define RTG_VEL_W 8   // velocity tiles: consecutive smoothed outputs per thread (8 vs 4: linear 61.2 vs 65.1 us, angular 110.5 vs 113.1)
-#endif
-#ifndef RTG_VEL_ANG_NWAY
-#define RTG_VEL_ANG_NWAY 1   // angular velocity tile: a batch's NB elements on the N-way leaf math (rtg_math.cuh)
 #endif
 #ifndef RTG_DOF_NWAY
 #define RTG_DOF_NWAY 4   // HuForwardModel lane groups: joint rotations per N-way group (one rare-case branch each)
@@ -140,28 +117,9 @@
 #define RTG_SIDES_UNIT_TAB_AOS 1   // the same for AoS: the fits only (the arm maps push it to 138-141 VGPRs, 3 waves/SIMD;
                                   // without the tip preload all sites fit in 120 but measured slower, profiles/r06/unit_tab/)
 #endif
-#ifndef RTG_FRAME1_SHARED_CODE
-#define RTG_FRAME1_SHARED_CODE 3   // k_fbp_frame1 / k_frame_server: 1 the two wrist (arm) waves run one copy of their code
-                                   // (120 -> 81 KB; B = 1 12.61-12.83 -> 12.32-12.42 us); 3 also the three fits one
-                                   // INLINED SVD copy after a per-wave A (60 KB): 12.13-12.38 us.  (2, an out-of-line
-                                   // shared SVD, measured slower -- 12.64-12.89 us, call overhead -- and was removed;
-                                   // profiles/r06/shared_code/)
-#endif
-#ifndef RTG_QUAD_SHARED_CODE
-#define RTG_QUAD_SHARED_CODE 3   // k_fbp_quad: the same code sharing, levels 1 / 3 (config 2: level 0 16.71-16.75, 1
-                                 // 16.54-16.57, 3 16.32-16.35 us vs 16.48-16.50 for level 1 in its own A/B)
-#endif
-#ifndef RTG_LAT5_SHARED_CODE
-#define RTG_LAT5_SHARED_CODE 0   // A/B knob (same values), k_fbp_latency5: the frame1 / quad code sharing; measured mixed
-                                 // (24576-32768 frames +3 %, 49152 -2 %; profiles/r06/shared_code/latency5/), off
-#endif
 #ifndef RTG_FRAME1_UNIT_TAB
 #define RTG_FRAME1_UNIT_TAB 6   // k_fbp_frame1 / k_frame_server (B = 1): the near-1.0f table at (1 fits | 6 arm maps + Euler
                                 // split); 6: 12.65-12.80 vs 12.88-13.10 us (profiles/r06/unit_tab/latency/)
-#endif
-#ifndef RTG_LAT_UNIT_TAB
-#define RTG_LAT_UNIT_TAB 0   // A/B knob (same values), k_fbp_quad / k_fbp_latency5: the near-1.0f table at (1 fits | 6 arm maps + Euler split);
-                             // all sites: B = 1 12.7-13.0 vs 12.9-13.2 us, config 2 17.2 vs 16.8 us (slower), profiles/r06/unit_tab/
 #endif
 #ifndef RTG_FK_UNIT_TAB
 #define RTG_FK_UNIT_TAB 1   // lane-group FK / inverse FK / HuForwardModel compose: qmul_norm through the near-1.0f table

@@ -110,9 +110,6 @@ RTG_DEV float acos_fast(float x, bool &ok)
 }
 RTG_DEV float cr_acos(float x)
 {
-#if RTG_EXP_ACOS_LIBM   // A/B knob (same values): round 4's libm f64 acos everywhere
-    return acos_libm(x);
-#endif
     bool ok;
     float r = acos_fast(x, ok);
     if (!(RTG_EXP_NO_RARE & 2) && __builtin_expect(!ok, 0)) r = acos_libm_call(x);
@@ -1865,9 +1862,6 @@ RTG_DEV bool quat_in_xyz_axis(Q q, int s0, int s1, int s2, bool extrinsic, Q out
 // :121/138): the atan2-free form above, the scipy restatement where it declines.  Same values (check [7]).
 RTG_DEV bool quat_in_xyz_intrinsic(Q q, Q out[3])
 {
-#if RTG_EXP_EULER_SCIPY   // A/B knob (same values): the scipy restatement for every frame (round 4)
-    return quat_in_xyz_axis(q, 0, 1, 2, false, out);
-#endif
     bool refused = false;
     if (__builtin_expect(!quat_in_xyz_fast(q, out), 0)) refused = quat_in_xyz_axis(q, 0, 1, 2, false, out);
     return refused;

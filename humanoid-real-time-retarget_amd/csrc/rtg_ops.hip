@@ -561,11 +561,6 @@ __global__ __launch_bounds__(256) void k_velocity_tile(const float *__restrict__
 #pragma unroll
                 for (int k = 0; k < SEG + 2; ++k) raw[k] = k < nr + 2 ? q[(int64_t)k * C] : 0.0f;
                 // np.gradient inside the sequence: (p[t+1] - p[t-1]) / 2 (x / 2 == x * 0.5, correctly rounded)
-#if RTG_VEL_IEEE_DIV   // A/B knob (same values): one IEEE division per gradient
-#pragma unroll
-                for (int j = 0; j < SEG; ++j)
-                    if (j < nr) dst[j] = ((raw[j + 2] - raw[j]) * 0.5f) / dt;
-#else
                 // the SEG quotients by dt through the shared reciprocal (mulr_k: one rare-case branch per run)
                 float g[SEG], v[SEG];
 #pragma unroll
@@ -574,7 +569,6 @@ __global__ __launch_bounds__(256) void k_velocity_tile(const float *__restrict__
 #pragma unroll
                 for (int j = 0; j < SEG; ++j)
                     if (j < nr) dst[j] = v[j];
-#endif
             } else {
                 for (int j = 0; j < nr; ++j) {
                     const int x = x0 + j;
@@ -614,7 +608,7 @@ __global__ __launch_bounds__(256) void k_velocity_tile(const float *__restrict__
             }
         };
         if (threadIdx.x < n) fetch(threadIdx.x);
-#if RTG_VEL_UNIT_TAB && RTG_VEL_ANG_NWAY && !RTG_VEL_IEEE_DIV
+#if RTG_VEL_UNIT_TAB
         // the near-unit normalisation table (rtg_math.cuh) for the quaternion products, filled while the first loads fly
         __shared__ UnitEnt utab[2 * kUnitTabK + 1];
         unit_tab_fill(utab, (int)threadIdx.x);
@@ -626,7 +620,6 @@ __global__ __launch_bounds__(256) void k_velocity_tile(const float *__restrict__
             uint32_t cat[NB];
 #pragma unroll
             for (int k = 0; k < NB; ++k) { ca[k] = qa[k]; cb[k] = qb[k]; cl[k] = last[k]; cat[k] = at[k]; }
-#if RTG_VEL_ANG_NWAY && !RTG_VEL_IEEE_DIV
             // round 6: the NB elements on the N-way leaf math (one rare-case branch per step for all of them, so
             // their instruction streams interleave); every element's value as below.  Elements past the rows and
             // last frames compute on whatever they hold and are replaced / not stored.
@@ -668,25 +661,6 @@ __global__ __launch_bounds__(256) void k_velocity_tile(const float *__restrict__
                         sg[cat[k] + 2 * NS] = av[k].z;
                     }
             }
-#else
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                if (e0 + 256u * k >= n) continue;
-                Q d = qident();
-                if (!cl[k]) d = qmul_norm(ca[k], qconj(cb[k]));
-                const Q aa = qangle_axis_abs(d);
-#if RTG_VEL_IEEE_DIV
-                sg[cat[k]] = (aa.y * aa.x) / dt;
-                sg[cat[k] + NS] = (aa.z * aa.x) / dt;
-                sg[cat[k] + 2 * NS] = (aa.w * aa.x) / dt;
-#else
-                const V av = mulr_v(V{aa.y * aa.x, aa.z * aa.x, aa.w * aa.x}, Rcp{vt.rdt, dt});
-                sg[cat[k]] = av.x;
-                sg[cat[k] + NS] = av.y;
-                sg[cat[k] + 2 * NS] = av.z;
-#endif
-            }
-#endif
             if (e0 + 256 * NB < n) fetch(e0 + 256 * NB);
         }
     }
@@ -1064,8 +1038,8 @@ int probe_valu_iters() { return kProbeIters; }
 extern "C" const char *rtg_build_info(void)
 {
     return "{\"abi\":" RTG_STR(RTG_ABI_VERSION) ",\"arch\":\"gfx950\",\"knobs\":{"
-        RTG_KNOB(RTG_DOF_NWAY) RTG_KNOB(RTG_DOF_UNIT_TAB) RTG_KNOB(RTG_FK_UNIT_TAB) RTG_KNOB(RTG_UNIT_TAB_K) RTG_KNOB(RTG_SIDES_SHARED_FIT) RTG_KNOB(RTG_UPPER_UNIT_TAB) RTG_KNOB(RTG_ROT_UNIT_TAB) RTG_KNOB(RTG_EULER_LIBM) RTG_KNOB(RTG_SIDES_UNIT_TAB) RTG_KNOB(RTG_SIDES_UNIT_TAB_AOS) RTG_KNOB(RTG_LAT_UNIT_TAB) RTG_KNOB(RTG_FRAME1_UNIT_TAB) RTG_KNOB(RTG_FRAME1_SHARED_CODE) RTG_KNOB(RTG_QUAD_SHARED_CODE) RTG_KNOB(RTG_LAT5_SHARED_CODE) RTG_KNOB(RTG_VEL_UNIT_TAB) RTG_KNOB(RTG_SIDES_SOA_WAVES) RTG_KNOB(RTG_SIDES_UNIFORM_WAVE) RTG_KNOB(RTG_SIDES_TILES) RTG_KNOB(RTG_SIDES_SPLIT_READOUT) RTG_KNOB(RTG_SIDES_ARMS2) RTG_KNOB(RTG_SIDES_EARLY_WORDS) RTG_KNOB(RTG_AOS_PRELOAD_TIPS) RTG_KNOB(RTG_QUAD8_MAX_B) RTG_KNOB(RTG_QUAD_MAX_B) RTG_KNOB(RTG_LATENCY_MAX_B)
-        RTG_KNOB(RTG_EXP_TIMESTAMPS) RTG_KNOB(RTG_EXP_SKIP_SIGNAL) RTG_KNOB(RTG_EXP_STUB_SVD) RTG_KNOB(RTG_EXP_NO_TABLE) RTG_KNOB(RTG_EXP_MULR_NOBRANCH) RTG_KNOB(RTG_FK_F16_MAXJ) RTG_KNOB(RTG_FK_NT_OUT) RTG_KNOB(RTG_TORSO_X0) RTG_KNOB(RTG_EXP_ACOS_LIBM) RTG_KNOB(RTG_EXP_EULER_SCIPY) RTG_KNOB(RTG_VEL_SEG) RTG_KNOB(RTG_VEL_LDS_MIN) RTG_KNOB(RTG_VEL_IEEE_DIV) RTG_KNOB(RTG_DOF_NT_STORE) RTG_KNOB(RTG_IN_NT_LOAD) RTG_KNOB(RTG_VEL_W) RTG_KNOB(RTG_VEL_ANG_NB) RTG_KNOB(RTG_VEL_ANG_NWAY) RTG_KNOB(RTG_EXP_NO_RARE)
+        RTG_KNOB(RTG_DOF_NWAY) RTG_KNOB(RTG_DOF_UNIT_TAB) RTG_KNOB(RTG_FK_UNIT_TAB) RTG_KNOB(RTG_UNIT_TAB_K) RTG_KNOB(RTG_SIDES_SHARED_FIT) RTG_KNOB(RTG_UPPER_UNIT_TAB) RTG_KNOB(RTG_ROT_UNIT_TAB) RTG_KNOB(RTG_EULER_LIBM) RTG_KNOB(RTG_SIDES_UNIT_TAB) RTG_KNOB(RTG_SIDES_UNIT_TAB_AOS) RTG_KNOB(RTG_FRAME1_UNIT_TAB) RTG_KNOB(RTG_VEL_UNIT_TAB) RTG_KNOB(RTG_SIDES_SOA_WAVES) RTG_KNOB(RTG_SIDES_UNIFORM_WAVE) RTG_KNOB(RTG_SIDES_TILES) RTG_KNOB(RTG_SIDES_EARLY_WORDS) RTG_KNOB(RTG_AOS_PRELOAD_TIPS) RTG_KNOB(RTG_QUAD8_MAX_B) RTG_KNOB(RTG_QUAD_MAX_B) RTG_KNOB(RTG_LATENCY_MAX_B)
+        RTG_KNOB(RTG_EXP_TIMESTAMPS) RTG_KNOB(RTG_EXP_SKIP_SIGNAL) RTG_KNOB(RTG_EXP_STUB_SVD) RTG_KNOB(RTG_EXP_NO_TABLE) RTG_KNOB(RTG_EXP_MULR_NOBRANCH) RTG_KNOB(RTG_FK_F16_MAXJ) RTG_KNOB(RTG_FK_NT_OUT) RTG_KNOB(RTG_TORSO_X0) RTG_KNOB(RTG_VEL_SEG) RTG_KNOB(RTG_VEL_LDS_MIN) RTG_KNOB(RTG_DOF_NT_STORE) RTG_KNOB(RTG_VEL_W) RTG_KNOB(RTG_VEL_ANG_NB) RTG_KNOB(RTG_EXP_NO_RARE)
         "\"RTG_EXP_HOT_INPUTS\":\"" RTG_STR(RTG_EXP_HOT_INPUTS) "\"},\"wrong_answer_knobs\":"
         RTG_STR(RTG_WRONG_ANSWER_KNOBS) "}";
 }

@@ -190,44 +190,6 @@ RTG_DEV void link_rt(const Emit &E, int link, Q q)
     E.st[(link <= 18 ? link - 12 : link - 14) * E.sst] = make_float2(q.w, k == 0 ? q.x : (k == 1 ? q.y : q.z));
     if (E.lr) st4(E.lr + 4 * link, q);
 }
-// solve_arm / emit_euler_xyz with a run-time first link: two waves of a side pair run one copy of the code
-template <typename Tab = NoTab>
-RTG_DEV Q solve_arm_rt(const Emit &E, int L0, V upper, V fore, ArmZero zs, ArmZero ze, Q parent, Tab tab = Tab{})
-{
-    Q p, r, y, e;
-    {
-        const V v[1] = {upper};
-        const ArmZero z[1] = {zs};
-        const Q par[1] = {parent};
-        Q a[1], b[1];
-        arm_pair_n<true, 1>(v, z, par, a, b, tab);
-        p = a[0];
-        r = b[0];
-    }
-    link_rt(E, L0, p);
-    link_rt(E, L0 + 1, r);
-    {
-        const V v[1] = {fore};
-        const ArmZero z[1] = {ze};
-        const Q par[1] = {qmul(qmul(parent, p), r)};
-        Q a[1], b[1];
-        arm_pair_n<false, 1>(v, z, par, a, b, tab);
-        y = a[0];
-        e = b[0];
-    }
-    link_rt(E, L0 + 2, y);
-    link_rt(E, L0 + 3, e);
-    return qmul(qmul(qmul(p, r), y), e);
-}
-RTG_DEV bool emit_euler_xyz_rt(const Emit &E, int L0, Q local)
-{
-    Q eul[3];
-    const bool refused = quat_in_xyz_intrinsic(local, eul);
-    link_rt(E, L0, eul[0]);
-    link_rt(E, L0 + 1, eul[1]);
-    link_rt(E, L0 + 2, eul[2]);
-    return refused;
-}
 // quat_in_xyz_axis(q, 'XYZ') -> links L0..L0+2; true where scipy refuses q (transform3d.py:53)
 template <int L0>
 RTG_DEV bool emit_euler_xyz(const Emit &E, Q local)
@@ -261,11 +223,7 @@ template <>
 struct FV<true> {
     const float *__restrict__ p;
     int64_t s;
-    RTG_DEV float e(int64_t i) const
-    {
-        if (RTG_IN_NT_LOAD) return __builtin_nontemporal_load(p + i);   // A/B knob: streaming input planes
-        return p[i];
-    }
+    RTG_DEV float e(int64_t i) const { return p[i]; }
     RTG_DEV V p3(int j) const { return V{e((3 * j) * s), e((3 * j + 1) * s), e((3 * j + 2) * s)}; }
     RTG_DEV Q q4(int j) const { return Q{e((4 * j) * s), e((4 * j + 1) * s), e((4 * j + 2) * s), e((4 * j + 3) * s)}; }
 };
@@ -352,19 +310,6 @@ RTG_DEV Q fbp_wrist_fit(const SolverConsts &C, const View &H, bool &svd_nan, con
     const V M[5] = {vsub(H.p3(2), h0), vsub(H.p3(6), h0), vsub(H.p3(10), h0), vsub(H.p3(14), h0), vsub(H.p3(17), h0)};
     return cal_joint_quat<5>(SIDE ? C.Zr : C.Zl, M, svd_nan, hook, tab);
 }
-// fbp_wrist_fit with a run-time side (the B = 1 kernel: both wrist waves run ONE copy of the fit's code, not two
-// template instances -- the I-cache then holds one; RTG_FRAME1_SHARED_CODE).  Z is C.Zl or C.Zr itself: the same bits.
-template <typename View, typename Hook = NoHook, typename Tab = NoTab>
-RTG_DEV Q fbp_wrist_fit_rt(const SolverConsts &C, const View &H, int side, bool &svd_nan, const Hook &hook = Hook{},
-                           Tab tab = Tab{})
-{
-    const V h0 = H.p3(0);
-    const V M[5] = {vsub(H.p3(2), h0), vsub(H.p3(6), h0), vsub(H.p3(10), h0), vsub(H.p3(14), h0), vsub(H.p3(17), h0)};
-    V Z[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) Z[k] = side ? C.Zr[k] : C.Zl[k];
-    return cal_joint_quat<5>(Z, M, svd_nan, hook, tab);
-}
 // A side's body points (shoulder, elbow, wrist), loaded at kernel start with the torso / wrist-fit loads of the
 // same rows (measured -4 %: DESIGN.md §5), and its hand points for the gripper (0 and the tips 4,8,12,16,19).
 struct ArmPts { V sh, el, wr; };
@@ -380,13 +325,6 @@ RTG_DEV TipPts load_tips(const View &H)
     return TipPts{H.p3(0), {H.p3(4), H.p3(8), H.p3(12), H.p3(16), H.p3(19)}};
 }
 
-// one arm's chain from its points and R10 (full_body_pos_retargeter.py:75-93)
-template <int SIDE>
-RTG_DEV Q fbp_arm(const SolverConsts &C, const ArmPts &ap, Q R10, const Emit &E)
-{
-    return solve_arm<SIDE ? 21 : 12>(E, vsub(ap.el, ap.sh), vsub(ap.wr, ap.el), SIDE ? C.rsh : C.lsh,
-                                     SIDE ? C.rel : C.lel, R10);
-}
 // Both arms' chains at once (round 6): solve_arm for the left and the right arm on the N-way leaf math, so the two
 // independent chains interleave in one instruction stream (the same values: arm_pair_n).  Returns the chains.
 template <typename Tab = NoTab>
@@ -609,7 +547,7 @@ __global__ __launch_bounds__(kSideThreads, (side_min_waves<KIND, SOA>())) void k
         // Euler split / gripper -- 1.5 SVD-equivalents per wave.  Two per-tile LDS flags hand R10 (left -> right)
         // and the left chain (right -> left) over, so each wave waits only for what it reads; a third counts the
         // waves out, and the second one to finish stores the tile's DOF rows while the first exits.
-        __shared__ int sflag[kSideTiles][4];   // per tile: [0] R10 ready, [1] left chain ready, [2] waves done, [3] right chain ready
+        __shared__ int sflag[kSideTiles][4];   // per tile: [0] R10 ready, [1] left chain ready, [2] waves done, [3] unused (pitch)
         if (threadIdx.x < 4 * kSideTiles) (&sflag[0][0])[threadIdx.x] = 0;
         // the near-unit normalisation table (rtg_math.cuh), per site: 1 the fits' quaternions, 2 the arm maps'
         // angle-axis quaternions, 4 the Euler split's products (RTG_SIDES_UNIT_TAB for SoA, _AOS for AoS)
@@ -702,8 +640,7 @@ __global__ __launch_bounds__(kSideThreads, (side_min_waves<KIND, SOA>())) void k
         TS(4);
         Q chain = qident();
         if (side) {
-#if RTG_SIDES_ARMS2
-            // both arm chains in one instruction stream (fbp_arms2), then both hand-overs
+            // both arm chains in one instruction stream (fbp_arms2), then the hand-over
             if (live) {
                 R10 = slot_get(E.row);   // read R10 before the same lane overwrites the slot with the chain
                 Q cl;
@@ -712,17 +649,6 @@ __global__ __launch_bounds__(kSideThreads, (side_min_waves<KIND, SOA>())) void k
             }
             if (wds) Emit::wait_words();   // the left chain's table words (slots 0-3) have landed in LDS
             lds_signal(&fl[1]);   // the left chain and its exp-map slots 0-3 are in LDS
-            if (RTG_SIDES_SPLIT_READOUT) lds_signal(&fl[3]);   // the right chain's exp-map slots 7-10 are in LDS
-#else
-            if (live) {
-                R10 = slot_get(E.row);   // read R10 before the same lane overwrites the slot with the chain
-                const Q cl = fbp_arm<0>(C, apL, R10, E);
-                slot_put(E.row, cl);
-            }
-            lds_signal(&fl[1]);   // the left chain and its exp-map slots 0-3 are in LDS
-            if (live) chain = fbp_arm<1>(C, apR, R10, E);
-            if (RTG_SIDES_SPLIT_READOUT) lds_signal(&fl[3]);   // the right chain's exp-map slots 7-10 are in LDS
-#endif
         } else if (live) {
             emit_fixed_links(E, true, kSlotDwords);   // the slot's dwords stay the right wave's until the chain is read
             bool nan = false;
@@ -746,19 +672,8 @@ __global__ __launch_bounds__(kSideThreads, (side_min_waves<KIND, SOA>())) void k
         }
         TS(7);
         // exp-map read-out: the left wave reads slots 0-6 (the left chain's 0-3, written by the right wave before
-        // the flag, and its own wrist's 4-6), the right wave 7-13 (all its own).  RTG_SIDES_SPLIT_READOUT: the left
-        // wave (the shorter program) also reads the right chain's slots 7-10, after the right wave's flag for them
-        if (RTG_SIDES_SPLIT_READOUT) {
-            if (side) {
-                if (live) E.finalize(11, 3);
-            } else {
-                if (live) E.finalize(0, 7);
-                lds_wait(&fl[3], C.err);
-                if (live) E.finalize(7, 4);
-            }
-        } else if (live) {
-            E.finalize(side ? 7 : 0, 7);
-        }
+        // the flag, and its own wrist's 4-6), the right wave 7-13 (all its own)
+        if (live) E.finalize(side ? 7 : 0, 7);
         st = side ? ((fit1_nan ? kStRightSvd : 0u) | (euler_refused ? kStRightEuler : 0u))
                   : ((fit1_nan ? kStTorsoSvd : 0u) | (fit2_nan ? kStLeftSvd : 0u) | (euler_refused ? kStLeftEuler : 0u));
         sstat[side][r] = (uint8_t)st;
@@ -893,14 +808,10 @@ RTG_DEV void fbp_latency5_tile(const SolverConsts &C, const float *__restrict__ 
     __shared__ float2 sst[14 * kLatFrames];
     __shared__ int sflag[3];                   // R10 ready, left arm ready, right arm ready
     __shared__ uint8_t sstat[3][kLatFrames];   // status bits of the torso wave and the two wrist waves
-    __shared__ UnitEnt sut[2 * kUnitTabK + 1];   // the near-unit normalisation table (RTG_LAT_UNIT_TAB)
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t f = f0 + lane;
     const bool live = f < B;
     if (threadIdx.x < 3) sflag[threadIdx.x] = 0;
-    if (RTG_LAT_UNIT_TAB) unit_tab_fill(sut, (int)threadIdx.x - 256);   // wave 4 (the arm wave with the least to do)
-    const auto tabF = TabSel<(RTG_LAT_UNIT_TAB & 1) != 0>::get(sut);
-    const auto tab = TabSel<(RTG_LAT_UNIT_TAB & 6) != 0>::get(sut);
     __syncthreads();
 #if RTG_EXP_TIMESTAMPS
     float *const tsb = body_rot;
@@ -922,34 +833,12 @@ RTG_DEV void fbp_latency5_tile(const SolverConsts &C, const float *__restrict__ 
     auto view = [&](const float *base, int row_floats) { return frame_view<SOA>(base, f, row_floats, B); };
     const auto b = view(in0, 63);
     bool fit_nan = false, euler_refused = false;   // this wave's raise points (lane masks, not a VGPR)
-    // RTG_LAT5_SHARED_CODE: the three fits form their A per wave and run ONE inlined copy of the SVD; the two waves
-    // of each side pair run one copy of their code (run-time side); the same operations on the same operands
-    constexpr bool kShared = RTG_LAT5_SHARED_CODE != 0;
-    Q fitq = qident();
-    if (kShared && w < 3 && live) {
-        float A[9];
-        if (w == 0) {
-            const V b10 = b.p3(10);
-            const V Mt[3] = {vsub(b.p3(17), b10), vsub(b.p3(13), b10), vsub(b.p3(11), b10)};
-            fit_nan = form_joint_A<3>(C.Zt, Mt, A);
-        } else {
-            const auto H = view(w == 2 ? in2 : in1, 60);
-            const V h0 = H.p3(0);
-            const V M[5] = {vsub(H.p3(2), h0), vsub(H.p3(6), h0), vsub(H.p3(10), h0), vsub(H.p3(14), h0),
-                            vsub(H.p3(17), h0)};
-            V Z[5];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) Z[k] = w == 2 ? C.Zr[k] : C.Zl[k];
-            fit_nan = form_joint_A<5>(Z, M, A);
-        }
-        fitq = joint_quat_of_A(A, hook, tabF);
-    }
     if (w == 0) {
         if (live) {
             bool nan = false;
-            const Q q = kShared ? fitq : fbp_torso(C, b, nan, hook, tabF);
+            const Q q = fbp_torso(C, b, nan, hook);
             sfit[lane] = make_float4(q.x, q.y, q.z, q.w);
-            if (!kShared) fit_nan = nan;
+            fit_nan = nan;
         }
         lds_signal(&sflag[0]);
         TS(1);
@@ -966,9 +855,7 @@ RTG_DEV void fbp_latency5_tile(const SolverConsts &C, const float *__restrict__ 
             const float4 t = sfit[lane];
             const Q R10{t.x, t.y, t.z, t.w};
             const V up = vsub(ap.el, ap.sh), fo = vsub(ap.wr, ap.el);
-            const Q ch = kShared ? solve_arm_rt(E, side ? 21 : 12, up, fo, side ? C.rsh : C.lsh, side ? C.rel : C.lel, R10, tab)
-                         : side ? solve_arm<21>(E, up, fo, C.rsh, C.rel, R10, tab)
-                                : solve_arm<12>(E, up, fo, C.lsh, C.lel, R10, tab);
+            const Q ch = side ? solve_arm<21>(E, up, fo, C.rsh, C.rel, R10) : solve_arm<12>(E, up, fo, C.lsh, C.lel, R10);
             schain[side][lane] = make_float4(ch.x, ch.y, ch.z, ch.w);
         }
         lds_signal(&sflag[1 + side]);
@@ -981,13 +868,9 @@ RTG_DEV void fbp_latency5_tile(const SolverConsts &C, const float *__restrict__ 
         Q W = qident();
         TipPts tp{};
         if (live) {
-            if (kShared) {
-                W = fitq;
-            } else {
-                bool nan = false;
-                W = side ? fbp_wrist_fit<1>(C, H, nan, hook, tabF) : fbp_wrist_fit<0>(C, H, nan, hook, tabF);
-                fit_nan = nan;
-            }
+            bool nan = false;
+            W = side ? fbp_wrist_fit<1>(C, H, nan, hook) : fbp_wrist_fit<0>(C, H, nan, hook);
+            fit_nan = nan;
             tp = load_tips(H);
         }
         TS(1);
@@ -1001,9 +884,8 @@ RTG_DEV void fbp_latency5_tile(const SolverConsts &C, const float *__restrict__ 
             const Q R10{t.x, t.y, t.z, t.w}, chain{c.x, c.y, c.z, c.w};
             float *brow = body_rot ? body_rot + f * 236 : nullptr;
             fbp_gripper<PRECISE>(C, a, E.row + (side ? 27 : 18));
-            const Q loc = qnormalize_t(qmul(qconj(qnormalize_t(qmul(R10, chain), tab)), W), tab);
-            euler_refused = kShared ? emit_euler_xyz_rt(E, side ? 25 : 16, loc)
-                                    : side ? emit_euler_xyz<25>(E, loc) : emit_euler_xyz<16>(E, loc);
+            const Q loc = qnormalize(qmul(qconj(qnormalize(qmul(R10, chain))), W));
+            euler_refused = side ? emit_euler_xyz<25>(E, loc) : emit_euler_xyz<16>(E, loc);
             if (brow) {
                 if (side) fbp_body_rows<1>(brow, R10, W);
                 else fbp_body_rows<0>(brow, R10, W);
@@ -1110,20 +992,8 @@ RTG_DEV void arm_pair_lanes(V v1, ArmZero z0, Q parent, Q &first, Q &second, con
     first = gbc<G, 0>(q);
     second = gbc<G, 1>(q);
 }
-template <int L0, int G = 64, typename Hook = NoHook, typename Tab = NoTab>
-RTG_DEV Q solve_arm_lanes(const Emit &E, V upper, V fore, ArmZero zs, ArmZero ze, Q parent, const Hook &hook = Hook{},
-                          Tab tab = Tab{})
-{
-    const bool w0 = sublane<G>() == 0;
-    Q p, r, y, e;
-    arm_pair_lanes<true, G>(upper, zs, parent, p, r, [&](int k) { hook(k); }, tab);
-    if (w0) { E.link<L0>(p); E.link<L0 + 1>(r); }
-    arm_pair_lanes<false, G>(fore, ze, qmul(qmul(parent, p), r), y, e, [&](int k) { hook(4 + k); }, tab);
-    if (w0) { E.link<L0 + 2>(y); E.link<L0 + 3>(e); }
-    return qmul(qmul(qmul(p, r), y), e);
-}
-// solve_arm_lanes with a run-time first link (both arm waves of the B = 1 kernel run one copy; link_rt writes what
-// Emit::link writes when the wave has no early table words, as there)
+// solve_arm on arm_pair_lanes, with a run-time first link: the two arm waves of a block run one copy of the code
+// (link_rt writes what Emit::link writes when the wave has no early table words, as there)
 template <int G = 64, typename Hook = NoHook, typename Tab = NoTab>
 RTG_DEV Q solve_arm_lanes_rt(const Emit &E, int L0, V upper, V fore, ArmZero zs, ArmZero ze, Q parent,
                              const Hook &hook = Hook{}, Tab tab = Tab{})
@@ -1194,11 +1064,6 @@ RTG_DEV bool emit_euler_xyz_lanes_rt(const Emit &E, int L0, Q qf)
     if (sub < 3) link_rt(E, L0 + sub, elementary_quat(sub, sub == 0 ? ang[0] : (sub == 1 ? ang[1] : ang[2])));
     return refused;
 }
-template <int L0, int G = 64>
-RTG_DEV bool emit_euler_xyz_lanes(const Emit &E, Q qf)
-{
-    return emit_euler_xyz_lanes_rt<G>(E, L0, qf);
-}
 // Emit::finalize with one slot per sub-lane (slots s0 .. s0 + n - 1, n <= G)
 template <int G = 64>
 RTG_DEV void finalize_lanes(const Emit &E, int s0, int n)
@@ -1258,9 +1123,9 @@ RTG_DEV uint32_t fbp_frame1_tile(const SolverConsts &C, const float *rows, float
     const Emit E{sdof, local_rot, C.ang_tab, sst, 1};
     const FV<false> b{rows};
     uint32_t st = 0;
-#if RTG_FRAME1_SHARED_CODE >= 3
     // the three fits (torso on wave 0, the wrists on waves 1 / 2) form their A per wave and then run ONE inlined copy of
-    // the SVD's code (the same operations on the same A as cal_joint_quat)
+    // the SVD's code (the same operations on the same A as cal_joint_quat); the two waves of each side pair run one copy
+    // of theirs, the side a run-time value (120 -> 60 KB of code, profiles/r06/shared_code/)
     Q fitq = qident();
     bool fit_nan = false;
     if (w < 3 && w0) {
@@ -1281,18 +1146,10 @@ RTG_DEV uint32_t fbp_frame1_tile(const SolverConsts &C, const float *rows, float
         }
         fitq = joint_quat_of_A(A, hook, tabF);
     }
-#endif
     if (w == 0) {
         if (w0) {
-#if RTG_FRAME1_SHARED_CODE >= 3
-            const Q q = fitq;
-            const bool nan = fit_nan;
-#else
-            bool nan = false;
-            const Q q = fbp_torso(C, b, nan, hook, tabF);
-#endif
-            sfit = make_float4(q.x, q.y, q.z, q.w);
-            st = nan ? kStTorsoSvd : 0u;
+            sfit = make_float4(fitq.x, fitq.y, fitq.z, fitq.w);
+            st = fit_nan ? kStTorsoSvd : 0u;
         }
         lds_signal(&sflag[0]);
         TS(5);
@@ -1310,13 +1167,8 @@ RTG_DEV uint32_t fbp_frame1_tile(const SolverConsts &C, const float *rows, float
             if (k < 4) TS(8 + k);
             else if (k == 7) TS(12);
         };
-#if RTG_FRAME1_SHARED_CODE
         const Q ch = solve_arm_lanes_rt(E, side ? 21 : 12, up, fo, side ? C.rsh : C.lsh, side ? C.rel : C.lel, R10, ahook,
                                         tab);
-#else
-        const Q ch = side ? solve_arm_lanes<21>(E, up, fo, C.rsh, C.rel, R10, ahook, tab)
-                          : solve_arm_lanes<12>(E, up, fo, C.lsh, C.lel, R10, ahook, tab);
-#endif
         if (w0) schain[side] = make_float4(ch.x, ch.y, ch.z, ch.w);
         lds_signal(&sflag[1 + side]);
         TS(7);
@@ -1328,16 +1180,8 @@ RTG_DEV uint32_t fbp_frame1_tile(const SolverConsts &C, const float *rows, float
         Q W = qident();
         float a = 0.0f;
         if (w0) {
-            bool nan = false;
-#if RTG_FRAME1_SHARED_CODE >= 3
             W = fitq;
-            nan = fit_nan;
-#elif RTG_FRAME1_SHARED_CODE
-            W = fbp_wrist_fit_rt(C, H, side, nan, hook, tabF);
-#else
-            W = side ? fbp_wrist_fit<1>(C, H, nan, hook, tabF) : fbp_wrist_fit<0>(C, H, nan, hook, tabF);
-#endif
-            st = nan ? (side ? kStRightSvd : kStLeftSvd) : 0u;
+            st = fit_nan ? (side ? kStRightSvd : kStLeftSvd) : 0u;
             const TipPts tp = load_tips(H);
             a = hand_x_mean(qconj(W), tp.h0, tp.t);   // the gripper needs only W (:142-158 / :165-175)
         }
@@ -1355,11 +1199,7 @@ RTG_DEV uint32_t fbp_frame1_tile(const SolverConsts &C, const float *rows, float
             }
         }
         const Q loc = qnormalize_t(qmul(qconj(qnormalize_t(qmul(R10, chain), tab)), W), tab);
-#if RTG_FRAME1_SHARED_CODE
         const bool refused = emit_euler_xyz_lanes_rt(E, side ? 25 : 16, loc);
-#else
-        const bool refused = side ? emit_euler_xyz_lanes<25>(E, loc) : emit_euler_xyz_lanes<16>(E, loc);
-#endif
         st |= refused ? (side ? kStRightEuler : kStLeftEuler) : 0u;
         TS(7);
         finalize_lanes(E, side ? 11 : 4, 3);
@@ -1425,9 +1265,6 @@ __global__ __launch_bounds__(320) void k_fbp_quad(SolverConsts C, const float *_
     __shared__ float2 sst[kQuadFrames * 14];
     __shared__ int sflag[3];                     // R10 ready, left arm ready, right arm ready
     __shared__ uint8_t sstat[3][kQuadFrames];    // status bits of the torso wave and the two wrist waves
-    __shared__ UnitEnt sut[2 * kUnitTabK + 1];   // the near-unit normalisation table (RTG_LAT_UNIT_TAB)
-    const auto tabF = TabSel<(RTG_LAT_UNIT_TAB & 1) != 0>::get(sut);
-    const auto tab = TabSel<(RTG_LAT_UNIT_TAB & 6) != 0>::get(sut);
     const int64_t f0 = (int64_t)blockIdx.x * kQuadFrames;
     const int nf = (int)((B - f0) < kQuadFrames ? (B - f0) : kQuadFrames);
     // the tile's rows into LDS, all loads in flight together; a frame slot past B repeats the last frame (every lane
@@ -1446,7 +1283,6 @@ __global__ __launch_bounds__(320) void k_fbp_quad(SolverConsts C, const float *_
         }
     }
     if (threadIdx.x < 3) sflag[threadIdx.x] = 0;
-    if (RTG_LAT_UNIT_TAB) unit_tab_fill(sut, (int)threadIdx.x - 256);   // wave 4, while the rows are in flight
     __syncthreads();
     // with 8 frames per block a wave's upper 8 quads repeat the lower 8 (same rows, same values, never stored)
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, qq = lane >> 2, q = qq & (kQuadFrames - 1), sub = lane & 3;
@@ -1455,8 +1291,10 @@ __global__ __launch_bounds__(320) void k_fbp_quad(SolverConsts C, const float *_
     const Emit E{sdof + q * kDofStride, live && local_rot ? local_rot + f * 124 : nullptr, C.ang_tab, sst + q * 14, 1};
     const FV<false> b{rows + q * RP};
     uint32_t st = 0;
-#if RTG_QUAD_SHARED_CODE >= 3
-    // the three fits share one inlined copy of the SVD's code (k_fbp_frame1's level 3)
+    // the three fits share one inlined copy of the SVD's code, the waves of each side pair one copy of theirs, as in
+    // fbp_frame1_tile: this is that function's program line for line, on a lane quad per frame.  Change both together.
+    // One function for both measured this kernel 2-4 % slower: through a function's reference the compiler loads the
+    // solver constants another way than from the kernel argument ("Less code for the small-batch kernels")
     Q fitq = qident();
     bool fit_nan = false;
     if (w < 3 && sub == 0) {
@@ -1475,20 +1313,12 @@ __global__ __launch_bounds__(320) void k_fbp_quad(SolverConsts C, const float *_
             for (int k = 0; k < 5; ++k) Z[k] = w == 2 ? C.Zr[k] : C.Zl[k];
             fit_nan = form_joint_A<5>(Z, M, A);
         }
-        fitq = joint_quat_of_A(A, NoHook{}, tabF);
+        fitq = joint_quat_of_A(A);
     }
-#endif
     if (w == 0) {
         if (sub == 0) {
-#if RTG_QUAD_SHARED_CODE >= 3
-            const bool nan = fit_nan;
-            const Q t = fitq;
-#else
-            bool nan = false;
-            const Q t = fbp_torso(C, b, nan, NoHook{}, tabF);
-#endif
-            sfit[q] = make_float4(t.x, t.y, t.z, t.w);
-            st = nan ? kStTorsoSvd : 0u;
+            sfit[q] = make_float4(fitq.x, fitq.y, fitq.z, fitq.w);
+            st = fit_nan ? kStTorsoSvd : 0u;
         }
         lds_signal(&sflag[0]);
         if (sub == 0) emit_fixed_links(E);
@@ -1499,13 +1329,7 @@ __global__ __launch_bounds__(320) void k_fbp_quad(SolverConsts C, const float *_
         const float4 t = sfit[q];
         const Q R10{t.x, t.y, t.z, t.w};
         const V up = vsub(ap.el, ap.sh), fo = vsub(ap.wr, ap.el);
-#if RTG_QUAD_SHARED_CODE
-        const Q ch = solve_arm_lanes_rt<4>(E, side ? 21 : 12, up, fo, side ? C.rsh : C.lsh, side ? C.rel : C.lel, R10,
-                                           NoHook{}, tab);
-#else
-        const Q ch = side ? solve_arm_lanes<21, 4>(E, up, fo, C.rsh, C.rel, R10, NoHook{}, tab)
-                          : solve_arm_lanes<12, 4>(E, up, fo, C.lsh, C.lel, R10, NoHook{}, tab);
-#endif
+        const Q ch = solve_arm_lanes_rt<4>(E, side ? 21 : 12, up, fo, side ? C.rsh : C.lsh, side ? C.rel : C.lel, R10);
         if (sub == 0) schain[side][q] = make_float4(ch.x, ch.y, ch.z, ch.w);
         lds_signal(&sflag[1 + side]);
         finalize_lanes<4>(E, side ? 7 : 0, 4);
@@ -1515,16 +1339,8 @@ __global__ __launch_bounds__(320) void k_fbp_quad(SolverConsts C, const float *_
         Q W = qident();
         float a = 0.0f;
         if (sub == 0) {
-            bool nan = false;
-#if RTG_QUAD_SHARED_CODE >= 3
             W = fitq;
-            nan = fit_nan;
-#elif RTG_QUAD_SHARED_CODE
-            W = fbp_wrist_fit_rt(C, H, side, nan, NoHook{}, tabF);
-#else
-            W = side ? fbp_wrist_fit<1>(C, H, nan, NoHook{}, tabF) : fbp_wrist_fit<0>(C, H, nan, NoHook{}, tabF);
-#endif
-            st = nan ? (side ? kStRightSvd : kStLeftSvd) : 0u;
+            st = fit_nan ? (side ? kStRightSvd : kStLeftSvd) : 0u;
             const TipPts tp = load_tips(H);
             a = hand_x_mean(qconj(W), tp.h0, tp.t);   // the gripper needs only W (:142-158 / :165-175)
         }
@@ -1540,12 +1356,8 @@ __global__ __launch_bounds__(320) void k_fbp_quad(SolverConsts C, const float *_
                 else fbp_body_rows<0>(brow, R10, W);
             }
         }
-        const Q loc = qnormalize_t(qmul(qconj(qnormalize_t(qmul(R10, chain), tab)), W), tab);
-#if RTG_QUAD_SHARED_CODE
+        const Q loc = qnormalize(qmul(qconj(qnormalize(qmul(R10, chain))), W));
         const bool refused = emit_euler_xyz_lanes_rt<4>(E, side ? 25 : 16, loc);
-#else
-        const bool refused = side ? emit_euler_xyz_lanes<25, 4>(E, loc) : emit_euler_xyz_lanes<16, 4>(E, loc);
-#endif
         st |= refused ? (side ? kStRightEuler : kStLeftEuler) : 0u;
         finalize_lanes<4>(E, side ? 11 : 4, 3);
     }
