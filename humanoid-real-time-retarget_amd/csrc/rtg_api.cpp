@@ -50,6 +50,12 @@ struct rtg_retarget_plan_s {
     float *d_blob = nullptr;
 };
 
+// The zero-pose transform of mocap rotations: the view and the device blob it points into.
+struct rtg_rot_ingest_s {
+    RotIngestView view{};
+    float *d_blob = nullptr;
+};
+
 struct rtg_solver_s {
     int kind = 0;
     int precise = 0;
@@ -553,6 +559,66 @@ int rtg_ingest_vtrdyn_f32(const float *bp, const float *lhp, const float *rhp, i
     if (!bp || !lhp || !rhp || !body || !lh || !rh || !valid)
         return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_ingest_vtrdyn_f32: NULL buffer");
     RTG_TRY(launch_ingest_vtrdyn(bp, lhp, rhp, B, layout, body, lh, rh, valid, as_stream(stream)), "k_ingest_vtrdyn");
+    return RTG_OK;
+}
+
+// ---------------------------------------------------------------- rotation ingest (the zero-pose transforms)
+int rtg_rot_ingest_create(int32_t J_in, int32_t J_out, const int32_t *src, const float *pre, const float *post,
+                          rtg_rot_ingest_t *out)
+{
+    const char *fn = "rtg_rot_ingest_create";
+    if (!out) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: out is NULL", fn);
+    *out = nullptr;
+    if (J_in < 1 || J_in > kRotIngMaxJ || J_out < 1 || J_out > kRotIngMaxJ)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: J_in %d / J_out %d outside 1..%d", fn, J_in, J_out, kRotIngMaxJ);
+    if (!pre || !post) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL pre / post", fn);
+    if (!src && J_in != J_out)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: src is NULL (the identity) but J_in %d != J_out %d", fn, J_in, J_out);
+    for (int j = 0; src && j < J_out; ++j)
+        if (src[j] < 0 || src[j] >= J_in)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: src[%d] = %d outside 0..%d", fn, j, src[j], J_in - 1);
+    rtg_rot_ingest_s *h = new (std::nothrow) rtg_rot_ingest_s();
+    if (!h) return fail(RTG_ERR_OUT_OF_MEMORY, "%s: host allocation failed", fn);
+    std::vector<float> blob;
+    rot_ingest_blob(J_in, J_out, src, pre, post, blob, h->view);
+    int rc = hip_check(hipMalloc(&h->d_blob, sizeof(float) * blob.size()), "hipMalloc(rot ingest blob)");
+    if (rc == RTG_OK)
+        rc = hip_check(hipMemcpy(h->d_blob, blob.data(), sizeof(float) * blob.size(), hipMemcpyHostToDevice), "hipMemcpy");
+    if (rc == RTG_OK) rc = hip_check(launch_rot_ingest_tab(h->d_blob + 4 * h->view.o_tab, nullptr), "k_rot_ingest_tab");
+    if (rc == RTG_OK) rc = hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+    if (rc != RTG_OK) {
+        (void)hipFree(h->d_blob);
+        delete h;
+        return rc;
+    }
+    h->view.blob = h->d_blob;
+    *out = h;
+    return RTG_OK;
+}
+
+void rtg_rot_ingest_destroy(rtg_rot_ingest_t h)
+{
+    if (!h) return;
+    (void)hipFree(h->d_blob);
+    delete h;
+}
+
+int rtg_rot_ingest_f32(rtg_rot_ingest_t h, const float *q, int64_t B, int layout, float *out, rtg_stream_t stream)
+{
+    const char *fn = "rtg_rot_ingest_f32";
+    // what does not depend on the handle first: a caller (and a test on a machine without a GPU) sees these reasons
+    // whatever the handle is
+    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B < 0", fn);
+    if (layout != RTG_LAYOUT_AOS && layout != RTG_LAYOUT_SOA)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: bad layout %d", fn, layout);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(q), b = reinterpret_cast<uintptr_t>(out);
+    if (B > 0 && (!q || !out)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    if (B > 0 && ((a | b) & 15)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: q / out not 16-byte aligned", fn);
+    if (!h) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL handle", fn);
+    if (B == 0) return RTG_OK;
+    const uint64_t na = (uint64_t)B * h->view.J_in * 16, nb = (uint64_t)B * h->view.J_out * 16;
+    if (a < b + nb && b < a + na) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: q and out overlap", fn);
+    RTG_TRY(launch_rot_ingest(h->view, q, B, layout, out, as_stream(stream)), "k_rot_ingest");
     return RTG_OK;
 }
 

@@ -126,6 +126,22 @@ void retarget_blob(const RetargetTables &T, const int32_t *src_parents, const Q 
 // (4 K + 3 floats) of frame 0 there (the t-pose pass of plan creation)
 hipError_t launch_retarget_to(const RetargetView &P, bool local_in, const float *rot, const float *root_t, int64_t B,
                               float *out_rot, float *out_root_t, float *dump, hipStream_t s);
+// The zero-pose transform out[f, j] = qmul_norm(qmul_norm(q[f, src[j]], pre), post[j]) as one launch,
+// rtg_rot_ingest.hip.  The handle's device blob, in 16-byte units: pre | post (J_out) | src (J_out int32, padded) | the
+// near-unit table (2 kUnitTabK + 1 entries, written on the device by launch_rot_ingest_tab).
+constexpr int kRotIngAosTile = RTG_ROT_INGEST_TILE_AOS, kRotIngSoaTile = RTG_ROT_INGEST_TILE_SOA;   // frames per block
+constexpr int kRotIngMaxJ = 64;
+struct RotIngestView {
+    const float *blob;         // device
+    int32_t J_in, J_out;
+    int32_t n16;               // the blob's size
+    int32_t o_src, o_tab;      // offsets of its parts (post is at 1)
+};
+// host image of the blob (the table zeroed) and the view's layout fields; src == nullptr: the identity
+void rot_ingest_blob(int32_t J_in, int32_t J_out, const int32_t *src, const float *pre, const float *post,
+                     std::vector<float> &blob, RotIngestView &view);
+hipError_t launch_rot_ingest_tab(float *blob_tab, hipStream_t s);
+hipError_t launch_rot_ingest(const RotIngestView &P, const float *q, int64_t B, int layout, float *out, hipStream_t s);
 hipError_t launch_rescale_motion(const TopoView &T, const float *motion, int64_t B, const float *dir, float *out,
                                  hipStream_t s);
 hipError_t launch_quat_between(const float *v1, const float *v2, int64_t n, float *out, float *ws, hipStream_t s);

@@ -133,8 +133,16 @@
 #ifndef RTG_VEL_ANG_NB
 #define RTG_VEL_ANG_NB 2   // angular velocity tile: raw elements per thread per load batch (1-4 measured alike, ~110 us)
 #endif
+#ifndef RTG_ROT_INGEST_TILE_AOS
+#define RTG_ROT_INGEST_TILE_AOS 16   // k_rot_ingest (rtg_rot_ingest.hip): frames per block of 16 T threads, AoS out; a
+                                     // multiple of 4 in 8 .. 64 (8 / 16 / 32 measured alike)
+#endif
+#ifndef RTG_ROT_INGEST_TILE_SOA
+#define RTG_ROT_INGEST_TILE_SOA 16   // the same, SoA out (16 / 32 / 64: 76 / 79 / 103 us for 23 -> 21); rtg/ingest.py
+                                     // ROT_TILE_AOS / ROT_TILE_SOA repeat the two
+#endif
 #ifndef RTG_EXP_NO_RARE
-#define RTG_EXP_NO_RARE 0   // measurement knob, a bit mask: the rare-case branches of cr_sqrt (1) / cr_acos (2) /
+#define RTG_EXP_NO_RARE 0  // measurement knob, a bit mask: the rare-case branches of cr_sqrt (1) / cr_acos (2) /
 #endif                      // cr_sincos (4) / mulr (8) / sqrt_clamp_rcp (16) removed (wrong answers on rare inputs)
 #ifndef RTG_EXP_STUB_SVD
 #define RTG_EXP_STUB_SVD 0   // measurement knob (tools/build_variants.sh): R = identity-ish, wrong answers

@@ -14,7 +14,7 @@ PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("RTG_LIB", os.path.join(PKG_ROOT, "librtg_hip.so"))
 
 RTG_OK = 0
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # rtg_layout (input frame-batch layout of the solvers / producers)
 LAYOUT_AOS = 0
@@ -122,6 +122,10 @@ SIGNATURES = {
     "rtg_retarget_to_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "rtg_retarget_plan_tables": (c_int, [POINTER(c_int32), c_int32, POINTER(c_int32), c_int32, POINTER(c_int32),
                                          POINTER(c_int32), c_int32] + [POINTER(c_int32)] * 6),
+    "rtg_rot_ingest_create": (c_int, [c_int32, c_int32, POINTER(c_int32), POINTER(c_float), POINTER(c_float),
+                                      POINTER(c_void_p)]),
+    "rtg_rot_ingest_destroy": (None, [c_void_p]),
+    "rtg_rot_ingest_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "rtg_solver_create": (c_int, [c_int, POINTER(c_float), POINTER(c_float), POINTER(c_int32), c_int32, c_int,
                                   POINTER(c_void_p)]),
     "rtg_solver_destroy": (c_int, [c_void_p]),

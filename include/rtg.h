@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define RTG_ABI_VERSION 6   /* 6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
+#define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*);
+                               6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
                                5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
                                4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
                                   reserved), the inbox may be device memory (rtg_server_inbox_alloc), rtg_frame_server_signal;
@@ -207,6 +208,28 @@ int rtg_retarget_plan_tables(const int32_t *src_parents, int32_t J_s, const int3
  * layout: of the outputs body / lh / rh (the raw inputs are the reference's rows). */
 int rtg_ingest_vtrdyn_f32(const float *body_pos, const float *left_hand, const float *right_hand, int64_t B,
                           int layout, float *body, float *lh, float *rh, uint8_t *valid, rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Rotation ingest: the zero-pose transforms every caller puts recorded quaternions through before a rotation solver
+ * (retarget/utils/parse_mocap.py:65-134, zero_pose_transform.py:16-41), as ONE launch:
+ *     out[f, j] = quat_mul_norm(quat_mul_norm(q[f, src[j]], pre), post[j])
+ * pre (4) is the one axis rotation, post (J_out,4) = quat_inverse(t2zero[j]); src (J_out) picks the input row of
+ * output joint j (the broadcast's 23 -> 21 rows; NULL = the identity, which needs J_in == J_out).  The two products
+ * are the reference's, in its order, each normalised: bit for bit RTG_OP_QUAT_MUL_NORM applied twice, for any input
+ * (non-unit, zero, NaN, inf, -0 included).  1 <= J_in, J_out <= 64.  src, pre, post are host pointers, copied once
+ * into the handle's device blob on the current device (synchronously); use the handle on that device only.
+ * ---------------------------------------------------------------------- */
+typedef struct rtg_rot_ingest_s *rtg_rot_ingest_t;
+int rtg_rot_ingest_create(int32_t J_in, int32_t J_out, const int32_t *src, const float *pre, const float *post,
+                          rtg_rot_ingest_t *out);
+void rtg_rot_ingest_destroy(rtg_rot_ingest_t h);
+/* q (B,J_in,4) rows -> out in `layout`: (B,J_out,4) rows (RTG_LAYOUT_AOS) or component planes (J_out,4,B)
+ * (RTG_LAYOUT_SOA), what rtg_retarget_f32 reads as FULL_BODY_ROT's in0 / BODY_ROT's in0.  q and out are 16-byte
+ * aligned and must not overlap.  Never allocates or synchronises; B == 0 is a no-op (after the layout check).
+ * RTG_ERR_INVALID_ARGUMENT -- a NULL handle or buffer, B < 0, a bad layout, a misaligned or overlapping buffer; for
+ * rtg_rot_ingest_create a J outside 1..64, src[j] outside 0..J_in-1, src == NULL with J_in != J_out, a NULL pre /
+ * post / out -- is decided before any HIP call, with the reason in rtg_last_error(). */
+int rtg_rot_ingest_f32(rtg_rot_ingest_t h, const float *q, int64_t B, int layout, float *out, rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Motion-level prep of the legacy motion path (retarget/main.py)

@@ -8,6 +8,10 @@
   retarget_to -- the fused SkeletonState.retarget_to launch (C ABI, preallocated outputs, B=262144, local input;
               vtrdyn -> hu_v5 and vtrdyn_full -> hu) against the same result composed from the existing ops
               (state FK, gathers, normalisations, state inverse FK, quat_mul_norm ...), interleaved rounds
+  rot_ingest -- the fused zero-pose transform (rtg_rot_ingest_f32, C ABI, preallocated outputs, B=262144; the 23 -> 21
+              broadcast form and the 59 -> 59 form, both layouts) against the composed path (index_select, two
+              quat_mul_norm ops on constants expanded to (B J, 4), a transposing copy for the planes), interleaved
+              rounds, the results compared bit for bit; k_ingest_vtrdyn's time in the same session alongside
 """
 from __future__ import annotations
 
@@ -375,6 +379,69 @@ def retarget_to(B=262144, rounds=4):
         res[tag] = {"B": B, "J_s": Js, "J_t": Jt, "K": K, "bytes_per_frame": nbytes, "fused_us": f_us,
                     "composed_us": c_us, "fused_TBs": [B * nbytes / (u * 1e-6) / 1e12 for u in f_us],
                     "composed_equals_fused_bits": same, "every_fused_faster": max(f_us) < min(c_us)}
+    return res
+
+
+def rot_ingest(B=262144, rounds=4):
+    from rtg import ingest
+    from rtg.runtime import ptr, stream_handle
+    lib = _lib.lib()
+    res = {}
+    gen = torch.Generator(device="cuda").manual_seed(11)
+    for name in ("vtrdyn_broadcast", "vtrdyn_full"):
+        tr = getattr(ingest.ZeroPoseTransform, name)()
+        Ji, Jo = tr.J_in, tr.J_out
+        q = torch.nn.functional.normalize(torch.randn((B, Ji, 4), device="cuda", generator=gen), dim=-1)
+        h = tr._handle(q.device)
+        idx = torch.as_tensor(tr.src.astype(np.int64), device="cuda")
+        gather = Ji != Jo or not np.array_equal(tr.src, np.arange(Ji))
+        pre_x = torch.as_tensor(tr.pre, device="cuda").expand(B * Jo, 4).contiguous()     # the materialised constants
+        post_x = torch.as_tensor(tr.post, device="cuda").expand(B, Jo, 4).reshape(B * Jo, 4).contiguous()
+        g = torch.empty((B, Jo, 4), device="cuda")
+        m = torch.empty((B * Jo, 4), device="cuda")
+        c_aos = torch.empty((B, Jo, 4), device="cuda")
+        c_soa = torch.empty((Jo, 4, B), device="cuda")
+        nbytes = (Ji + Jo) * 16
+        for layout, code in (("aos", _lib.LAYOUT_AOS), ("soa", _lib.LAYOUT_SOA)):
+            out = torch.empty((Jo, 4, B) if layout == "soa" else (B, Jo, 4), device="cuda")
+
+            def fused():
+                _lib.check(lib.rtg_rot_ingest_f32(h, ptr(q), B, code, ptr(out), stream_handle()))
+
+            def composed():
+                rows = q
+                if gather:
+                    torch.index_select(q, 1, idx, out=g)
+                    rows = g
+                _lib.check(lib.rtg_quat_op_f32(_lib.OP_QUAT_MUL_NORM, ptr(rows), ptr(pre_x), None, B * Jo, ptr(m),
+                                               stream_handle()))
+                _lib.check(lib.rtg_quat_op_f32(_lib.OP_QUAT_MUL_NORM, ptr(m), ptr(post_x), None, B * Jo, ptr(c_aos),
+                                               stream_handle()))
+                if layout == "soa":
+                    c_soa.copy_(c_aos.permute(1, 2, 0))
+
+            fused()
+            composed()
+            torch.cuda.synchronize()
+            same = bool(torch.equal((c_soa if layout == "soa" else c_aos).view(torch.int32), out.view(torch.int32)))
+            f_us, c_us = [], []
+            for _ in range(rounds):   # interleaved: both see the same box state
+                f_us.append(time_events(fused, reps=30, warm=3) * 1e3)
+                c_us.append(time_events(composed, reps=10, warm=2) * 1e3)
+            res[f"{name}_{layout}"] = {"B": B, "J_in": Ji, "J_out": Jo, "bytes_per_frame": nbytes, "fused_us": f_us,
+                                       "composed_us": c_us,
+                                       "fused_TBs": [B * nbytes / (u * 1e-6) / 1e12 for u in f_us],
+                                       "composed_equals_fused_bits": same,
+                                       "every_fused_faster": max(f_us) < min(c_us)}
+    g3 = torch.Generator().manual_seed(5)
+    b23, l20, r20 = (torch.randn(B, n, 3, generator=g3).cuda() for n in (23, 20, 20))
+    nb = (23 + 20 + 20) * 12 + (21 + 20 + 20) * 12 + 1
+    for layout in ("aos", "soa"):
+        us = [time_events(lambda: ingest.reindex_frames(b23, l20, r20, layout=layout), reps=30, warm=3) * 1e3
+              for _ in range(rounds)]
+        res[f"k_ingest_vtrdyn_{layout}"] = {"B": B, "bytes_per_frame": nb, "us": us,
+                                            "TBs": [B * nb / (u * 1e-6) / 1e12 for u in us]}
+    res["tiles"] = {k: _lib.build_info()["knobs"][k] for k in ("RTG_ROT_INGEST_TILE_AOS", "RTG_ROT_INGEST_TILE_SOA")}
     return res
 
 
