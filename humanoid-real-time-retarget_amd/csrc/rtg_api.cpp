@@ -413,6 +413,49 @@ int rtg_fk_backward_f32(rtg_topology_t t, const float *local_rot, const float *g
     return RTG_OK;
 }
 
+// ---------------------------------------------------------------- keypoint fit of the joint-angle model
+int rtg_dof_fit_f32(rtg_dof_model_t m, const float *target_pos, const float *weight, const float *root_rot,
+                    const float *root_t, const float *dof_in, int64_t B, int clip, int32_t iters, float lr, float beta1,
+                    float beta2, float eps, int32_t step0, float *mom1, float *mom2, float *dof_out, float *loss,
+                    float *grad, rtg_stream_t stream)
+{
+    const char *fn = "rtg_dof_fit_f32";
+    // everything that needs no handle first
+    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)B);
+    if (iters < 0 || iters > RTG_DOF_FIT_MAX_ITERS)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: iters=%d is outside 0..%d", fn, iters, RTG_DOF_FIT_MAX_ITERS);
+    if (step0 < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: step0=%d < 0", fn, step0);
+    if (!std::isfinite(lr) || !std::isfinite(eps))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: lr=%g, eps=%g must be finite", fn, (double)lr, (double)eps);
+    if (!std::isfinite(beta1) || !std::isfinite(beta2) || beta1 < 0.0f || beta1 >= 1.0f || beta2 < 0.0f || beta2 >= 1.0f)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: betas (%g, %g) must lie in [0, 1)", fn, (double)beta1, (double)beta2);
+    if ((mom1 == nullptr) != (mom2 == nullptr))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both Adam moment buffers (m, v) or neither", fn);
+    if (B > 0) {   // empty buffers have no address to give
+        if (!dof_out && !loss && !grad) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: every output is NULL", fn);
+        if (!target_pos || !root_rot || !root_t) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    }
+    if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL model", fn);
+    if (clip && !m->has_limits)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: clip_angles requested but the model has no DOF limits", fn);
+    const int J = m->topo->J;
+    if (J > kGroupMaxJ)
+        return fail(RTG_ERR_UNSUPPORTED, "%s: serves models of 1..%d joints (this one has %d)", fn, kGroupMaxJ, J);
+    if (B == 0) return RTG_OK;
+    if (J > 1 && !dof_in) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    if (J == 1) {   // no angles: nothing to step; the kernel's unconditional first-element loads get readable memory
+        dof_in = root_rot;
+        mom1 = mom2 = dof_out = grad = nullptr;
+        iters = 0;
+        if (!loss) return RTG_OK;
+    }
+    const DofView D{m->d_axis, m->d_lower, m->d_upper};
+    const DofFitArgs A{target_pos, weight, root_rot, root_t, dof_in, B, iters, step0, lr, beta1, beta2, eps,
+                       mom1, mom2, dof_out, loss, grad};
+    RTG_TRY(launch_dof_fit(m->topo->view(), D, clip != 0, A, as_stream(stream)), "k_dof_fit");
+    return RTG_OK;
+}
+
 // ---------------------------------------------------------------- SkeletonState.retarget_to
 int rtg_retarget_plan_tables(const int32_t *src_parents, int32_t Js, const int32_t *tgt_parents, int32_t Jt,
                              const int32_t *src_joint, const int32_t *tgt_joint, int32_t K, int32_t *kept_src,

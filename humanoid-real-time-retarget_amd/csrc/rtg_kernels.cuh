@@ -94,6 +94,16 @@ hipError_t launch_dof_fk(const TopoView &T, const DofView &D, bool clip, const f
 hipError_t launch_fk_backward(const TopoView &T, const DofView *D, bool clip, const float *lq_in, const float *g_rot,
                               const float *grad_g_rot, const float *grad_g_pos, int64_t B, float *lq_grad,
                               float *grad_root_rot, float *grad_root_t, hipStream_t s);
+// rtg_dof_fit_f32 (rtg_dof_fit.hip): the keypoint loss of the joint-angle model, its gradient and `iters` Adam steps
+// in one launch; lane groups only (T.gsched).  The pointers are rtg.h's (device memory; optional ones nullptr)
+struct DofFitArgs {
+    const float *target_pos, *weight, *root_rot, *root_t, *dof_in;
+    int64_t B;
+    int32_t iters, step0;
+    float lr, beta1, beta2, eps;
+    float *m, *v, *dof_out, *loss, *grad;
+};
+hipError_t launch_dof_fit(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A, hipStream_t s);
 // SkeletonState.retarget_to (poselib skeleton3d.py:742-889) as one launch, rtg_retarget_to.hip.
 // The host tables of a mapping of K (source joint, target joint) pairs: S_red / T_red are the trees with only the
 // mapped joints kept, each hung from its nearest kept ancestor (drop_nodes_by_names, :226-259).

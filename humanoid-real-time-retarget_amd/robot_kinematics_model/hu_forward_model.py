@@ -49,6 +49,27 @@ class HuForwardModel(BaseForwardModel):
                                                   motion_root_translation, clip=bool(clip_angles))
         return g_rot.to(dev), g_pos.to(dev)
 
+    def fit_keypoints(self, target_positions, motion_root_translation, motion_root_rotation,
+                      motion_joint_angles=None, weight=None, iters=32, lr=0.02, betas=(0.9, 0.999), eps=1e-8,
+                      clip_angles=True, state=None, return_grad=False):
+        """Not in the reference, which only ships the forward model of its optimisation-based converter: the loop that
+        model is for -- a keypoint loss sum_j weight[j] |g_pos[:, j] - target_positions[:, j]|^2 minimised over the
+        joint angles with torch.optim.Adam -- as one launch (ops.dof_fit).  (L, J, 3) targets, (L, 3) root translation,
+        (L, 1, 4) root rotation, (L, J-1, 1) starting angles (default: zeros) -> ((L, J-1, 1) angles, (L,) loss,
+        state[, (L, J-1, 1) gradient]); ``state`` from an earlier call continues its optimiser.  The angles are not
+        projected onto the limits: apply _clip_angles (or a clamp) to the result for the final pose."""
+        if clip_angles and not self._model.has_limits:
+            raise ValueError("clip_angles needs DOF limits with one entry per DOF")
+        dev = home_device(target_positions, motion_root_translation, motion_root_rotation)
+        n = self.num_joints - 1
+        res = ops.dof_fit(self._model, target_positions, motion_root_rotation, motion_root_translation,
+                          dof0=motion_joint_angles, weight=weight, iters=iters, lr=lr, betas=betas, eps=eps,
+                          clip=bool(clip_angles), state=state, return_grad=return_grad)
+        dof, loss, new_state = res[:3]
+        shaped = lambda a: a.reshape(tuple(loss.shape) + (n, 1)).to(dev)
+        out = (shaped(dof), loss.to(dev), new_state)
+        return out + (shaped(res[3]),) if return_grad else out
+
     def _clip_angles(self, motion_joint_angles):
         """:27-33, forward value: (clamp(a, lo, hi) - a) + a, elementwise on the angles' device."""
         a = motion_joint_angles

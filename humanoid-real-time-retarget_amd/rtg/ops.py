@@ -360,6 +360,117 @@ class _DofFK(torch.autograd.Function):
         return None, None, g_d, g_rr, g_rt
 
 
+DOF_FIT_MAX_ITERS = 4096   # rtg.h RTG_DOF_FIT_MAX_ITERS
+
+
+def _as_tensor(x):
+    return x if isinstance(x, torch.Tensor) else torch.as_tensor(x)
+
+
+def _fit_inputs(model, target_pos, root_rot, root_t, dof, weight):
+    """The fit's inputs as contiguous float32 device tensors: target_pos (..., J, 3) sets the batch shape; the angles
+    (..., J-1) [or (..., J-1, 1)], root rotation (..., 4) [or (..., 1, 4)] and translation (..., 3) as in
+    dof_forward_kinematics; weight (J,) or None."""
+    require_gpu_rtg()
+    n = model.num_dofs
+    tp = dev_f32(target_pos, (n + 1, 3), "target_pos")
+    lead = tuple(tp.shape[:-2])
+    if dof is None:
+        d = torch.zeros(lead + (n,), device=tp.device, dtype=torch.float32)
+    else:
+        d = _as_tensor(dof)
+        if d.dim() >= 2 and d.shape[-1] == 1 and d.shape[-2] == n:
+            d = d[..., 0]
+        d = dev_f32(d, (n,), "motion_joint_angles")
+        if tuple(d.shape[:-1]) != lead:
+            raise ValueError(f"motion_joint_angles {tuple(d.shape)} do not match target_pos {tuple(tp.shape)}")
+    rr = _as_tensor(root_rot)
+    if rr.dim() >= 2 and rr.shape[-2] == 1 and rr.shape[-1] == 4:
+        rr = rr[..., 0, :]
+    rr = dev_f32(rr, (4,), "motion_root_rotation").expand(*lead, 4).contiguous()
+    rt = dev_f32(root_t, (3,), "motion_root_translation").expand(*lead, 3).contiguous()
+    w = None
+    if weight is not None:
+        w = dev_f32(weight, (n + 1,), "weight")
+        if w.dim() != 1:
+            raise ValueError(f"weight must be ({n + 1},), got {tuple(w.shape)}")
+    return tp, d, rr, rt, w
+
+
+def _fit_launch(model, clip, tp, w, rr, rt, d, iters=0, lr=0.0, betas=(0.9, 0.999), eps=1e-8, step0=0, m=None, v=None,
+                want_dof=False, want_loss=True, want_grad=False):
+    """rtg_dof_fit_f32 on prepared tensors; m, v are updated in place.  Returns (dof_out, loss, grad), None where not
+    asked for."""
+    lead = tuple(tp.shape[:-2])
+    B = int(torch.Size(lead).numel())
+    out = torch.empty_like(d) if want_dof else None
+    loss = torch.empty(lead, device=d.device, dtype=torch.float32) if want_loss else None
+    grad = torch.empty_like(d) if want_grad else None
+    check(lib().rtg_dof_fit_f32(model.handle, ptr(tp), ptr(w), ptr(rr), ptr(rt), ptr(d), B, int(bool(clip)), int(iters),
+                                float(lr), float(betas[0]), float(betas[1]), float(eps), int(step0), ptr(m), ptr(v),
+                                ptr(out), ptr(loss), ptr(grad), stream_handle()))
+    return out, loss, grad
+
+
+def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: int = 32, lr: float = 0.02,
+            betas=(0.9, 0.999), eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False):
+    """Fit the joint angles of a DofModel to target keypoints: ``iters`` steps of torch.optim.Adam (no weight decay, no
+    amsgrad) on L_f = sum_j weight[j] |P_j(a_f) - target_pos[f, j]|^2, P the positions of dof_forward_kinematics --
+    forward model, loss, gradient and optimiser in ONE launch (rtg_dof_fit_f32).
+
+    target_pos (..., J, 3); root_rot / root_t as in dof_forward_kinematics (given, not fitted); dof0 (..., J-1) [or
+    (..., J-1, 1)] the start, default zeros; weight (J,) or None for all ones.  ``state`` is the optimiser's
+    ``(m, v, step)`` from an earlier call (None: a fresh optimiser); it is returned updated, so calls chain: two calls
+    of n steps give the bits of one call of 2n.  The iterate is not projected onto the limits (``clip`` only clips
+    inside the forward model, straight-through); the final pose is the clamp the caller applies.
+
+    Returns ``(dof, loss, state)`` -- the angles after the last step (dof0's shape), the per-frame loss there (...),
+    and the new state -- plus the gradient there (dof's shape) when ``return_grad``.  ``iters=0`` only evaluates.
+    Raises RtgError without a GPU: there is no CPU fallback."""
+    tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof0, weight)
+    iters = int(iters)
+    if not 0 <= iters <= DOF_FIT_MAX_ITERS:
+        raise ValueError(f"iters must be in 0..{DOF_FIT_MAX_ITERS}, got {iters}")
+    if state is None:
+        m, v, step = torch.zeros_like(d), torch.zeros_like(d), 0
+    else:
+        m, v, step = state
+        m, v = (dev_f32(x, (model.num_dofs,), "state").reshape(d.shape).clone() for x in (m, v))
+        step = int(step)
+    out, loss, grad = _fit_launch(model, clip, tp, w, rr, rt, d.detach(), iters, lr, betas, eps, step, m, v,
+                                  want_dof=True, want_grad=bool(return_grad))
+    if dof0 is not None and tuple(_as_tensor(dof0).shape) == tuple(d.shape) + (1,):
+        out = out.unsqueeze(-1)
+        grad = None if grad is None else grad.unsqueeze(-1)
+    res = (out, loss, (m, v, step + iters))
+    return res + (grad,) if return_grad else res
+
+
+def keypoint_loss(model, dof, target_pos, root_rot, root_t, weight=None, clip: bool = False):
+    """The per-frame keypoint loss L_f = sum_j weight[j] |P_j(dof_f) - target_pos[f, j]|^2 of dof_fit, (...), as the
+    evaluate-only launch of rtg_dof_fit_f32.  Differentiable in ``dof`` (only): the launch computes the gradient
+    along with the loss, and backward scales its rows by the upstream cotangent -- for callers who keep their own
+    optimiser.  Under no_grad, or when dof does not require grad, it is the plain launch without the gradient."""
+    tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof, weight)
+    if torch.is_grad_enabled() and d.requires_grad:
+        return _KeypointLoss.apply(model, bool(clip), d, tp, rr, rt, w)
+    return _fit_launch(model, clip, tp, w, rr, rt, d.detach())[1]
+
+
+class _KeypointLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, clip, d, tp, rr, rt, w):
+        _, loss, grad = _fit_launch(model, clip, tp, w, rr, rt, d, want_grad=True)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        (grad,) = ctx.saved_tensors
+        return None, None, grad * grad_loss.unsqueeze(-1), None, None, None, None
+
+
 def rescale_motion(topo: Topology, motion, dir=None):
     """Retarget.rescale_motion_to_standard_size (retarget/main.py:37-47) after coord_transform(dir) (:170)."""
     J = topo.num_joints

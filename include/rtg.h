@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*);
+#define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*); rtg_dof_fit_f32 came
+                                  later as a new symbol only -- nothing that existed changed, so the version stays 7;
                                6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
                                5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
                                4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
@@ -160,6 +161,36 @@ int rtg_dof_fk_backward_f32(rtg_dof_model_t model, const float *dof, const float
 int rtg_fk_backward_f32(rtg_topology_t topo, const float *local_rot, const float *g_rot, const float *grad_g_rot,
                         const float *grad_g_pos, int64_t B, float *grad_local_rot, float *grad_root_t,
                         rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Fit joint angles to target keypoints: the loop a caller of the differentiable joint-angle model runs (a keypoint
+ * loss minimised over the angles with torch.optim.Adam), as ONE launch.  Per frame f
+ *     L_f = sum_j weight[j] |P_j(a_f) - target_pos[f,j]|^2,
+ * P the g_pos of rtg_dof_fk_f32 on the same model, root and clip (float32 arithmetic with the device sincosf, not the
+ * forward call's bit-exact one; the clip is straight-through, hu_forward_model.py:27-33).  The call takes `iters`
+ * steps of Adam (no weight decay, no amsgrad) on the angles, k = 1..iters, t = step0 + k, g = dL_f/da_f:
+ *     m = beta1 m + (1 - beta1) g,  v = beta2 v + (1 - beta2) g^2,
+ *     a -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).
+ * The iterate is not projected onto the limits (like the torch loop: the final pose is the clamp the caller applies).
+ * iters == 0 is the fused evaluate-only call.
+ *   target_pos (B,J,3); weight (J) or NULL = all 1; root_rot (B,4), root_t (B,3): given, not fitted;
+ *   dof_in (B,J-1) the start; step0: Adam steps already taken; m, v (B,J-1): the moments, read and written in place --
+ *   both NULL = start at 0 and do not write them;
+ *   -> dof_out (B,J-1) (may alias dof_in), loss (B) and grad (B,J-1): the loss and its gradient AT dof_out (one more
+ *   sweep after the last step; with iters == 0 that is at dof_in).  Each output may be NULL, not all three.
+ * A DOF whose subtree carries no weight (a leaf joint's DOF among them: a leaf's rotation moves no position) gets a
+ * gradient of exactly +-0, and from a zero state its angle keeps its bits.  A frame's results depend on that frame's
+ * rows alone: not on the batch, the tile, or another frame's NaN / inf; runs are bit-identical, and one launch of n
+ * steps equals n launches of one step that carry (m, v, step0).
+ * Errors: iters outside 0..4096, step0 < 0, lr / betas / eps not finite, betas outside [0, 1), exactly one of m, v
+ * NULL, clip without limits -> RTG_ERR_INVALID_ARGUMENT; more than 64 joints -> RTG_ERR_UNSUPPORTED.  B == 0 is a
+ * no-op.
+ * ---------------------------------------------------------------------- */
+#define RTG_DOF_FIT_MAX_ITERS 4096   /* bounds one launch's run time */
+int rtg_dof_fit_f32(rtg_dof_model_t model, const float *target_pos, const float *weight, const float *root_rot,
+                    const float *root_t, const float *dof_in, int64_t B, int clip, int32_t iters, float lr, float beta1,
+                    float beta2, float eps, int32_t step0, float *m, float *v, float *dof_out, float *loss, float *grad,
+                    rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * SkeletonState.retarget_to (poselib skeleton3d.py:742-889): the generic skeleton-to-skeleton retarget, rotations

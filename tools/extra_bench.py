@@ -12,6 +12,12 @@
               broadcast form and the 59 -> 59 form, both layouts) against the composed path (index_select, two
               quat_mul_norm ops on constants expanded to (B J, 4), a transposing copy for the planes), interleaved
               rounds, the results compared bit for bit; k_ingest_vtrdyn's time in the same session alongside
+  fit      -- the fused keypoint fit (rtg_dof_fit_f32, C ABI, preallocated outputs, 33-link Hu, B=262144, clip on): the
+              evaluate-only launch (iters = 0), one launch of 32 steps reported per step, and the composed iteration
+              it replaces (ops.dof_forward_kinematics, the torch loss, backward(), torch.optim.Adam(fused=True)),
+              interleaved rounds
+  fit_traffic -- a few launches of each fused form and nothing else, for a counter run of its own (FETCH_SIZE or
+              WRITE_SIZE, one per run) against the algorithmic bytes that `fit` prints
 """
 from __future__ import annotations
 
@@ -443,6 +449,76 @@ def rot_ingest(B=262144, rounds=4):
                                             "TBs": [B * nb / (u * 1e-6) / 1e12 for u in us]}
     res["tiles"] = {k: _lib.build_info()["knobs"][k] for k in ("RTG_ROT_INGEST_TILE_AOS", "RTG_ROT_INGEST_TILE_SOA")}
     return res
+
+
+def _fit_setup(B):
+    from rtg.runtime import DofModel
+    import importlib
+    hu = importlib.import_module("retarget.robot_config.Hu")
+    lo, hi = hu.Hu_DOF_LOWER.numpy().astype(np.float32), hu.Hu_DOF_UPPER.numpy().astype(np.float32)
+    M = DofModel(topo("hu"), hu.Hu_DOF_AXIS, lo, hi)
+    gen = torch.Generator(device="cuda").manual_seed(17)
+    lo_d, hi_d = torch.as_tensor(lo, device="cuda"), torch.as_tensor(hi, device="cuda")
+    rr = torch.nn.functional.normalize(torch.randn((B, 4), device="cuda", generator=gen), dim=-1)
+    rt = torch.randn((B, 3), device="cuda", generator=gen) * 0.3
+    truth = lo_d + (hi_d - lo_d) * torch.rand((B, 32), device="cuda", generator=gen)
+    tgt = ops.dof_forward_kinematics(M, truth, rr, rt, clip=True)[1].contiguous()   # reachable targets
+    start = (0.5 * (lo_d + hi_d)).expand(B, 32).contiguous()
+    return M, tgt, rr, rt, start
+
+
+def _fit_call(M, tgt, rr, rt, start, B, iters, out, loss, grad, m=None, v=None):
+    from rtg.runtime import ptr, stream_handle
+    f, sh = _lib.lib().rtg_dof_fit_f32, stream_handle()
+    args = (M.handle, ptr(tgt), None, ptr(rr), ptr(rt), ptr(start), B, 1, iters, 0.02, 0.9, 0.999, 1e-8, 0, ptr(m),
+            ptr(v), ptr(out), ptr(loss), ptr(grad), sh)
+    _lib.check(f(*args))
+    return lambda: f(*args)
+
+
+def fit(B=262144, rounds=4, iters=32):
+    M, tgt, rr, rt, start = _fit_setup(B)
+    J = 33
+    out, grad = torch.empty((B, 32), device="cuda"), torch.empty((B, 32), device="cuda")
+    loss = torch.empty((B,), device="cuda")
+    m, v = torch.zeros((B, 32), device="cuda"), torch.zeros((B, 32), device="cuda")
+    evaluate = _fit_call(M, tgt, rr, rt, start, B, 0, None, loss, grad)
+    steps = _fit_call(M, tgt, rr, rt, start, B, iters, out, loss, None)            # no state: read and write the least
+    steps_state = _fit_call(M, tgt, rr, rt, start, B, iters, out, loss, None, m, v)
+    # the loop it replaces, one iteration: forward launch, torch loss, backward launch, fused Adam
+    a = start.clone().requires_grad_(True)
+    opt = torch.optim.Adam([a], lr=0.02, fused=True)
+
+    def composed():
+        opt.zero_grad(set_to_none=True)
+        gp = ops.dof_forward_kinematics(M, a, rr, rt, clip=True)[1]
+        (gp - tgt).square().sum().backward()
+        opt.step()
+
+    ev, st, ss, co = [], [], [], []
+    for _ in range(rounds):   # interleaved: all see the same box state
+        ev.append(time_events(evaluate, reps=20, warm=2) * 1e3)
+        st.append(time_events(steps, reps=5, warm=1) * 1e3 / iters)
+        ss.append(time_events(steps_state, reps=5, warm=1) * 1e3 / iters)
+        co.append(time_events(composed, reps=10, warm=2) * 1e3)
+    rd, wr = J * 12 + (J - 1) * 4 + 28, (J - 1) * 4 + 4
+    return {"B": B, "J": J, "iters": iters, "evaluate_us": ev, "fused_us_per_iteration": st,
+            "fused_with_state_us_per_iteration": ss, "composed_us_per_iteration": co,
+            "algorithmic_bytes_per_frame": {"read": rd, "written": wr, "state_rows_each_way": 2 * (J - 1) * 4},
+            "evaluate_algorithmic_bytes_per_frame": {"read": rd, "written": (J - 1) * 4 + 4},
+            "every_fused_faster": max(st) < min(co)}
+
+
+def fit_traffic(B=262144, iters=32):
+    M, tgt, rr, rt, start = _fit_setup(B)
+    out, grad = torch.empty((B, 32), device="cuda"), torch.empty((B, 32), device="cuda")
+    loss = torch.empty((B,), device="cuda")
+    for call in (_fit_call(M, tgt, rr, rt, start, B, 0, None, loss, grad),
+                 _fit_call(M, tgt, rr, rt, start, B, iters, out, loss, None)):
+        for _ in range(3):
+            call()
+    torch.cuda.synchronize()
+    return {"B": B, "launches": "4 x iters=0 (loss, grad out), then 4 x iters=%d (dof, loss out); grids equal" % iters}
 
 
 if __name__ == "__main__":
