@@ -81,6 +81,17 @@
                          // (A/B knob, same values: SoA 93.2-94.5 vs 95.3-96.6 us in one session, medians 94.6 vs 95.0 in a
                          // second; 8 rounds pooled 94.3 vs 95.6 mean; profiles/r07/ab_headline*.log)
 #endif
+#ifndef RTG_FIT_FAST_DIV
+#define RTG_FIT_FAST_DIV 1   // the Kabsch fits' SVD (la_lartg / la_lasv2 / la_las2_min / la_lapy2): quotients by one
+                             // denominator share one reciprocal (fdiv_n: the compiler's IEEE f32 sequence minus its
+                             // scaling, behind a range guard) and square roots of arguments that cannot be tiny skip
+                             // cr_sqrt's 2^64 scaling (cr_sqrt_nt); 0: fdiv and cr_sqrt at every such site (A/B knob,
+                             // same values)
+#endif
+#ifndef RTG_FIT_FAST_DIV_TU
+#define RTG_FIT_FAST_DIV_TU RTG_FIT_FAST_DIV   // the same per translation unit: the Makefile's IEEE_DIV_TUS get 0 (rtg_ops, so
+                                               // rtg_build_info reports 0 here: k_cal_joint_quat would lose a wave)
+#endif
 #ifndef RTG_DOF_NT_STORE
 #define RTG_DOF_NT_STORE 1   // A/B knob (same values): the solvers' DOF rows (whole 128-B lines) as non-temporal stores
                              // (headline 101.3 vs 104.5 us SoA, 114.4 vs 117.7 AoS; profiles/r05/nt/)

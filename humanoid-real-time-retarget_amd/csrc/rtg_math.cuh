@@ -55,6 +55,25 @@ RTG_DEV float cr_sqrt(float x)
     s = rup > 0.0f ? sup : s;
     return tiny ? s * 0x1p-32f : s;
 }
+// cr_sqrt for an argument that is "not tiny": x >= 2^-96, or +-0, +inf or NaN.  For such x cr_sqrt's `tiny` test
+// selects the unscaled value both times (it reads true on +-0 too, but 0 * 2^64 = 0 and 0 * 2^-32 = 0 with the
+// sign kept), so its five scaling instructions (compare, multiply, select; multiply, select) drop out and the rest
+// is the same sequence: the same bits as cr_sqrt.  Only for call sites whose comment says why the argument is in
+// that set; a negative or denormal argument needs cr_sqrt.  tools/check_fdiv.hip checks it against __builtin_sqrtf
+// on every such bit pattern.
+RTG_DEV float cr_sqrt_nt(float x)
+{
+#if RTG_FIT_FAST_DIV_TU
+    float s = __builtin_amdgcn_sqrtf(x);
+    const float sdn = __uint_as_float(__float_as_uint(s) - 1u), sup = __uint_as_float(__float_as_uint(s) + 1u);
+    const float rdn = __builtin_fmaf(-sdn, s, x), rup = __builtin_fmaf(-sup, s, x);
+    s = rdn <= 0.0f ? sdn : s;
+    s = rup > 0.0f ? sup : s;
+    return s;
+#else
+    return cr_sqrt(x);
+#endif
+}
 // Rounding test for an f64 approximation y of a value whose f32 rounding is wanted: true when the bits f32 rounding
 // drops (29 of them, for an f32-normal |y|) are not within D f64 ulps of the midpoint 2^28, i.e. every value within
 // D ulps of y rounds to (float)y.  An approximation with relative error <= 2^-k is within 2^(53-k) ulps.  Integer
@@ -924,7 +943,7 @@ RTG_DEV Q axis_half_quat(int axis, float a)
 // routine follows the published LAPACK algorithm; the FMA placement inside MKL's BLAS kernels was measured stage
 // by stage against MKL's own entry points (tools/mkl_sgesdd_probe.py) and matches bit for bit.  The
 // oracle (oracle/rtg_oracle.c, la_gesdd3) restates the same routines independently.  All divisions / square
-// roots are IEEE-exact (fdiv = the compiler's IEEE f32 division; shared denominators rcp64 + mulr_k; cr_sqrt).  Matrices are column-major: a[r + 3 c].
+// roots are IEEE-exact (fdiv = the compiler's IEEE f32 division; quotients by one denominator fdiv_n; cr_sqrt / cr_sqrt_nt).  Matrices are column-major: a[r + 3 c].
 RTG_DEV float fdiv(float a, float b)
 {
     return a / b;   // the compiler's IEEE f32 division sequence (measured 6 % faster here than rcp64 + mulr)
@@ -933,13 +952,69 @@ RTG_DEV float la_sqrt(float x)
 {
     return cr_sqrt(x);
 }
+RTG_DEV float la_sqrt_nt(float x) { return cr_sqrt_nt(x); }   // the argument cannot be tiny: see cr_sqrt_nt, and say why
+// ---- N IEEE f32 quotients a_i / b by one denominator (round 13).  The compiler's division is, per quotient,
+//   bs = v_div_scale(b), as = v_div_scale(a);  y = v_rcp_f32(bs);  y = fma(fma(-bs, y, 1), y, y);
+//   q = as * y;  q = fma(fma(-bs, q, as), y, q);  q = v_div_fmas(fma(-bs, q, as), y, q);  v_div_fixup(q, b, a)
+// and it rebuilds all of it for every quotient, the reciprocal included, because v_div_scale reads the numerator.
+// Inside the window below nothing is scaled and nothing fixed up, so the sequence is plain f32 arithmetic whose
+// reciprocal part (three VALU, the one transcendental) depends on b alone: fdiv_n computes it once and runs the five
+// quotient instructions per numerator -- the same instructions on the same operands, hence the same bits.
+//
+// The window: |b| and every |a_i| in [2^-47, 2^47] (kDivLo, kDivHi; la_lartg passes its own test, see there).  By
+// the ISA's definition v_div_scale_f32 returns its operand unscaled and VCC = 0 unless one of: an operand is 0 or
+// NaN; exponent(a) - exponent(b) >= 96; b is denormal; 1 / b is denormal (|b| > 2^126); a / b is denormal
+// (exponent(a) - exponent(b) <= -126 or so); exponent(a) <= 23 (|a| < 2^-103).  In the window the exponents differ
+// by at most 94 and each lies in [-47, 47], so none holds; with VCC = 0 v_div_fmas is an FMA.  v_div_fixup changes
+// q only for 0 / inf / NaN operands, an exponent difference below -150 or an infinite q, none of which can occur:
+// |a / b| lies in [2^-94, 2^94].  47 is the widest power of two for which the exponent difference stays under 96;
+// SGESDD's rescaling holds the fitted matrix inside [2^-40, 2^40], so ordinary fits stay well inside.  A zero
+// numerator fails the guard (the bare sequence would turn -0 / b into +0), as do inf and NaN (every comparison
+// reads false).  A lane outside the window sends its whole group through a_i / b behind ONE rare-case branch
+// (N-way, as mulr_k).  tools/check_fdiv.hip (tests/test_gpu_fdiv.py) checks it on the device against a / b.
+constexpr float kDivLo = 0x1p-47f, kDivHi = 0x1p47f;
+RTG_DEV bool fdiv_in_window(float x)
+{
+    const float ax = fabsf(x);
+    return (ax >= kDivLo) & (ax <= kDivHi);
+}
+// the bare sequence: a_i / b only where b and a_i are in the window (the caller tests that and redoes the rest)
+template <int N>
+RTG_DEV void fdiv_n_bare(const float (&a)[N], float b, float (&q)[N])
+{
+    float y = __builtin_amdgcn_rcpf(b);
+    y = __builtin_fmaf(__builtin_fmaf(-b, y, 1.0f), y, y);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        float t = a[i] * y;
+        t = __builtin_fmaf(__builtin_fmaf(-b, t, a[i]), y, t);
+        q[i] = __builtin_fmaf(__builtin_fmaf(-b, t, a[i]), y, t);
+    }
+}
+template <int N>
+RTG_DEV void fdiv_n(const float (&a)[N], float b, float (&q)[N])
+{
+#if RTG_FIT_FAST_DIV_TU
+    bool ok = fdiv_in_window(b);
+#pragma unroll
+    for (int i = 0; i < N; ++i) ok &= fdiv_in_window(a[i]);
+    fdiv_n_bare<N>(a, b, q);
+    if (__builtin_expect(!ok, 0)) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) q[i] = a[i] / b;
+    }
+#else
+#pragma unroll
+    for (int i = 0; i < N; ++i) q[i] = a[i] / b;
+#endif
+}
 RTG_DEV float la_sign(float a, float b) { return __builtin_copysignf(fabsf(a), b); }   // Fortran SIGN
 RTG_DEV float la_lapy2(float x, float y)                                                 // SLAPY2
 {
     const float xa = fabsf(x), ya = fabsf(y);
     const float w = fmaxf(xa, ya), z = fminf(xa, ya);
     const float r = fdiv(z, w);
-    return z == 0.0f ? w : w * la_sqrt(1.0f + r * r);
+    return z == 0.0f ? w : w * la_sqrt_nt(1.0f + r * r);   // 1 + r^2 >= 1 (or NaN): not tiny
 }
 // SLARFG(n, alpha, x): n = 3 (x = x0, x1) or n = 2 (x = x0); returns tau, updates alpha (= beta) and x
 template <int NX>
@@ -976,6 +1051,25 @@ RTG_DEV void la_lartg(float f, float g, float &c, float &s, float &r)   // SLART
     const float f1 = fabsf(f), g1 = fabsf(g);
     // the common case (f, g nonzero and in range) runs unconditionally; the other three cases of SLARTG redo the
     // outputs behind ONE rare-case branch -- the same operations per case as the reference's cascade
+#if RTG_FIT_FAST_DIV_TU
+    // the unconditional form is the bare shared-reciprocal one, valid for |f|, |g| in fdiv_n's window [2^-47, 2^47]:
+    // then f^2 + g^2 lies in [2^-93, 2^95] (not tiny: cr_sqrt_nt; no overflow) and d in [2^-47, 2^47.5], whose
+    // exponent is still at most 47, so the exponents of f1 and g differ from d's by at most 94 and fdiv_n's argument
+    // holds for both quotients (which are <= 1 and >= 2^-95).  The window test takes the place of the four range
+    // comparisons and two zero tests below (it implies them all); a lane outside it takes the rare-case branch,
+    // where SLARTG's common case is redone with fdiv and cr_sqrt.
+    const bool common = (f1 >= kDivLo) & (f1 <= kDivHi) & (g1 >= kDivLo) & (g1 <= kDivHi);
+    {
+        const float d = la_sqrt_nt(f * f + g * g);
+        const float num[2] = {f1, g};
+        float quo[2];
+        fdiv_n_bare<2>(num, d, quo);
+        c = quo[0];
+        r = __builtin_copysignf(d, f);
+        s = f < 0.0f ? -quo[1] : quo[1];   // g / r with r = +-d (RN is sign-symmetric)
+    }
+#else
+    const bool common = (g != 0.0f) & (f != 0.0f) & (f1 > rtmin) & (f1 < rtmax) & (g1 > rtmin) & (g1 < rtmax);
     {
         const float d = la_sqrt(f * f + g * g);
         const float quo[2] = {fdiv(f1, d), fdiv(g, d)};
@@ -983,9 +1077,18 @@ RTG_DEV void la_lartg(float f, float g, float &c, float &s, float &r)   // SLART
         r = __builtin_copysignf(d, f);
         s = f < 0.0f ? -quo[1] : quo[1];   // g / r with r = +-d (RN is sign-symmetric)
     }
-    if (__builtin_expect(!((g != 0.0f) & (f != 0.0f) & (f1 > rtmin) & (f1 < rtmax) & (g1 > rtmin) & (g1 < rtmax)), 0)) {
+#endif
+    if (__builtin_expect(!common, 0)) {
         if (g == 0.0f) { c = 1.0f; s = 0.0f; r = f; }
         else if (f == 0.0f) { c = 0.0f; s = __builtin_copysignf(1.0f, g); r = g1; }
+#if RTG_FIT_FAST_DIV_TU
+        else if ((f1 > rtmin) & (f1 < rtmax) & (g1 > rtmin) & (g1 < rtmax)) {   // the common case outside the window
+            const float d = la_sqrt(f * f + g * g), q = fdiv(g, d);
+            c = fdiv(f1, d);
+            r = __builtin_copysignf(d, f);
+            s = f < 0.0f ? -q : q;
+        }
+#endif
         else {
             const float u = fminf(safmax, fmaxf(safmin, fmaxf(f1, g1)));
             const float fs = fdiv(f, u), gs = fdiv(g, u), d = la_sqrt(fs * fs + gs * gs);
@@ -1002,16 +1105,24 @@ RTG_DEV float la_las2_min(float f, float g, float h)   // SLAS2, SSMIN only (the
     const float fhmn = fminf(fa, ha), fhmx = fmaxf(fa, ha);
     if (fhmn == 0.0f) return 0.0f;
     if (ga < fhmx) {
-        const float as = 1.0f + fdiv(fhmn, fhmx), at = fdiv(fhmx - fhmn, fhmx);
-        float au = fdiv(ga, fhmx);
+        const float num[3] = {fhmn, fhmx - fhmn, ga};
+        float quo[3];
+        fdiv_n<3>(num, fhmx, quo);
+        const float as = 1.0f + quo[0], at = quo[1];
+        float au = quo[2];
         au = au * au;
-        const float c = fdiv(2.0f, la_sqrt(as * as + au) + la_sqrt(at * at + au));
+        // as >= 1 (the quotient is >= 0), so as^2 + au >= 1: not tiny.  at^2 + au can be (at = 0, au tiny): cr_sqrt
+        const float c = fdiv(2.0f, la_sqrt_nt(as * as + au) + la_sqrt(at * at + au));
         return fhmn * c;
     }
     const float au = fdiv(fhmx, ga);
     if (au == 0.0f) return fdiv(fhmn * fhmx, ga);
-    const float as = 1.0f + fdiv(fhmn, fhmx), at = fdiv(fhmx - fhmn, fhmx), p = as * au, q = at * au;
-    const float c = fdiv(1.0f, la_sqrt(1.0f + p * p) + la_sqrt(1.0f + q * q));
+    const float num[2] = {fhmn, fhmx - fhmn};
+    float quo[2];
+    fdiv_n<2>(num, fhmx, quo);
+    const float as = 1.0f + quo[0], at = quo[1], p = as * au, q = at * au;
+    // 1 + p^2 and 1 + q^2 are >= 1 (or NaN): not tiny
+    const float c = fdiv(1.0f, la_sqrt_nt(1.0f + p * p) + la_sqrt_nt(1.0f + q * q));
     const float mn = (fhmn * c) * au;
     return mn + mn;
 }
@@ -1035,10 +1146,42 @@ RTG_DEV void la_lasv2(float f, float g, float h, float &ssmin, float &ssmax, flo
                 gasmal = false;
                 ssmax = ga;
                 ssmin = ha > 1.0f ? fdiv(fa, fdiv(ga, ha)) : fdiv(fa, ga) * ha;
-                clt = 1.0f; slt = fdiv(ht, gt); srt = 1.0f; crt = fdiv(ft, gt);
+                const float num[2] = {ht, ft};
+                float quo[2];
+                fdiv_n<2>(num, gt, quo);
+                clt = 1.0f; slt = quo[0]; srt = 1.0f; crt = quo[1];
             }
         }
         if (gasmal) {
+#if RTG_FIT_FAST_DIV_TU
+            const float d = fa - ha, l = d == fa ? 1.0f : fdiv(d, fa);
+            const float numf[2] = {gt, ht};
+            float quof[2];
+            fdiv_n<2>(numf, ft, quof);   // m = gt / ft, and ht / ft for slt
+            const float m = quof[0], mm = m * m;
+            float t = 2.0f - l;
+            const float tt = t * t;
+            // l = (fa - ha) / fa lies in [0, 1], so t = 2 - l >= 1 and tt + mm >= 1 (or NaN): not tiny.
+            // No such bound is claimed for l^2 + mm: cr_sqrt
+            const float s = la_sqrt_nt(tt + mm);
+            const float r = l == 0.0f ? fabsf(m) : la_sqrt(l * l + mm);
+            const float a = 0.5f * (s + r);
+            ssmax = fa * a;
+            if (mm == 0.0f) t = l == 0.0f ? la_sign(2.0f, ft) * la_sign(1.0f, gt) : fdiv(gt, la_sign(d, ft)) + fdiv(m, t);
+            else t = (fdiv(m, s + t) + fdiv(m, r + l)) * (1.0f + a);
+            const float l2 = la_sqrt_nt(t * t + 4.0f);   // >= 4 (or NaN): not tiny
+            const float numl[2] = {2.0f, t};
+            float quol[2];
+            fdiv_n<2>(numl, l2, quol);
+            crt = quol[0];
+            srt = quol[1];
+            const float numa[3] = {ha, crt + srt * m, quof[1] * srt};
+            float quoa[3];
+            fdiv_n<3>(numa, a, quoa);
+            ssmin = quoa[0];
+            clt = quoa[1];
+            slt = quoa[2];
+#else   // the same operations in the order they had before the groups were formed
             const float d = fa - ha, l = d == fa ? 1.0f : fdiv(d, fa);
             const float m = fdiv(gt, ft), mm = m * m;
             float t = 2.0f - l;
@@ -1055,6 +1198,7 @@ RTG_DEV void la_lasv2(float f, float g, float h, float &ssmin, float &ssmax, flo
             srt = fdiv(t, l2);
             clt = fdiv(crt + srt * m, a);
             slt = fdiv(fdiv(ht, ft) * srt, a);
+#endif
         }
     }
     if (swap) { csl = srt; snl = crt; csr = slt; snr = clt; }

@@ -43,7 +43,12 @@ def classify(insts):
     mov_rr = [i for i in mov if re.match(r"v_mov_b32(_e32)?\s+v\d+,\s*v\d+\s*$", i)]
     return {"valu": len(valu), "packed_f32": len(pk), "v_mov_b32": len(mov), "v_mov_b32_reg_reg": len(mov_rr),
             "v_cndmask": sum(op(i).startswith("v_cndmask") for i in valu),
-            "f64": sum("_f64" in op(i) for i in valu), "s_nop": sum(op(i) == "s_nop" for i in insts),
+            "f64": sum("_f64" in op(i) for i in valu),
+            # one v_div_fixup_f32 per inlined IEEE f32 division (11 VALU each), one v_sqrt_f32 per inlined cr_sqrt /
+            # cr_sqrt_nt (14 / 9 VALU), v_rcp_f32: the divisions' plus one per shared-reciprocal group (fdiv_n)
+            "ieee_div_f32": sum(op(i).startswith("v_div_fixup_f32") for i in valu),
+            "v_rcp_f32": sum(op(i).startswith("v_rcp_f32") for i in valu),
+            "v_sqrt_f32": sum(op(i).startswith("v_sqrt_f32") for i in valu), "s_nop": sum(op(i) == "s_nop" for i in insts),
             "plain": len(valu) - len(pk), "issue_slots": len(valu) + len(pk)}
 
 
