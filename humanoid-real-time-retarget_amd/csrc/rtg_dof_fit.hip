@@ -13,14 +13,7 @@
 // on the spot, so there is no gradient image and no separate update pass.  The root is given, not fitted: its rows
 // are written once and the reverse sweep stops above it.
 //
-// LDS images of a tile (floats; every image starts 16-byte aligned):
-//   G   [F J] float4    forward: global rotations; reverse: a finished joint's contribution to its parent
-//   P   [F J 3]         positions, then in place the residual adjoints 2 w_j (P_j - T_j), then the complete adjoints
-//   T   [F J 3]         the targets, loaded once as coalesced pieces
-//   A, M, V [F (J-1)]   the angles and the two Adam moments; in the evaluation sweep after the last step (the moments
-//                       are out by then) M receives the gradient rows
-//   tab [J] float4      per joint {axis, lower, upper, weight}
-//   schedule [gsteps L] GEnt, next-sibling table [J], loss partials [64], Adam's bias corrections of 64 steps [128]
+// LDS images of a tile: FitImages below (every image starts 16-byte aligned).
 // 33-link Hu, F = 16 (10 steps): 29.3 KiB; a 64-joint chain, F = 8, 64 steps: 43.9 KiB (the largest: gsteps <= J).
 //
 // Arithmetic: as in rtg_fk_grad.hip no operation order is owed to a reference (explicit fmaf, the device sincosf,
@@ -36,11 +29,6 @@
 
 namespace rtg {
 
-__host__ __device__ inline size_t fit_group_lds_floats(int J, int F, int steps)
-{
-    return (size_t)4 * F * J + 2 * pad16f((size_t)3 * F * J) + 3 * pad16f((size_t)F * (J - 1)) + (size_t)4 * J +
-           (size_t)steps * (64 / F) * 8 + pad16f((size_t)J) + 64 + 128;
-}
 constexpr size_t kFitMaxLdsBytes = 64 * 1024;   // the dynamic-LDS attribute the launcher sets (J = 64, 64 steps: 43.9 KiB)
 
 // beta^t in float64 by squaring: a function of (beta, t) alone, so a launch that starts at step0 = k takes the very
@@ -57,11 +45,33 @@ RTG_DEV double pow_int(double b, int t)
 }
 
 struct FitImages {
-    f4v *G;
-    float *P, *T, *A, *M, *V;
-    const f4v *tab;
-    const GEnt *sch;
-    const int *nsib;
+    f4v *G;          // [F J] forward: global rotations; reverse: a finished joint's contribution to its parent
+    float *P;        // [F J 3] positions, then in place the residual adjoints 2 w_j (P_j - T_j), then the complete ones
+    float *T;        // [F J 3] the targets, loaded once as coalesced pieces
+    float *A, *M, *V;   // [F (J-1)] the angles and the two Adam moments; in the evaluation sweep after the last step
+                        // (the moments are out by then) M receives the gradient rows
+    f4v *tab;        // [J] per joint {axis, lower, upper, weight}
+    GEnt *sch;       // [gsteps L] the schedule
+    int *nsib;       // [J] the next-sibling table
+    float *lossp;    // [64] loss partials
+    float *adam;     // [128] {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} of 64 steps
+    size_t floats;
+    __host__ __device__ FitImages(float *base, int J, int F, int steps)
+    {
+        LdsCarve c(base);
+        G = c.take<f4v>((size_t)F * J);
+        P = c.take<float>((size_t)3 * F * J);
+        T = c.take<float>((size_t)3 * F * J);
+        A = c.take<float>((size_t)F * (J - 1));
+        M = c.take<float>((size_t)F * (J - 1));
+        V = c.take<float>((size_t)F * (J - 1));
+        tab = c.take<f4v>(J);
+        sch = c.take<GEnt>((size_t)steps * (64 / F));
+        nsib = c.take<int>(J);
+        lossp = c.take<float>(64);
+        adam = c.take<float>(128);
+        floats = c.floats;
+    }
 };
 
 // the forward sweep: G and P of every joint below the root from the angles (the root's rows stay as loaded)
@@ -78,8 +88,7 @@ RTG_DEV void fit_forward(const FitImages &I, int J, int gsteps, bool live, int f
         if (live && j != 0xFF && j != 0) {
             const f4v t = I.tab[j];
             const AngleRot r = angle_rot<CLIP>(I.A[fr * nd + j - 1], __float_as_int(t.x), t.y, t.z);
-            const f4v gpv = I.G[base + p];
-            const Q Gp{gpv.x, gpv.y, gpv.z, gpv.w};
+            const Q Gp = q_of(I.G[base + p]);
             const Q u = qmul(Gp, angle_quat(r));
             const float n = __builtin_sqrtf(fdot4(u, u));
             const float rn = (u.w < 0.0f ? -1.0f : 1.0f) / (n < 1e-9f ? 1e-9f : n);   // quat_unit(quat_pos(u)); NaN passes
@@ -135,23 +144,16 @@ RTG_DEV void fit_reverse(const FitImages &I, int J, int gsteps, bool live, int f
         if (s > 0) en = I.sch[(s - 1) * G::L + sub];   // the next step's entry: its latency under this step
         const int j = e.code & 0xFF, p = (e.code >> 8) & 0xFF;
         if (live && j != 0xFF && j != 0) {
-            f4v a{0.0f, 0.0f, 0.0f, 0.0f};
-            float *pj = I.P + 3 * (base + j);
-            V pb{pj[0], pj[1], pj[2]};
-            for (int c = (e.code >> 16) & 0xFF; c != 0xFF; c = I.nsib[c]) {   // the children, ascending
-                a += I.G[base + c];
-                const float *pc = I.P + 3 * (base + c);
-                pb.x += pc[0]; pb.y += pc[1]; pb.z += pc[2];
-            }
-            pj[0] = pb.x; pj[1] = pb.y; pj[2] = pb.z;
-            const f4v gpv = I.G[base + p], gjv = I.G[base + j];
-            const Q Gp{gpv.x, gpv.y, gpv.z, gpv.w}, Gj{gjv.x, gjv.y, gjv.z, gjv.w};
+            V pb;
+            const f4v a = child_pull(f4v{0.0f, 0.0f, 0.0f, 0.0f}, I.G, I.P, base, j, (e.code >> 16) & 0xFF, I.nsib,
+                                     pb);
+            const Q Gp = q_of(I.G[base + p]), Gj = q_of(I.G[base + j]);
             const f4v t = I.tab[j];
             const int i = fr * nd + j - 1;
             const float ang = I.A[i];
             const AngleRot r = angle_rot<CLIP>(ang, __float_as_int(t.x), t.y, t.z);
-            const JointAdj o = joint_adjoint(Gp, Gj, angle_quat(r), V{e.lx, e.ly, e.lz}, Q{a.x, a.y, a.z, a.w}, pb);
-            I.G[base + j] = f4v{o.gp.x, o.gp.y, o.gp.z, o.gp.w};
+            const JointAdj o = joint_adjoint(Gp, Gj, angle_quat(r), V{e.lx, e.ly, e.lz}, q_of(a), pb);
+            I.G[base + j] = v_of(o.gp);
             const float g = angle_grad(r, o.lqb);
             if (EVAL) {
                 I.M[i] = g;
@@ -172,97 +174,33 @@ __global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, Dof
 {
     extern __shared__ __attribute__((aligned(16))) float ft_lds[];
     using G = Grp<F>;
-    constexpr int NP = (3 * G::NR + 3) / 4;   // float4 pieces per lane of a tile's position rows
     const int J = T.J, lane = (int)threadIdx.x, nd = J - 1;
     const int64_t f0 = (int64_t)blockIdx.x * F;
-    const int nfr = (int)((A.B - f0) < F ? (A.B - f0) : F);
-    const int nrec = nfr * J, npos = 3 * nrec, nang = nfr * nd;
-    const size_t npad = pad16f((size_t)3 * F * J), apad = pad16f((size_t)F * nd);
-    FitImages I;
-    I.G = reinterpret_cast<f4v *>(ft_lds);
-    I.P = ft_lds + (size_t)4 * F * J;
-    I.T = I.P + npad;
-    I.A = I.T + npad;
-    I.M = I.A + apad;
-    I.V = I.M + apad;
-    f4v *tab = reinterpret_cast<f4v *>(I.V + apad);
-    GEnt *sch = reinterpret_cast<GEnt *>(reinterpret_cast<float *>(tab) + 4 * J);
-    int *nsib = reinterpret_cast<int *>(sch + T.gsteps * G::L);
-    float *lossp = reinterpret_cast<float *>(nsib) + pad16f((size_t)J);
-    float *adam = lossp + 64;   // {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} of 64 steps
-    I.tab = tab;
-    I.sch = sch;
-    I.nsib = nsib;
+    const int nfr = tile_frames<F>(A.B, f0);
+    const int npos = 3 * nfr * J, nang = nfr * nd;
+    const FitImages I(ft_lds, J, F, T.gsteps);
+    float *lossp = I.lossp, *adam = I.adam;
 
     // every global load of the tile first (a lane past the rows re-reads element 0), then the LDS images
     const bool state = A.m != nullptr;
-    float ang[G::NR], m0[G::NR], v0[G::NR];
-    {
-        const float *drow = A.dof_in + f0 * nd;   // J = 1: no angles, the host passes a readable dummy
-        const float *mrow = state ? A.m + f0 * nd : drow, *vrow = state ? A.v + f0 * nd : drow;
-#pragma unroll
-        for (int k = 0; k < G::NR; ++k) {
-            const int i = k * 64 + lane, ii = i < nang ? i : 0;
-            ang[k] = drow[ii];
-            m0[k] = state ? mrow[ii] : 0.0f;
-            v0[k] = state ? vrow[ii] : 0.0f;
-        }
+    ScalarRows<F> ang, m0 = {}, v0 = {};
+    ang.load(A.dof_in + f0 * nd, nang);   // J = 1: no angles, the host passes a readable dummy
+    if (state) {
+        m0.load(A.m + f0 * nd, nang);
+        v0.load(A.v + f0 * nd, nang);
     }
     const float *trow = A.target_pos + f0 * J * 3;
-    const bool taligned = (reinterpret_cast<uintptr_t>(trow) & 15u) == 0;
-    const int n4 = npos >> 2;
-    f4v tv[NP];
-    float ttail = 0.0f;
-    if (taligned) {
-        const f4v *ts = reinterpret_cast<const f4v *>(trow);
-        if (n4 > 0) {   // (a lone one-joint frame has no whole piece to re-read)
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                const int i = k * 64 + lane;
-                tv[k] = ts[i < n4 ? i : 0];
-            }
-        }
-        if (4 * n4 + lane < npos) ttail = trow[4 * n4 + lane];
-    }
-    const f4v rr = reinterpret_cast<const f4v *>(A.root_rot)[f0 + (lane < nfr ? lane : 0)];
-    const float rt = A.root_t[f0 * 3 + (lane < 3 * nfr ? lane : 0)];
-    for (int i = lane; i < T.gsteps * G::L; i += 64) {
-        const GEnt e = T.gsched[i];
-        sch[i] = e;
-        const int j = e.code & 0xFF;
-        if (j != 0xFF) nsib[j] = (e.code >> 24) & 0xFF;
-    }
-    for (int j = lane; j < J; j += 64) {
-        const float w = A.weight ? ld_const(A.weight + j) : 1.0f;
-        tab[j] = j == 0 ? f4v{0.0f, 0.0f, 0.0f, w}
-                        : f4v{__int_as_float(ld_const(D.axis + (j - 1))), CLIP ? ld_const(D.lower + (j - 1)) : 0.0f,
-                              CLIP ? ld_const(D.upper + (j - 1)) : 0.0f, w};
-    }
-#pragma unroll
-    for (int k = 0; k < G::NR; ++k) {
-        const int i = k * 64 + lane;
-        if (i < nang) {
-            I.A[i] = ang[k];
-            I.M[i] = m0[k];
-            I.V[i] = v0[k];
-        }
-    }
-    if (taligned) {
-        f4v *td = reinterpret_cast<f4v *>(I.T);
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int i = k * 64 + lane;
-            if (i < n4) td[i] = tv[k];
-        }
-        if (4 * n4 + lane < npos) I.T[4 * n4 + lane] = ttail;
-    } else {
-        for (int i = lane; i < npos; i += 64) I.T[i] = trow[i];
-    }
-    if (lane < nfr) I.G[lane * J] = rr;   // root: global = the root rotation, unnormalised (hu_forward_model.py:24)
-    if (lane < 3 * nfr) {
-        const int q = lane / 3;
-        I.P[3 * J * q + (lane - 3 * q)] = rt;
-    }
+    PosRows<F> tp;
+    tp.load(trow, npos);
+    const f4v rr = root_rot_load(A.root_rot, f0, nfr);
+    const float rt = root_t_load(A.root_t, f0, nfr);
+    group_sched_fill(T, G::L, I.sch, I.nsib);
+    joint_tab_fill<CLIP, true>(D, J, I.tab, A.weight);
+    ang.store(I.A, nang);
+    m0.store(I.M, nang);
+    v0.store(I.V, nang);
+    tp.to_lds(I.T, trow, npos);
+    root_preset(I.G, I.P, J, nfr, rr, rt);   // the root rotation, unnormalised (hu_forward_model.py:24)
     wave_sync();
 
     const int fr = lane >> G::LOG_L, sub = lane & (G::L - 1);
@@ -290,26 +228,10 @@ __global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, Dof
     }
 
     // the iterate and its state out (coalesced), then loss and gradient there by one more sweep
-    {
-        float a[G::NR], mm[G::NR], vv[G::NR];
-#pragma unroll
-        for (int k = 0; k < G::NR; ++k) {
-            const int i = k * 64 + lane, ii = i < nang ? i : 0;
-            a[k] = I.A[ii];
-            mm[k] = I.M[ii];
-            vv[k] = I.V[ii];
-        }
-#pragma unroll
-        for (int k = 0; k < G::NR; ++k) {
-            const int i = k * 64 + lane;
-            if (i < nang) {
-                if (A.dof_out) A.dof_out[f0 * nd + i] = a[k];
-                if (state) {
-                    A.m[f0 * nd + i] = mm[k];
-                    A.v[f0 * nd + i] = vv[k];
-                }
-            }
-        }
+    if (A.dof_out) ScalarRows<F>::copy_out(I.A, A.dof_out + f0 * nd, nang);
+    if (state) {
+        ScalarRows<F>::copy_out(I.M, A.m + f0 * nd, nang);
+        ScalarRows<F>::copy_out(I.V, A.v + f0 * nd, nang);
     }
     if (!A.loss && !A.grad) return;
     wave_sync();   // the M image is read out before the evaluation sweep writes gradients into it
@@ -327,11 +249,7 @@ __global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, Dof
     }
     if (A.grad) {
         fit_reverse<CLIP, true, F>(I, J, T.gsteps, live, fr, sub, S);
-#pragma unroll
-        for (int k = 0; k < G::NR; ++k) {
-            const int i = k * 64 + lane;
-            if (i < nang) A.grad[f0 * nd + i] = I.M[i];
-        }
+        ScalarRows<F>::copy_out(I.M, A.grad + f0 * nd, nang);
     }
 }
 
@@ -339,24 +257,15 @@ hipError_t launch_dof_fit(const TopoView &T, const DofView &D, bool clip, const 
 {
     if (!T.gsched) return hipErrorInvalidValue;   // J > kGroupMaxJ: the caller reports it as unsupported
     const int F = T.gF;
-    const size_t lds = sizeof(float) * fit_group_lds_floats(T.J, F, T.gsteps);
+    const size_t lds = sizeof(float) * FitImages(nullptr, T.J, F, T.gsteps).floats;
     if (lds > kFitMaxLdsBytes) return hipErrorInvalidValue;
-    const dim3 g(grid_for(A.B, F)), b(64);
-#define RTG_FIT_GROUP(CLIP, FR)                                                                                       \
-    do {                                                                                                              \
-        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_group<CLIP, FR>),       \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes); \
-        if (attr != hipSuccess) return attr;                                                                          \
-        hipLaunchKernelGGL((k_dof_fit_group<CLIP, FR>), g, b, lds, s, T, D, A);                                       \
-    } while (0)
-    if (F == 16) {
-        if (clip) RTG_FIT_GROUP(true, 16);
-        else RTG_FIT_GROUP(false, 16);
-    } else {
-        if (clip) RTG_FIT_GROUP(true, 8);
-        else RTG_FIT_GROUP(false, 8);
-    }
-#undef RTG_FIT_GROUP
+    hipError_t attr = hipSuccess;
+    group_dispatch(F, [&](auto f, auto cl) {
+        attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_group<cl(), f()>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
+        if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A);
+    }, clip);
+    if (attr != hipSuccess) return attr;
     return hipGetLastError();
 }
 

@@ -3,10 +3,7 @@
 // runs the lane-group kernels below; larger trees fall back to the lane walks (one frame per thread).
 #include "rtg_device.cuh"
 #include "rtg_fk_group.cuh"
-
-#include <algorithm>
-#include <type_traits>
-#include <vector>
+#include "rtg_group_sched.h"
 
 namespace rtg {
 
@@ -109,11 +106,7 @@ __global__ __launch_bounds__(256) void k_dof_fk_walk(TopoView T, DofView D, cons
     for (int j = 1; j < T.J; ++j) {
         const int p = T.parents[j];
         float a = drow[j - 1];
-        if (CLIP) {   // torch.clamp (min then max; NaN passes), then the straight-through sum
-            float c = a < D.lower[j - 1] ? D.lower[j - 1] : a;
-            c = c > D.upper[j - 1] ? D.upper[j - 1] : c;
-            a = (c - a) + a;
-        }
+        if (CLIP) a = clamp_st(a, D.lower[j - 1], D.upper[j - 1]);
         const int ax = D.axis[j - 1];
         const Q lq = qfrom_angle_unit_axis(a, V{ax == 0 ? 1.0f : 0.0f, ax == 1 ? 1.0f : 0.0f, ax == 2 ? 1.0f : 0.0f});
         const Q g = ld4(gr + 4 * p);
@@ -133,9 +126,9 @@ __global__ __launch_bounds__(256) void k_dof_fk_walk(TopoView T, DofView D, cons
 // l of load k takes record 64 k + l, so every instruction reads or writes 1 KiB of consecutive bytes, each line of
 // the rows is requested once, and the positions leave as consecutive dwordx4 pieces.  The records go through LDS:
 //   1. every record of the tile is loaded (all loads in flight) and stored into the LDS image of the rows;
-//   2. the joints are composed by a host-built list schedule (fk_group_schedule): at step s, sub-lane u of each
-//      frame's group composes the joint the schedule names, reading its parent's global transform from the image and
-//      writing its own over its local rotation -- a parent is always composed at an earlier step.  Each joint is
+//   2. the joints are composed by a host-built list schedule (group_list_schedule, rtg_group_sched.h): at step s,
+//      sub-lane u of each frame's group composes the joint the schedule names, reading its parent's global transform
+//      from the image and writing its own over its local rotation -- a parent is always composed earlier.  Each joint is
 //      composed exactly as in kinematics.py:27-37 / fk_stream_tile (same device functions, same operands, same
 //      order), so the bits are the same whatever the schedule; only which lane does it and when changes.  Hu: 31
 //      joints in 10 steps (its depth + 1) on four lanes;
@@ -143,16 +136,25 @@ __global__ __launch_bounds__(256) void k_dof_fk_walk(TopoView T, DofView D, cons
 // LDS per wave: F J 28 bytes plus the schedule (Hu: 13.9 + 1.3 KiB).  Inverse FK (kinematics.py:41-63) has no chain:
 // each record's parent is read from the image and its local rotation stored straight from the lane that loaded it.
 // ----------------------------------------------------------------------------
-// rot [F J] float4 | pos [F J 3] float | schedule [gsteps L] GEnt | extra floats (kernel-specific tables)
-// ... | the near-unit table (kUnitTabFloats)
-__host__ __device__ inline size_t group_core_floats(int J, int F, int steps)
-{
-    return (size_t)F * J * 4 + pad16f((size_t)F * J * 3) + (size_t)steps * (64 / F) * 8;
-}
-__host__ __device__ inline size_t group_lds_floats(int J, int F, int steps)
-{
-    return group_core_floats(J, F, steps) + kUnitTabFloats;
-}
+// The FK tile's images; dof: the joint-angle model's per-joint {axis, lower, upper} table behind them
+struct FkImages {
+    f4v *rot;        // [F J] the local rotations, overwritten by the global ones
+    float *pos;      // [F J 3] the positions, the root's preset
+    GEnt *sch;       // [gsteps L] the schedule
+    UnitEnt *utab;   // the near-unit table
+    f4v *ntab;       // dof: [J]
+    size_t floats;
+    __host__ __device__ FkImages(float *base, int J, int F, int steps, bool dof)
+    {
+        LdsCarve c(base);
+        rot = c.take<f4v>((size_t)F * J);
+        pos = c.take<float>((size_t)3 * F * J);
+        sch = c.take<GEnt>((size_t)steps * (64 / F));
+        utab = c.take_unit_tab();
+        ntab = c.take<f4v>(dof ? J : 0);
+        floats = c.floats;
+    }
+};
 
 // The schedule's steps over the tile image (rot: global rotations written over the local ones; pos: positions, the
 // root's preset).  LQ(j, lq) gives joint j's local rotation from its image record (FK: the record itself, with the
@@ -174,19 +176,18 @@ RTG_DEV void group_compose(const TopoView &T, f4v *rot, float *pos, const GEnt *
             Q ng;
             V nt;
             if (j == 0) {   // root: global = local, unnormalised; position = the root translation (kinematics.py:27-29)
-                ng = Q{lv.x, lv.y, lv.z, lv.w};
+                ng = q_of(lv);
                 nt = V{pos[3 * base], pos[3 * base + 1], pos[3 * base + 2]};
             } else {
-                const Q lq = LQ(j, Q{lv.x, lv.y, lv.z, lv.w}, e, fr);
-                const f4v gv = rot[base + p];
-                const Q g{gv.x, gv.y, gv.z, gv.w};
+                const Q lq = LQ(j, q_of(lv), e, fr);
+                const Q g = q_of(rot[base + p]);
                 const float *tp = pos + 3 * (base + p);
                 const V t{tp[0], tp[1], tp[2]};
                 const V rv = qrotate(g, V{e.lx, e.ly, e.lz});
                 ng = qmul_norm_tab(g, lq, utab);
                 nt = V{rv.x + t.x, rv.y + t.y, rv.z + t.z};
             }
-            rot[base + j] = f4v{ng.x, ng.y, ng.z, ng.w};
+            rot[base + j] = v_of(ng);
             float *op = pos + 3 * (base + j);
             op[0] = nt.x; op[1] = nt.y; op[2] = nt.z;
         }
@@ -194,64 +195,36 @@ RTG_DEV void group_compose(const TopoView &T, f4v *rot, float *pos, const GEnt *
     }
 }
 
-// the tile image out: rotations record-ordered, positions as consecutive dwordx4 pieces (16-byte aligned rows; any
-// other g_pos alignment stores dword by dword)
+// the tile image out: rotations record-ordered, positions as consecutive pieces (PosRows)
 template <int F>
 RTG_DEV void group_store(const f4v *rot, const float *pos, int nrec, float *__restrict__ g_rot, float *__restrict__ g_pos)
 {
-    using G = Grp<F>;
-    const int lane = (int)threadIdx.x;
-    f4v *dst = reinterpret_cast<f4v *>(g_rot);
-    f4v o[G::NR];   // every LDS read first (unconditional), then the stores: no wait between two stores
-#pragma unroll
-    for (int k = 0; k < G::NR; ++k) {
-        const int rec = k * 64 + lane;
-        o[k] = rot[rec < nrec ? rec : 0];
-    }
-#pragma unroll
-    for (int k = 0; k < G::NR; ++k) {
-        const int rec = k * 64 + lane;
-        if (rec < nrec) st_out(dst + rec, o[k]);
-    }
-    const int npos = 3 * nrec;
-    if ((reinterpret_cast<uintptr_t>(g_pos) & 15u) == 0) {
-        const int n4 = npos >> 2;
-        f4v *pd = reinterpret_cast<f4v *>(g_pos);
-        const f4v *ps = reinterpret_cast<const f4v *>(pos);
-        for (int i = lane; i < n4; i += 64) st_out(pd + i, ps[i]);
-        for (int i = 4 * n4 + lane; i < npos; i += 64) g_pos[i] = pos[i];
-    } else {
-        for (int i = lane; i < npos; i += 64) g_pos[i] = pos[i];
-    }
+    GroupRows<F> o;
+    o.load(rot, nrec);
+    o.out(g_rot, nrec);
+    PosRows<F>::out(pos, g_pos, 3 * nrec);
 }
 
 template <bool STATE, int F>
 RTG_DEV void fk_group_tile(const TopoView &T, const float *__restrict__ local_rot, const float *__restrict__ root_t,
                            int64_t B, int64_t f0, float *__restrict__ g_rot, float *__restrict__ g_pos, float *lds)
 {
-    const int J = T.J, lane = (int)threadIdx.x;
-    const int nfr = (int)((B - f0) < F ? (B - f0) : F);
-    const int nrec = nfr * J;
-    f4v *rot = reinterpret_cast<f4v *>(lds);
-    float *pos = lds + 4 * F * J;
-    GEnt *sch = reinterpret_cast<GEnt *>(pos + pad16f((size_t)3 * F * J));
+    const int J = T.J;
+    const int nfr = tile_frames<F>(B, f0), nrec = nfr * J;
+    const FkImages I(lds, J, F, T.gsteps, false);
     GroupRows<F> rows;
     rows.load(local_rot + f0 * J * 4, nrec);
-    const float r = root_t[f0 * 3 + (lane < 3 * nfr ? lane : 0)];
-    group_sched_fill(T, Grp<F>::L, sch);
-    UnitEnt *utab = reinterpret_cast<UnitEnt *>(lds + group_core_floats(J, F, T.gsteps));
-    if (RTG_FK_UNIT_TAB) unit_tab_fill(utab, (int)threadIdx.x);
-    rows.to_lds(rot, nrec);
-    if (lane < 3 * nfr) {
-        const int fr = lane / 3;
-        pos[3 * J * fr + (lane - 3 * fr)] = r;
-    }
+    const float r = root_t_load(root_t, f0, nfr);
+    group_sched_fill(T, Grp<F>::L, I.sch);
+    if (RTG_FK_UNIT_TAB) unit_tab_fill(I.utab, (int)threadIdx.x);
+    rows.store(I.rot, nrec);
+    root_preset(I.pos, J, nfr, r);
     wave_sync();
-    group_compose<F>(T, rot, pos, sch, nfr, utab, [&](int, Q lq, const GEnt &e, int) {
-        if (STATE) lq = qmul_norm_tab(Q{e.qx, e.qy, e.qz, e.qw}, lq, utab);   // skeleton3d.py:412-418
+    group_compose<F>(T, I.rot, I.pos, I.sch, nfr, I.utab, [&](int, Q lq, const GEnt &e, int) {
+        if (STATE) lq = qmul_norm_tab(Q{e.qx, e.qy, e.qz, e.qw}, lq, I.utab);   // skeleton3d.py:412-418
         return lq;
     });
-    group_store<F>(rot, pos, nrec, g_rot + f0 * J * 4, g_pos + f0 * J * 3);
+    group_store<F>(I.rot, I.pos, nrec, g_rot + f0 * J * 4, g_pos + f0 * J * 3);
 }
 
 template <bool STATE, int F>
@@ -263,62 +236,58 @@ __global__ __launch_bounds__(64, 4) void k_fk_group(TopoView T, const float *__r
     fk_group_tile<STATE, F>(T, local_rot, root_t, B, (int64_t)blockIdx.x * F, g_rot, g_pos, fk_lds);
 }
 
-// inverse FK: LDS = the tile image | parents (J ints) | STATE: normalised conjugate tree quaternions (J float4)
+// inverse FK
 constexpr int kLrotFrames = 8;   // frames per wave of the inverse tiles (any J <= kGroupMaxJ)
-__host__ __device__ inline size_t lrot_core_floats(int J, int F) { return (size_t)F * J * 4 + pad16f((size_t)J) + (size_t)J * 4; }
-__host__ __device__ inline size_t lrot_group_lds_floats(int J, int F) { return lrot_core_floats(J, F) + kUnitTabFloats; }
+struct LrotImages {
+    f4v *rot;        // [F J] the global rotations
+    int *par;        // [J] the parents
+    f4v *tqn;        // [J] STATE: the normalised conjugate tree quaternions
+    UnitEnt *utab;   // the near-unit table
+    size_t floats;
+    __host__ __device__ LrotImages(float *base, int J, int F)
+    {
+        LdsCarve c(base);
+        rot = c.take<f4v>((size_t)F * J);
+        par = c.take<int>(J);
+        tqn = c.take<f4v>(J);
+        utab = c.take_unit_tab();
+        floats = c.floats;
+    }
+};
 template <bool STATE, int F>
 RTG_DEV void lrot_group_tile(const TopoView &T, const float *__restrict__ g_rot, int64_t B, int64_t f0,
                              float *__restrict__ local_rot, float *lds)
 {
     using G = Grp<F>;
     const int J = T.J, lane = (int)threadIdx.x;
-    const int nfr = (int)((B - f0) < F ? (B - f0) : F);
-    const int nrec = nfr * J;
-    f4v *rot = reinterpret_cast<f4v *>(lds);
-    int *par = reinterpret_cast<int *>(lds + 4 * F * J);
-    f4v *tqn = reinterpret_cast<f4v *>(lds + 4 * F * J + pad16f((size_t)J));
-    const f4v *src = reinterpret_cast<const f4v *>(g_rot + f0 * J * 4);
-    f4v v[G::NR];   // unconditional loads (a lane past the tile re-reads record 0): no branch between them
-#pragma unroll
-    for (int k = 0; k < G::NR; ++k) {
-        const int rec = k * 64 + lane;
-        v[k] = src[rec < nrec ? rec : 0];
-    }
-    UnitEnt *utab = reinterpret_cast<UnitEnt *>(lds + lrot_core_floats(J, F));
-    if (RTG_FK_UNIT_TAB) unit_tab_fill(utab, (int)threadIdx.x);
+    const int nfr = tile_frames<F>(B, f0), nrec = nfr * J;
+    const LrotImages I(lds, J, F);
+    f4v *rot = I.rot;
+    const UnitEnt *utab = I.utab;
+    GroupRows<F> rows;
+    rows.load(g_rot + f0 * J * 4, nrec);
+    if (RTG_FK_UNIT_TAB) unit_tab_fill(I.utab, (int)threadIdx.x);
     for (int j = lane; j < J; j += 64) {
-        par[j] = ld_const(T.parents + j);
-        if (STATE) {   // skeleton3d.py:470-478: quat_normalize(quat_conjugate(tree quat)), once per joint
-            const Q c = qnormalize(qconj(ld_const(T.tree_quat + j)));
-            tqn[j] = f4v{c.x, c.y, c.z, c.w};
-        }
+        I.par[j] = ld_const(T.parents + j);
+        // skeleton3d.py:470-478: quat_normalize(quat_conjugate(tree quat)), once per joint
+        if (STATE) I.tqn[j] = v_of(qnormalize(qconj(ld_const(T.tree_quat + j))));
     }
-#pragma unroll
-    for (int k = 0; k < G::NR; ++k) {
-        const int rec = k * 64 + lane;
-        if (rec < nrec) rot[rec] = v[k];
-    }
+    rows.store(rot, nrec);
     wave_sync();
-    const float rJ = 1.0f / (float)J;   // rec / J as ((rec + 1/2) / J) truncated: exact for rec < 2^12, J <= 64
+    const float rJ = item_rcp(J);
     f4v *dst = reinterpret_cast<f4v *>(local_rot + f0 * J * 4);
 #pragma unroll 3
     for (int k = 0; k < G::NR; ++k) {   // the records from the image: the loaded registers are free by now
         const int rec = k * 64 + lane;
         if (rec < nrec) {
-            const int fr = (int)(((float)rec + 0.5f) * rJ), j = rec - fr * J;
-            const f4v gv = rot[rec];
-            const Q gj{gv.x, gv.y, gv.z, gv.w};
+            const Item it = item_split(rec, rJ, J);
+            const Q gj = q_of(rot[rec]);
             Q q = gj;   // root copied (kinematics.py:49)
-            if (j > 0) {
-                const f4v pv = rot[fr * J + par[j]];
-                q = qmul_norm_tab(qconj(Q{pv.x, pv.y, pv.z, pv.w}), gj, utab);
-                if (STATE) {
-                    const f4v c = tqn[j];
-                    q = qmul_norm_tab(Q{c.x, c.y, c.z, c.w}, q, utab);
-                }
+            if (it.j > 0) {
+                q = qmul_norm_tab(qconj(q_of(rot[it.fr * J + I.par[it.j]])), gj, utab);
+                if (STATE) q = qmul_norm_tab(q_of(I.tqn[it.j]), q, utab);
             }
-            st_out(dst + rec, f4v{q.x, q.y, q.z, q.w});
+            st_out(dst + rec, v_of(q));
         }
     }
 }
@@ -336,7 +305,7 @@ __global__ __launch_bounds__(64, 4) void k_lrot_group(TopoView T, const float *_
 // floats, NR loads per lane) into joint rotations -- quat_from_angle_axis of the clipped angle about the joint's unit
 // axis -- and writes them into the tile image where FK's local rotations would be; then FK's compose runs as is.  (A
 // first version built each joint's rotation inside its compose step: the f64 sincos sat on the chain's critical path
-// and the kernel took 128 us against FK's 88, profiles/r06/fk/.)  LDS = the tile image | per-joint {axis, lower, upper}
+// and the kernel took 128 us against FK's 88, profiles/r06/fk/.)  LDS: FkImages with the per-joint table.
 // qfrom_angle_unit_axis(angle, e_ax) for N joints, element by element the same values: qnormalize's sign flip f
 // (on cos), its |q|^2 in any component order (the zero components add +0 exactly), (n, 1/n) from the table, the two
 // nonzero components' products by 1/n, and the zero components keep the sign of f sin (0 sin, times f, times 1/n > 0).
@@ -372,10 +341,6 @@ RTG_DEV void joint_rot_n(const float (&angle)[N], const int (&ax)[N], const Unit
                                                            ax[i] == 2 ? 1.0f : 0.0f});
     }
 }
-__host__ __device__ inline size_t dof_group_lds_floats(int J, int F, int steps)
-{
-    return group_lds_floats(J, F, steps) + (size_t)J * 4;
-}
 template <bool CLIP, int F>
 __global__ __launch_bounds__(64, 4) void k_dof_fk_group(TopoView T, DofView D, const float *__restrict__ dof,
                                                      const float *__restrict__ root_rot,
@@ -386,39 +351,22 @@ __global__ __launch_bounds__(64, 4) void k_dof_fk_group(TopoView T, DofView D, c
     using G = Grp<F>;
     const int J = T.J, lane = (int)threadIdx.x, nd = J - 1;
     const int64_t f0 = (int64_t)blockIdx.x * F;
-    const int nfr = (int)((B - f0) < F ? (B - f0) : F);
-    const int nrec = nfr * J;
-    f4v *rot = reinterpret_cast<f4v *>(fk_lds);
-    float *pos = fk_lds + 4 * F * J;
-    GEnt *sch = reinterpret_cast<GEnt *>(pos + pad16f((size_t)3 * F * J));
-    f4v *ntab = reinterpret_cast<f4v *>(fk_lds + group_lds_floats(J, F, T.gsteps));
-    const float *drow = dof + f0 * nd;
-    const int nang = nfr * nd;
-    float a[G::NR];   // unconditional loads (a lane past the rows re-reads element 0)
-#pragma unroll
-    for (int k = 0; k < G::NR; ++k) {
-        const int i = k * 64 + lane;
-        a[k] = drow[i < nang ? i : 0];
-    }
-    const f4v rr = reinterpret_cast<const f4v *>(root_rot)[f0 + (lane < nfr ? lane : 0)];
-    const float rt = root_t[f0 * 3 + (lane < 3 * nfr ? lane : 0)];
-    group_sched_fill(T, G::L, sch);
-    UnitEnt *utab = reinterpret_cast<UnitEnt *>(fk_lds + group_core_floats(J, F, T.gsteps));
-    if (kUnitTab) unit_tab_fill(utab, (int)threadIdx.x);
-    for (int j = 1 + lane; j < J; j += 64) {
-        const int ax = ld_const(D.axis + (j - 1));
-        ntab[j] = f4v{__int_as_float(ax), CLIP ? ld_const(D.lower + (j - 1)) : 0.0f,
-                      CLIP ? ld_const(D.upper + (j - 1)) : 0.0f, 0.0f};
-    }
-    if (lane < nfr) rot[lane * J] = rr;   // root: global = the root rotation (hu_forward_model.py:24)
-    if (lane < 3 * nfr) {
-        const int fr = lane / 3;
-        pos[3 * J * fr + (lane - 3 * fr)] = rt;
-    }
+    const int nfr = tile_frames<F>(B, f0), nrec = nfr * J, nang = nfr * nd;
+    const FkImages I(fk_lds, J, F, T.gsteps, true);
+    f4v *rot = I.rot;
+    const f4v *ntab = I.ntab;
+    const UnitEnt *utab = I.utab;
+    ScalarRows<F> a;
+    a.load(dof + f0 * nd, nang);
+    const f4v rr = root_rot_load(root_rot, f0, nfr);
+    const float rt = root_t_load(root_t, f0, nfr);
+    group_sched_fill(T, G::L, I.sch);
+    if (kUnitTab) unit_tab_fill(I.utab, (int)threadIdx.x);
+    joint_tab_fill<CLIP, false>(D, J, I.ntab);
+    root_preset(rot, I.pos, J, nfr, rr, rt);
     wave_sync();
-    // angle i = (frame fr, joint i mod nd + 1): its rotation into record fr J + j (i / nd as ((i + 1/2) / nd)
-    // truncated: exact for i < 2^12)
-    const float rnd = 1.0f / (float)(nd > 0 ? nd : 1);
+    // angle i = (frame fr, joint i mod nd + 1): its rotation into record fr J + j
+    const float rnd = item_rcp(nd > 0 ? nd : 1);
     // NW loads' rotations at a time on the N-way leaf math (one rare-case branch per group, the same bits); a lane
     // past the angles computes a dummy rotation (its j is still a joint) and does not store it
     auto rotations = [&](auto nw, int k0) {
@@ -429,14 +377,10 @@ __global__ __launch_bounds__(64, 4) void k_dof_fk_group(TopoView T, DofView D, c
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
             const int i = (k0 + w) * 64 + lane;
-            const int fr = (int)(((float)i + 0.5f) * rnd), j = i - fr * nd + 1;
+            const Item it = item_split(i, rnd, nd);
+            const int fr = it.fr, j = it.j + 1;
             const f4v t = ntab[j];
-            x[w] = a[k0 + w];
-            if (CLIP) {   // torch.clamp (min then max; NaN passes), then the straight-through sum
-                float c = x[w] < t.y ? t.y : x[w];
-                c = c > t.z ? t.z : c;
-                x[w] = (c - x[w]) + x[w];
-            }
+            x[w] = CLIP ? clamp_st(a.v[k0 + w], t.y, t.z) : a.v[k0 + w];
             // the axis is an exact unit vector: quat_from_angle_axis's normalisation is the identity (round 5)
             axi[w] = __float_as_int(t.x);
             rec[w] = i < nang ? fr * J + j : -1;
@@ -453,7 +397,7 @@ __global__ __launch_bounds__(64, 4) void k_dof_fk_group(TopoView T, DofView D, c
 #endif
 #pragma unroll
         for (int w = 0; w < NW; ++w)
-            if (rec[w] >= 0) rot[rec[w]] = f4v{q[w].x, q[w].y, q[w].z, q[w].w};
+            if (rec[w] >= 0) rot[rec[w]] = v_of(q[w]);
     };
     constexpr int NW = RTG_DOF_NWAY, NFULL = G::NR - G::NR % NW;
 #pragma unroll
@@ -461,8 +405,8 @@ __global__ __launch_bounds__(64, 4) void k_dof_fk_group(TopoView T, DofView D, c
 #pragma unroll
     for (int k = NFULL; k < G::NR; ++k) rotations(std::integral_constant<int, 1>{}, k);
     wave_sync();
-    group_compose<F>(T, rot, pos, sch, nfr, utab, [&](int, Q lq, const GEnt &, int) { return lq; });
-    group_store<F>(rot, pos, nrec, g_rot + f0 * J * 4, g_pos + f0 * J * 3);
+    group_compose<F>(T, rot, I.pos, I.sch, nfr, utab, [&](int, Q lq, const GEnt &, int) { return lq; });
+    group_store<F>(rot, I.pos, nrec, g_rot + f0 * J * 4, g_pos + f0 * J * 3);
 }
 
 // Mixed-target kinematics on the lane groups (config 5): a block is one tile of one segment; the segment's F comes
@@ -481,43 +425,23 @@ __global__ __launch_bounds__(64, 4) void k_fk_multi_group(FkMultiArgs A)
     else fk_group_tile<false, 8>(S.T, S.local_rot, S.root_t, S.B, t * 8, S.g_rot, S.g_pos, fk_lds);
 }
 
-// Host: the lane-group list schedule.  Joints become ready once their parent's step is past; each step takes up to L
-// ready joints, longest remaining chain (height) first, ties by index -- for a tree that is the critical-path bound
-// (depth + 1 steps) whenever L covers the widest level the chains keep busy (Hu on 4 lanes: 10 steps for 31 joints).
-// The bits do not depend on it (group_compose).  Returns the step count, or -1 if it would exceed max_steps.
+// Host: a topology's lane-group schedule: group_list_schedule's order over all J joints (the root takes an entry), each
+// entry with its joint's local translation, tree quaternion and child links.  Returns the step count, or -1 if it
+// would exceed max_steps.
 int32_t fk_group_schedule(const int32_t *parents, const V *local_t, const Q *tree_quat, int32_t J, int32_t F,
                           GEnt *out, int32_t max_steps)
 {
-    const int L = 64 / F;
-    std::vector<int> h(J, 1), done(J, -1);
-    for (int j = J - 1; j > 0; --j) h[parents[j]] = std::max(h[parents[j]], h[j] + 1);
-    // child links for the reverse sweep (rtg_fk_grad.hip): first child and next sibling, by index; 0xFF: none
-    std::vector<uint32_t> fc(J, 0xFF), ns(J, 0xFF);
-    for (int j = J - 1; j > 0; --j) {
-        ns[j] = fc[parents[j]];
-        fc[parents[j]] = (uint32_t)j;
-    }
-    int steps = 0, placed = 0;
-    std::vector<int> ready;
-    while (placed < J) {
-        if (steps >= max_steps) return -1;
-        ready.clear();
-        for (int j = 0; j < J; ++j)
-            if (done[j] < 0 && (j == 0 || (done[parents[j]] >= 0 && done[parents[j]] < steps))) ready.push_back(j);
-        std::stable_sort(ready.begin(), ready.end(), [&](int a, int b) { return h[a] > h[b]; });
-        for (int u = 0; u < L; ++u) {
-            GEnt &e = out[steps * L + u];
-            e = GEnt{0.f, 0.f, 0.f, 0xFFFF, 0.f, 0.f, 0.f, 1.f};
-            if (u < (int)ready.size()) {
-                const int j = ready[u];
-                done[j] = steps;
-                ++placed;
-                const uint32_t code = (uint32_t)j | ((uint32_t)(j ? parents[j] : 0xFF) << 8) | (fc[j] << 16) | (ns[j] << 24);
-                e = GEnt{local_t[j].x, local_t[j].y, local_t[j].z, (int32_t)code,
-                         tree_quat[j].x, tree_quat[j].y, tree_quat[j].z, tree_quat[j].w};
-            }
-        }
-        ++steps;
+    std::vector<int> order;
+    const int steps = group_list_schedule(parents, J, nullptr, true, 64 / F, max_steps, order);
+    std::vector<uint32_t> fc, ns;
+    group_child_links(parents, J, fc, ns);
+    for (size_t i = 0; steps > 0 && i < order.size(); ++i) {
+        const int j = order[i];
+        out[i] = GEnt{0.f, 0.f, 0.f, 0xFFFF, 0.f, 0.f, 0.f, 1.f};
+        if (j < 0) continue;
+        const uint32_t code = (uint32_t)j | ((uint32_t)(j ? parents[j] : 0xFF) << 8) | (fc[j] << 16) | (ns[j] << 24);
+        out[i] = GEnt{local_t[j].x, local_t[j].y, local_t[j].z, (int32_t)code,
+                      tree_quat[j].x, tree_quat[j].y, tree_quat[j].z, tree_quat[j].w};
     }
     return steps;
 }
@@ -527,15 +451,10 @@ hipError_t launch_fk(const TopoView &T, bool state, const float *lr, const float
 {
     if (T.gsched) {
         const int F = T.gF;
-        const size_t lds = sizeof(float) * group_lds_floats(T.J, F, T.gsteps);
-        const dim3 g(grid_for(B, F)), b(64);
-        if (F == 16) {
-            if (state) hipLaunchKernelGGL((k_fk_group<true, 16>), g, b, lds, s, T, lr, rt, B, gr, gp);
-            else hipLaunchKernelGGL((k_fk_group<false, 16>), g, b, lds, s, T, lr, rt, B, gr, gp);
-        } else {
-            if (state) hipLaunchKernelGGL((k_fk_group<true, 8>), g, b, lds, s, T, lr, rt, B, gr, gp);
-            else hipLaunchKernelGGL((k_fk_group<false, 8>), g, b, lds, s, T, lr, rt, B, gr, gp);
-        }
+        const size_t lds = sizeof(float) * FkImages(nullptr, T.J, F, T.gsteps, false).floats;
+        group_dispatch(F, [&](auto f, auto st) {
+            hipLaunchKernelGGL((k_fk_group<st(), f()>), dim3(grid_for(B, F)), dim3(64), lds, s, T, lr, rt, B, gr, gp);
+        }, state);
     } else if (state) {   // J > kGroupMaxJ: lane walk
         hipLaunchKernelGGL(k_fk<true>, dim3(grid_for(B, 256)), dim3(256), 0, s, T, lr, rt, B, gr, gp);
     } else {
@@ -548,10 +467,11 @@ hipError_t launch_local_rotation(const TopoView &T, bool state, const float *g, 
 {
     if (T.gsched) {   // 8 frames per wave whatever J: no chain here, so the smallest tile -- the most waves per CU --
                       // wins (Hu: 41.4 vs 46.8 us at 16 frames, profiles/r06/fk/)
-        const size_t lds = sizeof(float) * lrot_group_lds_floats(T.J, kLrotFrames);
-        const dim3 gd(grid_for(B, kLrotFrames)), b(64);
-        if (state) hipLaunchKernelGGL((k_lrot_group<true, kLrotFrames>), gd, b, lds, s, T, g, B, l);
-        else hipLaunchKernelGGL((k_lrot_group<false, kLrotFrames>), gd, b, lds, s, T, g, B, l);
+        const size_t lds = sizeof(float) * LrotImages(nullptr, T.J, kLrotFrames).floats;
+        dispatch_bools([&](auto st) {
+            hipLaunchKernelGGL((k_lrot_group<st(), kLrotFrames>), dim3(grid_for(B, kLrotFrames)), dim3(64), lds, s, T, g,
+                               B, l);
+        }, state);
     } else if (state) {   // J > kGroupMaxJ: lane walk
         hipLaunchKernelGGL(k_local_rotation<true>, dim3(grid_for(B, 256)), dim3(256), 0, s, T, g, B, l);
     } else {
@@ -572,8 +492,8 @@ hipError_t launch_fk_multi(FkMultiArgs &A, hipStream_t s)
         A.block_start[i] = blocks;
         blocks += grid_for(A.seg[i].B, group ? (A.seg[i].op == 0 ? T.gF : kLrotFrames) : 256);
         if (group) {
-            const size_t need =
-                A.seg[i].op == 0 ? group_lds_floats(T.J, T.gF, T.gsteps) : lrot_group_lds_floats(T.J, kLrotFrames);
+            const size_t need = A.seg[i].op == 0 ? FkImages(nullptr, T.J, T.gF, T.gsteps, false).floats
+                                                 : LrotImages(nullptr, T.J, kLrotFrames).floats;
             lds = need > lds ? need : lds;
         }
     }
@@ -589,15 +509,11 @@ hipError_t launch_dof_fk(const TopoView &T, const DofView &D, bool clip, const f
 {
     if (T.gsched) {
         const int F = T.gF;
-        const size_t lds = sizeof(float) * dof_group_lds_floats(T.J, F, T.gsteps);
-        const dim3 g(grid_for(B, F)), b(64);
-        if (F == 16) {
-            if (clip) hipLaunchKernelGGL((k_dof_fk_group<true, 16>), g, b, lds, s, T, D, dof, root_rot, root_t, B, gr, gp);
-            else hipLaunchKernelGGL((k_dof_fk_group<false, 16>), g, b, lds, s, T, D, dof, root_rot, root_t, B, gr, gp);
-        } else {
-            if (clip) hipLaunchKernelGGL((k_dof_fk_group<true, 8>), g, b, lds, s, T, D, dof, root_rot, root_t, B, gr, gp);
-            else hipLaunchKernelGGL((k_dof_fk_group<false, 8>), g, b, lds, s, T, D, dof, root_rot, root_t, B, gr, gp);
-        }
+        const size_t lds = sizeof(float) * FkImages(nullptr, T.J, F, T.gsteps, true).floats;
+        group_dispatch(F, [&](auto f, auto cl) {
+            hipLaunchKernelGGL((k_dof_fk_group<cl(), f()>), dim3(grid_for(B, F)), dim3(64), lds, s, T, D, dof, root_rot,
+                               root_t, B, gr, gp);
+        }, clip);
     } else if (clip) {   // J > kGroupMaxJ: lane walk
         hipLaunchKernelGGL(k_dof_fk_walk<true>, dim3(grid_for(B, 256)), dim3(256), 0, s, T, D, dof, root_rot, root_t, B,
                            gr, gp);

@@ -2,7 +2,7 @@
 // by the adjoint kernels (rtg_fk_grad.hip) and the fused keypoint fit (rtg_dof_fit.hip).  The derivation is in the
 // header comment of rtg_fk_grad.hip.  No operation order is owed to anyone here: explicit fmaf, the device sincosf.
 #pragma once
-#include "rtg_device.cuh"
+#include "rtg_fk_group.cuh"
 
 namespace rtg {
 
@@ -49,8 +49,7 @@ RTG_DEV JointAdj joint_adjoint(const Q &Gp, const Q &Gj, const Q &lq, const V &z
 }
 
 // the joint-angle model's local rotation and its derivative: lq = (sn e_ax, cs), d lq / d a = (cs e_ax, -sn) / 2, with
-// quat_from_angle_axis's w >= 0 flip already in sn, cs.  The clip is torch.clamp (min then max; NaN passes) in the
-// straight-through sum, as in the forward.
+// quat_from_angle_axis's w >= 0 flip already in sn, cs.  The clip is the forward's (clamp_st).
 struct AngleRot {
     float sn, cs;
     int ax;
@@ -58,11 +57,7 @@ struct AngleRot {
 template <bool CLIP>
 RTG_DEV AngleRot angle_rot(float a, int ax, float lo, float hi)
 {
-    if (CLIP) {
-        float c = a < lo ? lo : a;
-        c = c > hi ? hi : c;
-        a = (c - a) + a;
-    }
+    if (CLIP) a = clamp_st(a, lo, hi);
     float sn, cs;
     sincosf(a * 0.5f, &sn, &cs);
     const float f = cs < 0.0f ? -1.0f : 1.0f;

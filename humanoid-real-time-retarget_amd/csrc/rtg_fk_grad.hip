@@ -23,31 +23,42 @@ namespace rtg {
 // ----------------------------------------------------------------------------
 // Lane groups (J <= kGroupMaxJ): the forward's tile -- F frames per wave, 64 / F lanes per frame -- and its schedule
 // run backwards: at reverse step s, sub-lane u of each frame's group takes the joint the forward composed at step s.
-// Its children were composed at later forward steps, so they are already done.  LDS images, all rows as coalesced
-// pieces:
-//   G [F J] float4   the saved forward rotations
-//   A [F J] float4   in: the upstream rotation gradient rows (zeros when absent); a finished joint leaves its
-//                    contribution to its parent's adjoint here, the root its complete adjoint
-//   P [F J 3] float  in: the upstream position gradient rows; a finished joint leaves its complete adjoint here
-//   X                DOF: the angles [F (J - 1)] float, replaced by their gradients; plain FK: the local rotations
-//                    [F J] float4, replaced by theirs
+// Its children were composed at later forward steps, so they are already done.  The LDS images (BwdImages), all rows
+// moved as coalesced pieces by the kit's row movers (rtg_fk_group.cuh).
 // Without an upstream rotation gradient (ROT = false: a loss on positions only, the common case) A has nothing to
 // hold at the start, and a joint's saved rotation is last read when the joint itself is processed (its children, who
 // read it as their parent's, come first): the joint's contribution goes into its G row, and the A image is not
 // allocated -- a third less LDS, more tiles per CU.  The sums start from +0 and add the same terms in the same order,
 // so the bits are those of an explicit zero gradient.
 // Siblings: a joint does not add into its parent's rows.  The parent, when its turn comes, pulls its children's rows
-// in ascending index order (first child / next sibling links, in the schedule entries and a J-entry table), so every
-// sum has one fixed order whatever the schedule, and no LDS atomic is needed.
+// in ascending index order (child_pull: first child / next sibling links, in the schedule entries and a J-entry
+// table), so every sum has one fixed order whatever the schedule, and no LDS atomic is needed.
 // ----------------------------------------------------------------------------
-template <int F>
-constexpr int pos_pieces() { return (3 * Grp<F>::NR + 3) / 4; }   // float4 pieces per lane of a tile's position rows
-
-__host__ __device__ inline size_t bwd_group_lds_floats(int J, int F, int steps, bool dof, bool rot)
-{
-    return (size_t)(rot ? 8 : 4) * F * J + pad16f((size_t)3 * F * J) + (dof ? pad16f((size_t)F * (J - 1)) + (size_t)4 * J : (size_t)4 * F * J) +
-           (size_t)steps * (64 / F) * 8 + pad16f((size_t)J);
-}
+struct BwdImages {
+    f4v *G;       // [F J] the saved forward rotations
+    f4v *A;       // [F J] in: the upstream rotation gradient rows; a finished joint leaves its contribution to its
+                  // parent's adjoint here, the root its complete adjoint.  Not ROT: the G image
+    float *P;     // [F J 3] in: the upstream position gradient rows; a finished joint leaves its complete adjoint here
+    float *X;     // DOF: [F (J - 1)] the angles, replaced by their gradients
+    f4v *X4;      // plain FK: [F J] the local rotations, replaced by theirs
+    f4v *ntab;    // DOF: [J] per joint {axis, lower, upper}
+    GEnt *sch;    // [gsteps L] the schedule
+    int *nsib;    // [J] the next-sibling table
+    size_t floats;
+    __host__ __device__ BwdImages(float *base, int J, int F, int steps, bool dof, bool rot)
+    {
+        LdsCarve c(base);
+        G = c.take<f4v>((size_t)F * J);
+        A = rot ? c.take<f4v>((size_t)F * J) : G;
+        P = c.take<float>((size_t)3 * F * J);
+        X = c.take<float>(dof ? (size_t)F * (J - 1) : 0);
+        X4 = c.take<f4v>(dof ? 0 : (size_t)F * J);
+        ntab = c.take<f4v>(dof ? J : 0);
+        sch = c.take<GEnt>((size_t)steps * (64 / F));
+        nsib = c.take<int>(J);
+        floats = c.floats;
+    }
+};
 
 template <bool DOF, bool CLIP, bool ROT, int F>
 __global__ __launch_bounds__(64) void k_fk_bwd_group(TopoView T, DofView D, const float *__restrict__ lq_in,
@@ -58,83 +69,37 @@ __global__ __launch_bounds__(64) void k_fk_bwd_group(TopoView T, DofView D, cons
 {
     extern __shared__ __attribute__((aligned(16))) float bw_lds[];
     using G = Grp<F>;
-    constexpr int NP = pos_pieces<F>();
     const int J = T.J, lane = (int)threadIdx.x, nd = J - 1;
     const int64_t f0 = (int64_t)blockIdx.x * F;
-    const int nfr = (int)((B - f0) < F ? (B - f0) : F);
+    const int nfr = tile_frames<F>(B, f0);
     const int nrec = nfr * J, npos = 3 * nrec, nang = nfr * nd;
-    f4v *Gi = reinterpret_cast<f4v *>(bw_lds);
-    f4v *A = ROT ? Gi + F * J : Gi;
-    float *P = bw_lds + (ROT ? 8 : 4) * F * J;
-    float *X = P + pad16f((size_t)3 * F * J);
-    f4v *X4 = reinterpret_cast<f4v *>(X);
-    float *after = X + (DOF ? pad16f((size_t)F * nd) : (size_t)4 * F * J);
-    f4v *ntab = reinterpret_cast<f4v *>(after);   // DOF: per joint {axis, lower, upper}
-    GEnt *sch = reinterpret_cast<GEnt *>(after + (DOF ? 4 * J : 0));
-    int *nsib = reinterpret_cast<int *>(sch + T.gsteps * G::L);
+    const BwdImages I(bw_lds, J, F, T.gsteps, DOF, ROT);
+    f4v *Gi = I.G, *A = I.A, *X4 = I.X4;
+    float *P = I.P, *X = I.X;
+    const f4v *ntab = I.ntab;
+    const GEnt *sch = I.sch;
+    const int *nsib = I.nsib;
 
     // every global load of the tile first, then the LDS image
     GroupRows<F> rg, ra, rx;
+    ScalarRows<F> ang;
+    PosRows<F> rp;
     rg.load(g_rot + f0 * J * 4, nrec);
     if (ROT) ra.load(grad_g_rot + f0 * J * 4, nrec);
-    if (!DOF) rx.load(lq_in + f0 * J * 4, nrec);
-    float ang[G::NR];
-    if (DOF) {
-        const float *drow = lq_in + f0 * nd;   // J = 1: no angles, the host passes a readable dummy
-#pragma unroll
-        for (int k = 0; k < G::NR; ++k) {
-            const int i = k * 64 + lane;
-            ang[k] = drow[i < nang ? i : 0];
-        }
-    }
+    if (DOF) ang.load(lq_in + f0 * nd, nang);   // J = 1: no angles, the host passes a readable dummy
+    else rx.load(lq_in + f0 * J * 4, nrec);
     const float *prow = grad_g_pos ? grad_g_pos + f0 * J * 3 : nullptr;
-    const bool paligned = (reinterpret_cast<uintptr_t>(prow) & 15u) == 0;
-    const int n4 = npos >> 2;
-    f4v pv[NP];
-    float ptail = 0.0f;
-    if (prow && paligned) {
-        const f4v *ps = reinterpret_cast<const f4v *>(prow);
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int i = k * 64 + lane;
-            pv[k] = ps[i < n4 ? i : 0];
-        }
-        if (4 * n4 + lane < npos) ptail = prow[4 * n4 + lane];
-    }
-    for (int i = lane; i < T.gsteps * G::L; i += 64) {
-        const GEnt e = T.gsched[i];
-        sch[i] = e;
-        const int j = e.code & 0xFF;
-        if (j != 0xFF) nsib[j] = (e.code >> 24) & 0xFF;
-    }
-    if (DOF) {
-        for (int j = 1 + lane; j < J; j += 64)
-            ntab[j] = f4v{__int_as_float(ld_const(D.axis + (j - 1))), CLIP ? ld_const(D.lower + (j - 1)) : 0.0f,
-                          CLIP ? ld_const(D.upper + (j - 1)) : 0.0f, 0.0f};
-    }
-    rg.to_lds(Gi, nrec);
-    if (ROT) ra.to_lds(A, nrec);
-    if (DOF) {
-#pragma unroll
-        for (int k = 0; k < G::NR; ++k) {
-            const int i = k * 64 + lane;
-            if (i < nang) X[i] = ang[k];
-        }
-    } else {
-        rx.to_lds(X4, nrec);
-    }
+    if (prow) rp.load(prow, npos);
+    group_sched_fill(T, G::L, I.sch, I.nsib);
+    if (DOF) joint_tab_fill<CLIP, false>(D, J, I.ntab);
+    rg.store(Gi, nrec);
+    if (ROT) ra.store(A, nrec);
+    if (DOF) ang.store(X, nang);
+    else rx.store(X4, nrec);
     if (!prow) {
         for (int i = lane; i < npos; i += 64) P[i] = 0.0f;
-    } else if (paligned) {
-        f4v *pd = reinterpret_cast<f4v *>(P);
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int i = k * 64 + lane;
-            if (i < n4) pd[i] = pv[k];
-        }
-        if (4 * n4 + lane < npos) P[4 * n4 + lane] = ptail;
     } else {
-        for (int i = lane; i < npos; i += 64) P[i] = prow[i];
+        rp.to_lds(P, prow, npos);
     }
     wave_sync();
 
@@ -145,34 +110,24 @@ __global__ __launch_bounds__(64) void k_fk_bwd_group(TopoView T, DofView D, cons
         const GEnt e = sch[s * G::L + sub];
         const int j = e.code & 0xFF, p = (e.code >> 8) & 0xFF;
         if (live && j != 0xFF) {
-            f4v a = ROT ? A[base + j] : f4v{0.0f, 0.0f, 0.0f, 0.0f};
-            float *pj = P + 3 * (base + j);
-            V pb{pj[0], pj[1], pj[2]};
-            for (int c = (e.code >> 16) & 0xFF; c != 0xFF; c = nsib[c]) {   // the children, ascending
-                a += A[base + c];
-                const float *pc = P + 3 * (base + c);
-                pb.x += pc[0]; pb.y += pc[1]; pb.z += pc[2];
-            }
-            pj[0] = pb.x; pj[1] = pb.y; pj[2] = pb.z;
+            V pb;
+            const f4v a = child_pull(ROT ? A[base + j] : f4v{0.0f, 0.0f, 0.0f, 0.0f}, A, P, base, j, (e.code >> 16) & 0xFF, nsib, pb);
             if (j == 0) {   // the root is taken as given: its adjoints are the root gradients
                 A[base] = a;
                 if (!DOF) X4[base] = a;
             } else {
-                const f4v gpv = Gi[base + p], gjv = Gi[base + j];
-                const Q Gp{gpv.x, gpv.y, gpv.z, gpv.w}, Gj{gjv.x, gjv.y, gjv.z, gjv.w};
-                const Q gb{a.x, a.y, a.z, a.w};
+                const Q Gp = q_of(Gi[base + p]), Gj = q_of(Gi[base + j]), gb = q_of(a);
                 const V zl{e.lx, e.ly, e.lz};
                 if (DOF) {
                     const f4v t = ntab[j];
                     const AngleRot r = angle_rot<CLIP>(X[fr * nd + j - 1], __float_as_int(t.x), t.y, t.z);
                     const JointAdj o = joint_adjoint(Gp, Gj, angle_quat(r), zl, gb, pb);
-                    A[base + j] = f4v{o.gp.x, o.gp.y, o.gp.z, o.gp.w};
+                    A[base + j] = v_of(o.gp);
                     X[fr * nd + j - 1] = angle_grad(r, o.lqb);
                 } else {
-                    const f4v lv = X4[base + j];
-                    const JointAdj o = joint_adjoint(Gp, Gj, Q{lv.x, lv.y, lv.z, lv.w}, zl, gb, pb);
-                    A[base + j] = f4v{o.gp.x, o.gp.y, o.gp.z, o.gp.w};
-                    X4[base + j] = f4v{o.lqb.x, o.lqb.y, o.lqb.z, o.lqb.w};
+                    const JointAdj o = joint_adjoint(Gp, Gj, q_of(X4[base + j]), zl, gb, pb);
+                    A[base + j] = v_of(o.gp);
+                    X4[base + j] = v_of(o.lqb);
                 }
             }
         }
@@ -181,19 +136,9 @@ __global__ __launch_bounds__(64) void k_fk_bwd_group(TopoView T, DofView D, cons
 
     if (lq_grad) {
         if (DOF) {
-            float *gd = lq_grad + f0 * nd;
-#pragma unroll
-            for (int k = 0; k < G::NR; ++k) {
-                const int i = k * 64 + lane;
-                if (i < nang) gd[i] = X[i];
-            }
+            ScalarRows<F>::copy_out(X, lq_grad + f0 * nd, nang);
         } else {
-            f4v *dst = reinterpret_cast<f4v *>(lq_grad + f0 * J * 4);
-#pragma unroll
-            for (int k = 0; k < G::NR; ++k) {
-                const int rec = k * 64 + lane;
-                if (rec < nrec) st_out(dst + rec, X4[rec]);
-            }
+            GroupRows<F>::copy_out(X4, lq_grad + f0 * J * 4, nrec);
         }
     }
     if (grad_root_rot && lane < nfr) reinterpret_cast<f4v *>(grad_root_rot)[f0 + lane] = A[lane * J];
@@ -271,36 +216,24 @@ hipError_t launch_fk_backward(const TopoView &T, const DofView *D, bool clip, co
                               float *grad_root_rot, float *grad_root_t, hipStream_t s)
 {
     const DofView dv = D ? *D : DofView{nullptr, nullptr, nullptr};
-#define RTG_BWD_ARGS T, dv, lq_in, g_rot, grad_g_rot, grad_g_pos, B
-#define RTG_BWD_OUTS lq_grad, grad_root_rot, grad_root_t
     if (T.gsched) {
         const int F = T.gF;
-        const bool rot = grad_g_rot != nullptr;
-        const size_t lds = sizeof(float) * bwd_group_lds_floats(T.J, F, T.gsteps, D != nullptr, rot);
-        const dim3 g(grid_for(B, F)), b(64);
-#define RTG_BWD_GROUP(DOF, CLIP, ROT, FR) \
-    hipLaunchKernelGGL((k_fk_bwd_group<DOF, CLIP, ROT, FR>), g, b, lds, s, RTG_BWD_ARGS, RTG_BWD_OUTS)
-#define RTG_BWD_GROUP_F(DOF, CLIP, ROT) \
-    do { if (F == 16) RTG_BWD_GROUP(DOF, CLIP, ROT, 16); else RTG_BWD_GROUP(DOF, CLIP, ROT, 8); } while (0)
-#define RTG_BWD_GROUP_R(DOF, CLIP) \
-    do { if (rot) RTG_BWD_GROUP_F(DOF, CLIP, true); else RTG_BWD_GROUP_F(DOF, CLIP, false); } while (0)
-        if (!D) RTG_BWD_GROUP_R(false, false);
-        else if (clip) RTG_BWD_GROUP_R(true, true);
-        else RTG_BWD_GROUP_R(true, false);
-#undef RTG_BWD_GROUP_R
-#undef RTG_BWD_GROUP_F
-#undef RTG_BWD_GROUP
+        const bool dof = D != nullptr, rot = grad_g_rot != nullptr;
+        const size_t lds = sizeof(float) * BwdImages(nullptr, T.J, F, T.gsteps, dof, rot).floats;
+        group_dispatch(F, [&](auto f, auto d, auto c, auto r) {
+            hipLaunchKernelGGL((k_fk_bwd_group<d(), d() && c(), r(), f()>), dim3(grid_for(B, F)), dim3(64), lds, s, T, dv,
+                               lq_in, g_rot, grad_g_rot, grad_g_pos, B, lq_grad, grad_root_rot, grad_root_t);
+        }, dof, clip, rot);
     } else {   // J > kGroupMaxJ: lane walk
         const int fw = bwd_walk_frames(T.J);
         if (fw < 1) return hipErrorInvalidValue;
         const size_t lds = (size_t)28 * T.J * fw;
         const dim3 g(grid_for(B, fw)), b(64);
-        if (!D) hipLaunchKernelGGL((k_fk_bwd_walk<false, false>), g, b, lds, s, RTG_BWD_ARGS, fw, RTG_BWD_OUTS);
-        else if (clip) hipLaunchKernelGGL((k_fk_bwd_walk<true, true>), g, b, lds, s, RTG_BWD_ARGS, fw, RTG_BWD_OUTS);
-        else hipLaunchKernelGGL((k_fk_bwd_walk<true, false>), g, b, lds, s, RTG_BWD_ARGS, fw, RTG_BWD_OUTS);
+        dispatch_bools([&](auto d, auto c) {
+            hipLaunchKernelGGL((k_fk_bwd_walk<d(), d() && c()>), g, b, lds, s, T, dv, lq_in, g_rot, grad_g_rot, grad_g_pos,
+                               B, fw, lq_grad, grad_root_rot, grad_root_t);
+        }, D != nullptr, clip);
     }
-#undef RTG_BWD_ARGS
-#undef RTG_BWD_OUTS
     return hipGetLastError();
 }
 

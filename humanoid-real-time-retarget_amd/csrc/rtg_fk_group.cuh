@@ -1,8 +1,14 @@
-// rtg_fk_group.cuh -- the lane-group helpers shared by the forward kinematics kernels (rtg_fk.hip) and their
-// adjoints (rtg_fk_grad.hip): a tile is one wave, F frames, 64 / F lanes per frame, rows moved as 1 KiB pieces
-// through an LDS image (see the layout comment in rtg_fk.hip).
+// rtg_fk_group.cuh -- the lane-group tile kit shared by the forward kinematics kernels (rtg_fk.hip), their adjoints
+// (rtg_fk_grad.hip), the keypoint fit (rtg_dof_fit.hip) and retarget_to (rtg_retarget_to.hip): a tile is one wave, F
+// frames, 64 / F lanes per frame, rows moved as 1 KiB pieces through LDS images (the layout comment in rtg_fk.hip).
+// The parts: the LDS carve (LdsCarve: a kernel and its launcher call the same carve function), the row movers
+// (LaneRows as GroupRows: float4 records, and ScalarRows: scalars; PosRows: position rows), the table fills, the root preset, the
+// reverse sweep's child pull, the item split, the Q <-> f4v converters, the straight-through clamp and the launch
+// dispatch.  The multi-wave tile of rtg_rot_ingest.hip takes only the converters and the item split.
 #pragma once
 #include "rtg_device.cuh"
+
+#include <type_traits>
 
 namespace rtg {
 
@@ -19,6 +25,8 @@ RTG_DEV void wave_sync()
 }
 
 typedef float f4v __attribute__((ext_vector_type(4)));
+RTG_DEV Q q_of(f4v v) { return Q{v.x, v.y, v.z, v.w}; }
+RTG_DEV f4v v_of(Q q) { return f4v{q.x, q.y, q.z, q.w}; }
 // the lane-group tiles' output pieces (whole 1 KiB wave stores): non-temporal (RTG_FK_NT_OUT): never read back here,
 // they would only evict the rows still to be read from the L2
 RTG_DEV void st_out(f4v *p, f4v v)
@@ -33,18 +41,148 @@ struct Grp {
     static constexpr int L = 64 / F;             // lanes per frame
     static constexpr int LOG_L = F == 16 ? 2 : 3;
     static constexpr int NR = F == 16 ? 9 : 8;   // records per lane: F J <= 64 NR (group_frames)
+    static constexpr int NP = (3 * NR + 3) / 4;  // float4 pieces per lane of a tile's position rows
 };
+// the frames of the tile that starts at frame f0 (the last tile of a batch is ragged)
+template <int F>
+RTG_DEV int tile_frames(int64_t B, int64_t f0) { return (int)((B - f0) < F ? (B - f0) : F); }
+
 // the near-unit normalisation table (rtg_math.cuh) in the lane-group tiles' LDS, when any of them uses it
 constexpr bool kUnitTab = RTG_FK_UNIT_TAB || RTG_DOF_UNIT_TAB;
-constexpr size_t kUnitTabFloats = kUnitTab ? 4 * (2 * kUnitTabK + 1) : 0;
+constexpr size_t kUnitTabEnts = kUnitTab ? 2 * kUnitTabK + 1 : 0;
 RTG_DEV Q qmul_norm_tab(Q a, Q b, const UnitEnt *tab)
 {
     if (!RTG_FK_UNIT_TAB) return qmul_norm(a, b);
     return qnormalize_t(qmul(a, b), tab);
 }
 
-__host__ __device__ inline size_t pad16f(size_t nfloats) { return (nfloats + 3) & ~(size_t)3; }
+// item i of a tile's (frame, joint) items, J per frame: i / J as ((i + 1/2) / J) truncated with rJ = item_rcp(J),
+// exact for i < 2^12, J <= 64
+RTG_DEV float item_rcp(int J) { return 1.0f / (float)J; }
+struct Item {
+    int fr, j;
+};
+RTG_DEV Item item_split(int i, float rJ, int J)
+{
+    const int fr = (int)(((float)i + 0.5f) * rJ);
+    return Item{fr, i - fr * J};
+}
 
+// torch.clamp (min then max; NaN passes), then the straight-through sum (hu_forward_model.py:20-22)
+RTG_DEV float clamp_st(float a, float lo, float hi)
+{
+    float c = a < lo ? lo : a;
+    c = c > hi ? hi : c;
+    return (c - a) + a;
+}
+
+// ---------------------------------------------------------------------------------------------------- the LDS carve
+// A kernel's images are taken in order from its dynamic LDS, each starting 16-byte aligned.  One carve per kernel does
+// it, the constructor of its *Images struct: the kernel calls it on the real base and uses the pointers, its launcher
+// calls it on a null base and asks for `floats` of dynamic LDS.
+__host__ __device__ inline size_t pad16f(size_t nfloats) { return (nfloats + 3) & ~(size_t)3; }
+struct LdsCarve {
+    float *base;
+    size_t floats = 0;
+    __host__ __device__ explicit LdsCarve(float *b) : base(b) {}
+    template <typename T>
+    __host__ __device__ T *take(size_t n)
+    {
+        static_assert(sizeof(T) % sizeof(float) == 0, "images of whole floats");
+        T *p = base ? reinterpret_cast<T *>(base + floats) : nullptr;
+        floats += pad16f(n * (sizeof(T) / sizeof(float)));
+        return p;
+    }
+    __host__ __device__ UnitEnt *take_unit_tab() { return take<UnitEnt>(kUnitTabEnts); }
+};
+
+// ---------------------------------------------------------------------------------------------------- row movers
+// f(k, i) for a lane's N items i = 64 k + lane: one 64-item piece per k, consecutive lanes on consecutive items
+template <int N, typename Fn>
+RTG_DEV void lane_items(const Fn &f)
+{
+#pragma unroll
+    for (int k = 0; k < N; ++k) f(k, k * 64 + (int)threadIdx.x);
+}
+RTG_DEV void st_out(float *p, float v) { *p = v; }
+
+// N items per lane of n consecutive Ts, global rows or an LDS image.  `load` is unconditional (a lane past the rows
+// re-reads element 0), so no branch separates the loads and all are in flight; `store` into an LDS image comes after
+// the caller's other loads; `out` writes output rows (st_out).  `copy_out` moves an image out item by item: for rows
+// that leave long after the tile's loads, where the clamped indices of a second `load` would stay live in between.
+template <typename T, int N>
+struct LaneRows {
+    T v[N];
+    RTG_DEV void load(const void *rows, int n)
+    {
+        const T *s = static_cast<const T *>(rows);
+        lane_items<N>([&](int k, int i) { v[k] = s[i < n ? i : 0]; });
+    }
+    RTG_DEV void store(T *img, int n) const
+    {
+        lane_items<N>([&](int k, int i) { if (i < n) img[i] = v[k]; });
+    }
+    RTG_DEV void out(void *rows, int n) const
+    {
+        T *d = static_cast<T *>(rows);
+        lane_items<N>([&](int k, int i) { if (i < n) st_out(d + i, v[k]); });
+    }
+    RTG_DEV static void copy_out(const T *img, void *rows, int n)
+    {
+        T *d = static_cast<T *>(rows);
+        lane_items<N>([&](int, int i) { if (i < n) st_out(d + i, img[i]); });
+    }
+};
+template <int F>
+using GroupRows = LaneRows<f4v, Grp<F>::NR>;    // the tile's float4 records
+template <int F>
+using ScalarRows = LaneRows<float, Grp<F>::NR>;   // the joint angles, the Adam moments, the gradient rows
+
+// the tile's position rows (npos = 3 nrec floats): consecutive dwordx4 pieces and a dword tail when the rows are
+// 16-byte aligned, dword by dword at any other alignment
+template <int F>
+struct PosRows {
+    f4v v[Grp<F>::NP];
+    float tail;
+    bool aligned;
+    RTG_DEV void load(const float *__restrict__ rows, int npos)
+    {
+        const int lane = (int)threadIdx.x, n4 = npos >> 2;
+        aligned = (reinterpret_cast<uintptr_t>(rows) & 15u) == 0;
+        tail = 0.0f;
+        if (!aligned) return;   // to_lds copies dword by dword
+        const f4v *src = reinterpret_cast<const f4v *>(rows);
+        // (a lone one-joint frame has no whole piece to re-read)
+        if (n4 > 0) lane_items<Grp<F>::NP>([&](int k, int i) { v[k] = src[i < n4 ? i : 0]; });
+        if (4 * n4 + lane < npos) tail = rows[4 * n4 + lane];
+    }
+    RTG_DEV void to_lds(float *img, const float *__restrict__ rows, int npos) const
+    {
+        const int lane = (int)threadIdx.x, n4 = npos >> 2;
+        if (aligned) {
+            f4v *d = reinterpret_cast<f4v *>(img);
+            lane_items<Grp<F>::NP>([&](int k, int i) { if (i < n4) d[i] = v[k]; });
+            if (4 * n4 + lane < npos) img[4 * n4 + lane] = tail;
+        } else {
+            for (int i = lane; i < npos; i += 64) img[i] = rows[i];
+        }
+    }
+    RTG_DEV static void out(const float *img, float *__restrict__ rows, int npos)   // the image out (st_out pieces)
+    {
+        const int lane = (int)threadIdx.x;
+        if ((reinterpret_cast<uintptr_t>(rows) & 15u) == 0) {
+            const int n4 = npos >> 2;
+            f4v *pd = reinterpret_cast<f4v *>(rows);
+            const f4v *ps = reinterpret_cast<const f4v *>(img);
+            for (int i = lane; i < n4; i += 64) st_out(pd + i, ps[i]);
+            for (int i = 4 * n4 + lane; i < npos; i += 64) rows[i] = img[i];
+        } else {
+            for (int i = lane; i < npos; i += 64) rows[i] = img[i];
+        }
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------- fills
 // the tile's schedule into LDS (float4 copies, in flight with the tile's own loads)
 RTG_DEV void group_sched_fill(const TopoView &T, int L, GEnt *sch)
 {
@@ -53,29 +191,89 @@ RTG_DEV void group_sched_fill(const TopoView &T, int L, GEnt *sch)
     f4v *d = reinterpret_cast<f4v *>(sch);
     for (int i = (int)threadIdx.x; i < n; i += 64) d[i] = gs[i];
 }
+// the same with the next-sibling table of the reverse sweep (child_pull), from the entries' codes
+RTG_DEV void group_sched_fill(const TopoView &T, int L, GEnt *sch, int *nsib)
+{
+    const f4v *gs = reinterpret_cast<const f4v *>(T.gsched);
+    f4v *d = reinterpret_cast<f4v *>(sch);
+    for (int i = (int)threadIdx.x; i < T.gsteps * L; i += 64) {
+        const f4v lo = gs[2 * i], hi = gs[2 * i + 1];   // {lx, ly, lz, code}, the tree quaternion
+        d[2 * i] = lo;
+        d[2 * i + 1] = hi;
+        const int code = __float_as_int(lo.w), j = code & 0xFF;
+        if (j != 0xFF) nsib[j] = (code >> 24) & 0xFF;
+    }
+}
 
-// the tile's NR records per lane, all loads in flight (unconditional: a lane past the tile re-reads record 0, so no
-// branch separates them), then -- after the caller's other loads -- into the LDS image
-template <int F>
-struct GroupRows {
-    f4v v[Grp<F>::NR];
-    RTG_DEV void load(const float *__restrict__ rows, int nrec)
-    {
-        const f4v *src = reinterpret_cast<const f4v *>(rows);
-#pragma unroll
-        for (int k = 0; k < Grp<F>::NR; ++k) {
-            const int rec = k * 64 + (int)threadIdx.x;
-            v[k] = src[rec < nrec ? rec : 0];
-        }
+// the joint-angle model's per-joint table {axis, lower, upper, weight}: joints 1 .. J - 1, and with WEIGHT the root's
+// weight too (weight == nullptr: ones)
+template <bool CLIP, bool WEIGHT>
+RTG_DEV void joint_tab_fill(const DofView &D, int J, f4v *tab, const float *weight = nullptr)
+{
+    for (int j = (WEIGHT ? 0 : 1) + (int)threadIdx.x; j < J; j += 64) {
+        const float w = !WEIGHT ? 0.0f : (weight ? ld_const(weight + j) : 1.0f);
+        tab[j] = WEIGHT && j == 0
+                     ? f4v{0.0f, 0.0f, 0.0f, w}
+                     : f4v{__int_as_float(ld_const(D.axis + (j - 1))), CLIP ? ld_const(D.lower + (j - 1)) : 0.0f,
+                           CLIP ? ld_const(D.upper + (j - 1)) : 0.0f, w};
     }
-    RTG_DEV void to_lds(f4v *rot, int nrec) const
-    {
-#pragma unroll
-        for (int k = 0; k < Grp<F>::NR; ++k) {
-            const int rec = k * 64 + (int)threadIdx.x;
-            if (rec < nrec) rot[rec] = v[k];
-        }
+}
+
+// the tile's roots.  Lane l loads frame l's root rotation and float l of the root translations (a lane past them
+// re-reads element 0); root_preset puts them into the images' root rows: position = the root translation
+// (kinematics.py:27-29), global = the root rotation as given (hu_forward_model.py:24)
+RTG_DEV f4v root_rot_load(const float *__restrict__ root_rot, int64_t f0, int nfr)
+{
+    return reinterpret_cast<const f4v *>(root_rot)[f0 + ((int)threadIdx.x < nfr ? (int)threadIdx.x : 0)];
+}
+RTG_DEV float root_t_load(const float *__restrict__ root_t, int64_t f0, int nfr)
+{
+    return root_t[f0 * 3 + ((int)threadIdx.x < 3 * nfr ? (int)threadIdx.x : 0)];
+}
+RTG_DEV void root_preset(float *pos, int J, int nfr, float rt)
+{
+    const int lane = (int)threadIdx.x, fr = lane / 3;
+    if (lane < 3 * nfr) pos[3 * J * fr + (lane - 3 * fr)] = rt;
+}
+RTG_DEV void root_preset(f4v *rot, float *pos, int J, int nfr, f4v rr, float rt)
+{
+    if ((int)threadIdx.x < nfr) rot[(int)threadIdx.x * J] = rr;
+    root_preset(pos, J, nfr, rt);
+}
+
+// The reverse sweep's pull: joint j (rows at base + j) adds its children's rows in ascending index order (the first
+// child from the entry's code, then the next-sibling table), so every sum has one fixed order whatever the
+// schedule.  Returns a plus the children's rotation-adjoint rows of A; writes the summed position adjoint to P's row
+// j and returns it in pb.
+RTG_DEV f4v child_pull(f4v a, const f4v *A, float *P, int base, int j, int first_child, const int *nsib, V &pb)
+{
+    float *pj = P + 3 * (base + j);
+    pb = V{pj[0], pj[1], pj[2]};
+    for (int c = first_child; c != 0xFF; c = nsib[c]) {
+        a += A[base + c];
+        const float *pc = P + 3 * (base + c);
+        pb.x += pc[0]; pb.y += pc[1]; pb.z += pc[2];
     }
-};
+    pj[0] = pb.x; pj[1] = pb.y; pj[2] = pb.z;
+    return a;
+}
+
+// ---------------------------------------------------------------------------------------------------- launch dispatch
+// run-time bools, and the run-time F, as compile-time arguments: fn(std::integral_constant<int, F>{},
+// std::bool_constant<b0>{}, ...)
+template <typename Fn>
+inline void dispatch_bools(Fn &&fn) { fn(); }
+template <typename Fn, typename... B>
+inline void dispatch_bools(Fn &&fn, bool b, B... rest)
+{
+    if (b) dispatch_bools([&](auto... c) { fn(std::true_type{}, c...); }, rest...);
+    else dispatch_bools([&](auto... c) { fn(std::false_type{}, c...); }, rest...);
+}
+template <typename Fn, typename... B>
+inline void group_dispatch(int F, Fn &&fn, B... bools)
+{
+    if (F == 16) dispatch_bools([&](auto... c) { fn(std::integral_constant<int, 16>{}, c...); }, bools...);
+    else dispatch_bools([&](auto... c) { fn(std::integral_constant<int, 8>{}, c...); }, bools...);
+}
 
 }  // namespace rtg

@@ -8,7 +8,7 @@
 
 namespace rtg {
 
-// One (step, sub-lane) entry of the lane-group FK schedule (fk_group_schedule, rtg_fk.hip): at step s, sub-lane u of
+// One (step, sub-lane) entry of the lane-group FK schedule (group_list_schedule, rtg_group_sched.h): at step s, sub-lane u of
 // every frame's lane group composes joint `code & 0xFF` (0xFF: idle) from its parent `(code >> 8) & 0xFF`, with that
 // joint's zero-pose local translation and tree quaternion alongside (two ds_read_b128 per step).  The upper half of
 // `code` links the joint's children for the reverse sweep (rtg_fk_grad.hip): `(code >> 16) & 0xFF` its first child,
@@ -32,7 +32,7 @@ struct TopoView {
 };
 // the lane-group frames per wave for J joints (0: J too large, the lane-walk kernels run); F J <= 64 * 9 records
 inline int group_frames(int J) { return J <= RTG_FK_F16_MAXJ ? 16 : (J <= kGroupMaxJ ? 8 : 0); }
-// fills `out` (steps x (64 / F) entries) and returns the step count
+// a topology's schedule entries (rtg_fk.hip): fills `out` (steps x (64 / F) entries) and returns the step count
 int32_t fk_group_schedule(const int32_t *parents, const V *local_t, const Q *tree_quat, int32_t J, int32_t F,
                           GEnt *out, int32_t max_steps);
 

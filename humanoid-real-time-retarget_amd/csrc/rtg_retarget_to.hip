@@ -21,15 +21,14 @@
 // A tile is one wave and F frames (group_frames(max(Js, Jt))), 64 / F lanes per frame.  The source rows come in as
 // coalesced 1 KiB pieces into an LDS image, all loads in flight; stages 1 and 6 run the schedules' steps on the
 // frame's lane group, the other stages have no chain and spread their (frame, joint) items over the wave; the output
-// rows leave as whole-wave non-temporal stores.  LDS: image [F Js] | reduced rows [F K] (float4 each: the stage-3..6
-// rows overlay the image, dead after stage 2; stage 8's rows are stage 7's, indexed through src_of) | the plan's
-// blob (schedules, constants, index tables) | the near-unit table.  Each joint is composed by the device functions the
+// rows leave as whole-wave non-temporal stores.  LDS: RetargetImages below (the stage-3..6 rows overlay the image, dead
+// after stage 2; stage 8's rows are stage 7's, indexed through src_of; the blob holds the schedules, constants and
+// index tables).  Each joint is composed by the device functions the
 // FK kernels use (qmul_norm through the near-unit table, qnormalize, qrotate) with the reference's operands in the
 // reference's order, so the bits do not depend on the schedule or on which lane does what.
 #include "rtg_device.cuh"
 #include "rtg_fk_group.cuh"
-
-#include <algorithm>
+#include "rtg_group_sched.h"
 
 namespace rtg {
 
@@ -38,8 +37,6 @@ RTG_DEV Q qnorm_tab(Q q, const UnitEnt *tab)
     if (!RTG_FK_UNIT_TAB) return qnormalize(q);
     return qnormalize_t(q, tab);
 }
-RTG_DEV Q q_of(f4v v) { return Q{v.x, v.y, v.z, v.w}; }
-RTG_DEV f4v v_of(Q q) { return f4v{q.x, q.y, q.z, q.w}; }
 
 // a list schedule's steps on the rotations alone: joint j's row becomes qmul_norm(parent's global row,
 // qmul_norm(tree quaternion, row)) (:416-422); the root's row is its global rotation already and has no entry
@@ -62,10 +59,22 @@ RTG_DEV void rot_compose(f4v *img, int stride, const GEnt *sch, int steps, int n
     }
 }
 
-__host__ __device__ inline size_t retarget_lds_floats(const RetargetView &P)
-{
-    return 4 * ((size_t)P.F * P.Js + (size_t)P.F * P.K + (size_t)P.n16) + kUnitTabFloats;
-}
+struct RetargetImages {
+    f4v *img;        // [F Js] the source rows; dead after stage 2, its rows [F K] then take stages 3-6
+    f4v *red;        // [F K] the reduced rows
+    f4v *tab;        // [n16] the plan's blob
+    UnitEnt *utab;   // the near-unit table
+    size_t floats;
+    __host__ __device__ RetargetImages(float *base, const RetargetView &P)
+    {
+        LdsCarve c(base);
+        img = c.take<f4v>((size_t)P.F * P.Js);
+        red = c.take<f4v>((size_t)P.F * P.K);
+        tab = c.take<f4v>(P.n16);
+        utab = c.take_unit_tab();
+        floats = c.floats;
+    }
+};
 
 template <bool LOCAL_IN, int F>
 __global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const float *__restrict__ src_rot,
@@ -78,16 +87,15 @@ __global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const flo
     const int lane = (int)threadIdx.x;
     const int Js = P.Js, Jt = P.Jt, K = P.K;
     const int64_t f0 = (int64_t)blockIdx.x * F;
-    const int nfr = (int)((B - f0) < F ? (B - f0) : F);
-    f4v *img = reinterpret_cast<f4v *>(rt_lds);
-    f4v *red = img + F * Js;
-    f4v *tab = red + F * K;
+    const int nfr = tile_frames<F>(B, f0);
+    const RetargetImages I(rt_lds, P);
+    f4v *img = I.img, *red = I.red, *tab = I.tab;
     const GEnt *sch1 = reinterpret_cast<const GEnt *>(tab);
     const GEnt *sch6 = reinterpret_cast<const GEnt *>(tab + P.o_sch6);
     const f4v *cg = tab + P.o_cg, *tg = tab + P.o_tg, *ttqn = tab + P.o_ttq;
     const int *kept = reinterpret_cast<const int *>(tab + P.o_int);
     const int *spar = kept + K, *perm = spar + K, *src_of = perm + K, *tpar = src_of + Jt;
-    UnitEnt *utab = reinterpret_cast<UnitEnt *>(tab + P.n16);
+    UnitEnt *utab = I.utab;
 
     // the tile's rows and root translations, all loads in flight; the plan's blob and the near-unit table meanwhile
     GroupRows<F> rows;
@@ -103,22 +111,22 @@ __global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const flo
         }
     }
     if (kUnitTab) unit_tab_fill(utab, lane);
-    rows.to_lds(img, nfr * Js);
+    rows.store(img, nfr * Js);
     wave_sync();
 
     if (LOCAL_IN) rot_compose<F>(img, Js, sch1, P.steps1, nfr, utab);   // stage 1
 
     const int nk = nfr * K;
-    const float rK = 1.0f / (float)K;   // i / K as ((i + 1/2) / K) truncated: exact for i < 2^12, K <= 64
+    const float rK = item_rcp(K);
     for (int i = lane; i < nk; i += 64) {   // stage 2
-        const int fr = (int)(((float)i + 0.5f) * rK), k = i - fr * K;
-        red[i] = v_of(qnorm_tab(q_of(img[fr * Js + kept[k]]), utab));
+        const Item it = item_split(i, rK, K);
+        red[i] = v_of(qnorm_tab(q_of(img[it.fr * Js + kept[it.j]]), utab));
     }
     wave_sync();   // the image is dead from here: rows [F K] of it take stages 3-6
     const Q cid = qnormalize(qconj(qident()));   // S_red's tree quaternions are identities (:259, :477-481)
     for (int i = lane; i < nk; i += 64) {   // stages 3-5
-        const int fr = (int)(((float)i + 0.5f) * rK), k = i - fr * K;
-        const int ks = perm[k];
+        const Item it = item_split(i, rK, K);
+        const int fr = it.fr, k = it.j, ks = perm[k];
         const Q g = q_of(red[fr * K + ks]);
         Q l = g;   // S_red's root copied (:470)
         if (ks > 0) {
@@ -146,7 +154,7 @@ __global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const flo
     }
 
     for (int i = lane; i < nk; i += 64) {   // stage 7, and stage 8's normalisation (the same for every j it serves)
-        const int fr = (int)(((float)i + 0.5f) * rK), k = i - fr * K;
+        const int k = item_split(i, rK, K).j;
         const Q d = qmul_norm_tab(q_of(img[i]), q_of(cg[k]), utab);
         const Q n = qmul_norm_tab(d, q_of(tg[k]), utab);
         red[i] = v_of(qnorm_tab(n, utab));
@@ -160,13 +168,14 @@ __global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const flo
         o[2] = P.tgt_root.z + (tr.z - P.t_tp.z) * P.scale;
     }
     const int nrec = nfr * Jt;
-    const float rJ = 1.0f / (float)Jt;
+    const float rJ = item_rcp(Jt);
     f4v *dst = reinterpret_cast<f4v *>(out_rot + f0 * Jt * 4);
 #pragma unroll 3
     for (int k = 0; k < G::NR; ++k) {   // stages 8-9, record-ordered: whole-wave stores
         const int rec = k * 64 + lane;
         if (rec < nrec) {
-            const int fr = (int)(((float)rec + 0.5f) * rJ), j = rec - fr * Jt;
+            const Item it = item_split(rec, rJ, Jt);
+            const int fr = it.fr, j = it.j;
             const Q o = q_of(red[fr * K + src_of[j]]);
             Q q = o;   // T's root copied (:470)
             if (j > 0) {
@@ -243,39 +252,15 @@ bool retarget_tables(const int32_t *sp, int32_t Js, const int32_t *tp, int32_t J
     return true;
 }
 
-// List schedule of the joints j > 0 with inc[j] (an ancestor-closed set) on L lanes: a joint is ready once its parent's
-// step is past (the root needs none); each step takes up to L ready joints, longest remaining chain first, ties by
-// index (fk_group_schedule's rule).  Returns the step count.
-static int list_schedule(const int32_t *par, int J, const std::vector<char> &inc, int L, const Q *tq,
-                         std::vector<GEnt> &out)
+// a list schedule's entries for rot_compose: joint, parent and the joint's tree quaternion (no child links)
+static int rot_schedule(const int32_t *par, int J, const char *inc, int L, const Q *tq, std::vector<GEnt> &out)
 {
-    std::vector<int> h(J, 1), done(J, -2);
-    done[0] = -1;
-    int todo = 0;
-    for (int j = J - 1; j > 0; --j)
-        if (inc[j]) {
-            h[par[j]] = std::max(h[par[j]], h[j] + 1);
-            ++todo;
-        }
-    int steps = 0, placed = 0;
-    std::vector<int> ready;
-    while (placed < todo) {
-        ready.clear();
-        for (int j = 1; j < J; ++j)
-            if (inc[j] && done[j] == -2 && done[par[j]] != -2 && done[par[j]] < steps) ready.push_back(j);
-        std::stable_sort(ready.begin(), ready.end(), [&](int a, int b) { return h[a] > h[b]; });
-        for (int u = 0; u < L; ++u) {
-            GEnt e{0.f, 0.f, 0.f, 0xFFFF, 0.f, 0.f, 0.f, 1.f};
-            if (u < (int)ready.size()) {
-                const int j = ready[u];
-                done[j] = steps;
-                ++placed;
-                e = GEnt{0.f, 0.f, 0.f, (int32_t)((uint32_t)j | ((uint32_t)par[j] << 8)), tq[j].x, tq[j].y, tq[j].z, tq[j].w};
-            }
-            out.push_back(e);
-        }
-        ++steps;
-    }
+    std::vector<int> order;
+    const int steps = group_list_schedule(par, J, inc, false, L, J, order);
+    for (const int j : order)
+        out.push_back(j < 0 ? GEnt{0.f, 0.f, 0.f, 0xFFFF, 0.f, 0.f, 0.f, 1.f}
+                            : GEnt{0.f, 0.f, 0.f, (int32_t)((uint32_t)j | ((uint32_t)par[j] << 8)), tq[j].x, tq[j].y,
+                                   tq[j].z, tq[j].w});
     return steps;
 }
 
@@ -288,9 +273,9 @@ void retarget_blob(const RetargetTables &T, const int32_t *sp, const Q *stq, con
     for (int k = 0; k < K; ++k)
         for (int a = T.kept_s[k]; a != -1 && !inc[a]; a = sp[a]) inc[a] = 1;
     std::vector<GEnt> s1, s6;
-    const int steps1 = list_schedule(sp, Js, inc, L, stq, s1);
+    const int steps1 = rot_schedule(sp, Js, inc.data(), L, stq, s1);
     const std::vector<Q> ident(K, Q{0.f, 0.f, 0.f, 1.f});
-    const int steps6 = list_schedule(T.tred_par.data(), K, std::vector<char>(K, 1), L, ident.data(), s6);
+    const int steps6 = rot_schedule(T.tred_par.data(), K, nullptr, L, ident.data(), s6);
     V_.Js = Js, V_.Jt = Jt, V_.K = K, V_.F = F, V_.steps1 = steps1, V_.steps6 = steps6;
     V_.o_sch6 = 2 * (int)s1.size();
     V_.o_cg = V_.o_sch6 + 2 * (int)s6.size();
@@ -311,15 +296,11 @@ void retarget_blob(const RetargetTables &T, const int32_t *sp, const Q *stq, con
 hipError_t launch_retarget_to(const RetargetView &P, bool local_in, const float *rot, const float *root_t, int64_t B,
                               float *out_rot, float *out_root_t, float *dump, hipStream_t s)
 {
-    const size_t lds = sizeof(float) * retarget_lds_floats(P);
-    const dim3 g(grid_for(B, P.F)), b(64);
-    if (P.F == 16) {
-        if (local_in) hipLaunchKernelGGL((k_retarget_to<true, 16>), g, b, lds, s, P, rot, root_t, B, out_rot, out_root_t, dump);
-        else hipLaunchKernelGGL((k_retarget_to<false, 16>), g, b, lds, s, P, rot, root_t, B, out_rot, out_root_t, dump);
-    } else {
-        if (local_in) hipLaunchKernelGGL((k_retarget_to<true, 8>), g, b, lds, s, P, rot, root_t, B, out_rot, out_root_t, dump);
-        else hipLaunchKernelGGL((k_retarget_to<false, 8>), g, b, lds, s, P, rot, root_t, B, out_rot, out_root_t, dump);
-    }
+    const size_t lds = sizeof(float) * RetargetImages(nullptr, P).floats;
+    group_dispatch(P.F, [&](auto f, auto li) {
+        hipLaunchKernelGGL((k_retarget_to<li(), f()>), dim3(grid_for(B, P.F)), dim3(64), lds, s, P, rot, root_t, B, out_rot,
+                           out_root_t, dump);
+    }, local_in);
     return hipGetLastError();
 }
 

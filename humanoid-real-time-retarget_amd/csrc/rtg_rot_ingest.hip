@@ -23,8 +23,6 @@
 
 namespace rtg {
 
-RTG_DEV Q rq_of(f4v v) { return Q{v.x, v.y, v.z, v.w}; }
-
 // qmul_norm_tab for N pairs: one rare-case branch for the group
 template <int N>
 RTG_DEV void qmul_norm_tab_n(const Q (&a)[N], const Q (&b)[N], const UnitEnt *tab, Q (&out)[N])
@@ -57,10 +55,10 @@ RTG_DEV void rot_items(const RotItems &P, int tid, Q (&r)[4])
     for (int u = 0; u < N; ++u) {
         int i = u * NT + tid;
         i = i < P.nit ? i : 0;   // a lane past the tile repeats item 0
-        const int fr = (int)(((float)i + 0.5f) * P.rJ), j = i - fr * P.Jo;
-        a[u] = rq_of(P.img[fr * P.Ji + P.srcj[j]]);
+        const Item it = item_split(i, P.rJ, P.Jo);
+        a[u] = q_of(P.img[it.fr * P.Ji + P.srcj[it.j]]);
         b[u] = P.pre;
-        m[u] = rq_of(P.post[j]);
+        m[u] = q_of(P.post[it.j]);
     }
     qmul_norm_tab_n<N>(a, b, P.utab, o);
     qmul_norm_tab_n<N>(o, m, P.utab, a);
@@ -105,8 +103,8 @@ __global__ __launch_bounds__(16 * T, 4) void k_rot_ingest(RotIngestView P, const
     __syncthreads();
 
     const int nit = nfr * Jo;
-    const float rJ = 1.0f / (float)Jo;   // i / J as ((i + 1/2) / J) truncated: exact for i < 2^12, J <= 64
-    const Q pre = rq_of(cst[0]);
+    const float rJ = item_rcp(Jo);
+    const Q pre = q_of(cst[0]);
     const f4v *post = cst + 1;
     const int *srcj = reinterpret_cast<const int *>(cst + P.o_src);
     const UnitEnt *utab = reinterpret_cast<const UnitEnt *>(cst + P.o_tab);
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(16 * T, 4) void k_rot_ingest(RotIngestView P, const
 #pragma unroll
         for (int k = 0; k < NR; ++k) {
             const int i = k * NT + tid;
-            if (i < nit) dst[i] = f4v{r[k].x, r[k].y, r[k].z, r[k].w};
+            if (i < nit) dst[i] = v_of(r[k]);
         }
     } else {
         const int RS = 4 * Jo + 1;
@@ -135,8 +133,8 @@ __global__ __launch_bounds__(16 * T, 4) void k_rot_ingest(RotIngestView P, const
         for (int k = 0; k < NR; ++k) {
             const int i = k * NT + tid;
             if (i < nit) {
-                const int fr = (int)(((float)i + 0.5f) * rJ), j = i - fr * Jo;
-                float *d = res + fr * RS + 4 * j;
+                const Item it = item_split(i, rJ, Jo);
+                float *d = res + it.fr * RS + 4 * it.j;
                 d[0] = r[k].x, d[1] = r[k].y, d[2] = r[k].z, d[3] = r[k].w;
             }
         }

@@ -454,3 +454,34 @@ def test_a_bad_frame_stays_its_own(gpu):
         if not np.isnan(want[0]):   # a zero root rotation: every joint at the root translation, a finite loss -- a
             # sum of 99 non-negative float32 terms, each a few roundings: well within 1e-5 relative
             assert abs(bad0["loss"][f] - want[0]) <= 1e-5 * abs(want[0])
+
+
+@pytest.mark.parametrize("name", ["hu33", "tree37"])
+@pytest.mark.parametrize("iters", [0, 3])
+def test_targets_at_any_alignment(gpu, name, iters):
+    """target_pos 4 bytes into its buffer: the target rows then come in dword by dword instead of as dwordx4 pieces,
+    and loss and gradient (iters = 0), angles and moments (iters = 3) keep the bits of the aligned call.  One whole
+    tile plus a one-frame tile of both lane-group shapes."""
+    from rtg import _lib
+    from rtg.runtime import ptr
+    s = skel(name)
+    B, n = s.F + 1, s.J - 1
+    x = inputs(s, B, True, 7000 + s.J + iters)
+    aligned = _dev(x["tgt"])
+    buf = torch.empty(x["tgt"].size + 1, dtype=torch.float32, device="cuda")
+    shifted = buf[1:].view(x["tgt"].shape)
+    shifted.copy_(aligned)
+    assert aligned.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 == 4
+
+    def run(tp):
+        w, rr, rt, dof = _dev(x["w"]), _dev(x["rr"]), _dev(x["rt"]), _dev(x["dof"])
+        m, v = torch.zeros((B, n), device="cuda"), torch.zeros((B, n), device="cuda")
+        out = {k: torch.full(sh, 7.0, device="cuda") for k, sh in (("dof", (B, n)), ("loss", (B,)), ("grad", (B, n)))}
+        rc = _lib.lib().rtg_dof_fit_f32(s.model.handle, ptr(tp), ptr(w), ptr(rr), ptr(rt), ptr(dof), B, 1, iters, LR, B1,
+                                        B2, EPS, 0, ptr(m), ptr(v), ptr(out["dof"]), ptr(out["loss"]), ptr(out["grad"]),
+                                        None)
+        assert rc == 0, _lib.lib().rtg_last_error()
+        torch.cuda.synchronize()
+        return dict({k: _np(t) for k, t in out.items()}, m=_np(m), v=_np(v))
+
+    assert_same_bits(run(aligned), run(shifted), f"{name} iters={iters}")

@@ -340,3 +340,60 @@ def test_dof_fk_lane_walk_forward_vs_oracle(gpu, J):
         ogr, ogp = orc.dof_fk(par, lt, axis, dof, rr, rt, lo if clip else None, hi if clip else None)
         np.testing.assert_array_equal(_np(gr), ogr)
         np.testing.assert_array_equal(_np(gp), ogp)
+
+
+def _offset4(x):
+    """A device copy of x that starts 4 bytes into its buffer: its rows are not 16-byte aligned."""
+    buf = torch.empty(x.size + 1, dtype=torch.float32, device="cuda")
+    view = buf[1:].view(x.shape)
+    view.copy_(torch.as_tensor(x))
+    assert view.data_ptr() % 16 == 4
+    return view
+
+
+@pytest.mark.parametrize("kind,J,Bs", [("hu", 33, (17,)), ("bushy", 37, (9,)), ("chain", 1, (1, 17))])
+def test_position_cotangent_at_any_alignment(gpu, hu_clip, kind, J, Bs):
+    """grad_g_pos 4 bytes into its buffer: the position rows then come in dword by dword instead of as dwordx4 pieces,
+    and every output of both adjoints, with and without the rotation cotangent, keeps the bits of the aligned call.
+    The 33-link Hu model (16 frames per wave) and the 37-joint binary tree (8) at one whole tile plus a one-frame tile;
+    the one-joint chain, whose lone frame is a 12-byte row with no whole 16-byte piece to load."""
+    from rtg import _lib, ops
+    from rtg.runtime import DofModel, Topology, ptr
+    rng = np.random.default_rng(4000 + J)
+    if kind == "hu":
+        par, lt, axis, lo, hi = hu_clip[1]
+    else:
+        par, lt = _tree(kind, J), rng.normal(0, 0.3, (J, 3)).astype(np.float32)
+        axis = rng.integers(0, 3, J - 1).astype(np.int32)
+        lo, hi = (-0.5 - rng.uniform(0, 1, J - 1)).astype(np.float32), (0.5 + rng.uniform(0, 1, J - 1)).astype(np.float32)
+    topo = Topology(par, lt)
+    model = DofModel(topo, axis, lo, hi)
+    lib = _lib.lib()
+    for B in Bs:
+        dev = lambda a: torch.as_tensor(a).cuda()
+        dof = dev(rng.uniform(-3, 3, (B, J - 1)).astype(np.float32))
+        rr, rt = dev(_scaled_quats(rng, B)), dev(rng.normal(0, 0.3, (B, 3)).astype(np.float32))
+        lr = dev(np.ascontiguousarray(_scaled_quats(rng, B * J).reshape(B, J, 4)))
+        cr = dev(rng.normal(size=(B, J, 4)).astype(np.float32))
+        cp = rng.normal(size=(B, J, 3)).astype(np.float32)
+        g_dof = ops.dof_forward_kinematics(model, dof, rr, rt, clip=True)[0].contiguous()
+        g_fk = ops.forward_kinematics(topo, lr, rt)[0].contiguous()
+
+        def run(form, cot_rot, cot_pos):
+            outs = [torch.full(s, 7.0, device="cuda") for s in
+                    (((B, J - 1), (B, 4), (B, 3)) if form == "dof" else ((B, J, 4), (B, 3)))]
+            if form == "dof":
+                rc = lib.rtg_dof_fk_backward_f32(model.handle, ptr(dof) if J > 1 else None, ptr(g_dof), ptr(cot_rot),
+                                                 ptr(cot_pos), B, 1, ptr(outs[0]) if J > 1 else None, ptr(outs[1]),
+                                                 ptr(outs[2]), None)
+            else:
+                rc = lib.rtg_fk_backward_f32(topo.handle, ptr(lr), ptr(g_fk), ptr(cot_rot), ptr(cot_pos), B,
+                                             ptr(outs[0]), ptr(outs[1]), None)
+            assert rc == 0, lib.rtg_last_error()
+            torch.cuda.synchronize()
+            return [_np(o).view(np.uint32) for o in outs]
+
+        for form in ("dof", "fk"):
+            for cot_rot in (cr, None):
+                for a, b in zip(run(form, cot_rot, dev(cp)), run(form, cot_rot, _offset4(cp))):
+                    np.testing.assert_array_equal(a, b, err_msg=f"{kind} J={J} B={B} {form} rot={cot_rot is not None}")

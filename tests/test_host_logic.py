@@ -353,3 +353,20 @@ def test_frame_post_extension_refuses_what_it_cannot_post():
         rc, code, *_ = fp.post(0, 0, 1, 0, b, l, r, 0, 0, 0, 1000)
         assert rc == fp.NOT_HOST_F32 and code == 0
     assert fp.SERVER_ENDED == 6
+
+
+def test_group_scheduler_invariants(tmp_path):
+    """The lane-group list scheduler (csrc/rtg_group_sched.h, plain C++) through its stand-alone check
+    (tests/group_sched_check.cpp): every included joint exactly once, parents strictly earlier, complete ascending
+    child links, on chains, stars, random trees and masks -- and the 31-joint Hu tree on 4 lanes takes the 10 steps
+    DESIGN.md quotes."""
+    import subprocess
+    from rtg import assets
+    exe = str(tmp_path / "group_sched_check")
+    src = os.path.join(REPO, "tests", "group_sched_check.cpp")
+    inc = os.path.join(REPO, "humanoid-real-time-retarget_amd", "csrc")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I", inc, src, "-o", exe], check=True, timeout=120)
+    hu = [str(int(p)) for p in assets.parents("hu_v5")]
+    assert len(hu) == 31
+    r = subprocess.run([exe, "10"] + hu, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "0 failures" in r.stdout, r.stdout[-2000:]

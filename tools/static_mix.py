@@ -49,6 +49,7 @@ def classify(insts):
             "ieee_div_f32": sum(op(i).startswith("v_div_fixup_f32") for i in valu),
             "v_rcp_f32": sum(op(i).startswith("v_rcp_f32") for i in valu),
             "v_sqrt_f32": sum(op(i).startswith("v_sqrt_f32") for i in valu), "s_nop": sum(op(i) == "s_nop" for i in insts),
+            "ds": sum(op(i).startswith("ds_") for i in insts), "global": sum(op(i).startswith("global_") for i in insts),
             "plain": len(valu) - len(pk), "issue_slots": len(valu) + len(pk)}
 
 
