@@ -56,6 +56,13 @@ struct rtg_rot_ingest_s {
     float *d_blob = nullptr;
 };
 
+// A motion library's clip table on the device; F_total bounds the caller's arrays (the overlap checks).
+struct rtg_motion_lib_s {
+    MotionClip *d_clips = nullptr;
+    int32_t C = 0;
+    int64_t F_total = 0;
+};
+
 struct rtg_solver_s {
     int kind = 0;
     int precise = 0;
@@ -662,6 +669,111 @@ int rtg_rot_ingest_f32(rtg_rot_ingest_t h, const float *q, int64_t B, int layout
     const uint64_t na = (uint64_t)B * h->view.J_in * 16, nb = (uint64_t)B * h->view.J_out * 16;
     if (a < b + nb && b < a + na) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: q and out overlap", fn);
     RTG_TRY(launch_rot_ingest(h->view, q, B, layout, out, as_stream(stream)), "k_rot_ingest");
+    return RTG_OK;
+}
+
+// ---------------------------------------------------------------- motion sampling
+int rtg_motion_lib_create(const int64_t *start, const int32_t *len, const float *fps, int32_t C, int64_t F_total,
+                          rtg_motion_lib_t *out)
+{
+    const char *fn = "rtg_motion_lib_create";
+    if (!out) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: out is NULL", fn);
+    *out = nullptr;
+    if (!start || !len || !fps) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL start / len / fps", fn);
+    if (C < 1) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: C=%d clips (need at least 1)", fn, C);
+    if (F_total < 1 || F_total > INT32_MAX)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: F_total=%lld outside 1..2^31-1", fn, (long long)F_total);
+    std::vector<MotionClip> tab((size_t)C);
+    for (int c = 0; c < C; ++c) {
+        if (len[c] < 1) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: len[%d]=%d < 1", fn, c, len[c]);
+        if (start[c] < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: start[%d]=%lld < 0", fn, c, (long long)start[c]);
+        if (start[c] > F_total - len[c])
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: clip %d ends at row %lld, past F_total=%lld", fn, c,
+                        (long long)start[c] + len[c], (long long)F_total);
+        if (!std::isfinite(fps[c]) || !(fps[c] > 0.0f))
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: fps[%d]=%g must be finite and positive", fn, c, (double)fps[c]);
+        tab[c] = MotionClip{start[c], len[c], fps[c]};
+    }
+    rtg_motion_lib_s *h = new (std::nothrow) rtg_motion_lib_s();
+    if (!h) return fail(RTG_ERR_OUT_OF_MEMORY, "%s: host allocation failed", fn);
+    int rc = hip_check(hipMalloc(&h->d_clips, sizeof(MotionClip) * C), "hipMalloc(motion clip table)");
+    if (rc == RTG_OK)
+        rc = hip_check(hipMemcpy(h->d_clips, tab.data(), sizeof(MotionClip) * C, hipMemcpyHostToDevice), "hipMemcpy");
+    if (rc != RTG_OK) {
+        (void)hipFree(h->d_clips);
+        delete h;
+        return rc;
+    }
+    h->C = C;
+    h->F_total = F_total;
+    *out = h;
+    return RTG_OK;
+}
+
+void rtg_motion_lib_destroy(rtg_motion_lib_t h)
+{
+    if (!h) return;
+    (void)hipFree(h->d_clips);
+    delete h;
+}
+
+int rtg_motion_sample_f32(rtg_topology_t topo, rtg_motion_lib_t lib, const float *rot, const float *root_t,
+                          const float *vec, int32_t K, const int32_t *clip, const float *time, int64_t N, int flags,
+                          float *local_rot_out, float *root_t_out, float *vec_out, float *g_rot, float *g_pos,
+                          rtg_stream_t stream)
+{
+    const char *fn = "rtg_motion_sample_f32";
+    // what does not depend on the handles first: a caller (and a test on a machine without a GPU) sees these reasons
+    // whatever the handles are
+    if (N < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: N=%lld < 0", fn, (long long)N);
+    if (K < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: K=%d < 0", fn, K);
+    if (flags & ~(RTG_MOTION_NORMALIZE | RTG_MOTION_GLOBAL | RTG_MOTION_STATE))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: unknown flags 0x%x", fn, flags);
+    const bool global = (flags & RTG_MOTION_GLOBAL) != 0;
+    if (N > 0) {   // empty buffers have no address to give
+        if ((vec == nullptr) != (vec_out == nullptr))
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both vec and vec_out or neither", fn);
+        if (vec && K < 1) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: vec rows given with K=%d", fn, K);
+        if ((g_rot == nullptr) != (g_pos == nullptr))
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both g_rot and g_pos or neither", fn);
+        if (global != (g_rot != nullptr))
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: g_rot / g_pos go with RTG_MOTION_GLOBAL (flag %d, buffers %s)",
+                        fn, (int)global, g_rot ? "given" : "NULL");
+        if (!rot || !root_t || !clip || !time || !local_rot_out || !root_t_out)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    }
+    if ((reinterpret_cast<uintptr_t>(rot) | reinterpret_cast<uintptr_t>(local_rot_out) |
+         reinterpret_cast<uintptr_t>(g_rot)) & 15)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: rot / local_rot_out / g_rot not 16-byte aligned", fn);
+    if (!topo) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL topology", fn);
+    if (!lib) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL library", fn);
+    const int J = topo->J;
+    if (J > kGroupMaxJ || !topo->d_gsched)
+        return fail(RTG_ERR_UNSUPPORTED, "%s: serves skeletons of 1..%d joints (this one has %d)", fn, kGroupMaxJ, J);
+    if (N == 0) return RTG_OK;
+    {   // no output may overlap an input (or another output)
+        struct Span { const void *p; uint64_t n; const char *name; };
+        const uint64_t Ft = (uint64_t)lib->F_total, n = (uint64_t)N, j = (uint64_t)J, k = (uint64_t)K;
+        const Span in[] = {{rot, Ft * j * 16, "rot"}, {root_t, Ft * 12, "root_t"}, {vec, Ft * k * 12, "vec"},
+                           {clip, n * 4, "clip"}, {time, n * 4, "time"}};
+        const Span outs[] = {{local_rot_out, n * j * 16, "local_rot_out"}, {root_t_out, n * 12, "root_t_out"},
+                             {vec_out, n * k * 12, "vec_out"}, {g_rot, n * j * 16, "g_rot"}, {g_pos, n * j * 12, "g_pos"}};
+        auto hit = [](const Span &a, const Span &b) {
+            const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
+            return a.p && b.p && x < y + b.n && y < x + a.n;
+        };
+        for (size_t o = 0; o < 5; ++o) {
+            for (const Span &i : in)
+                if (hit(outs[o], i)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: %s and %s overlap", fn, outs[o].name, i.name);
+            for (size_t o2 = o + 1; o2 < 5; ++o2)
+                if (hit(outs[o], outs[o2]))
+                    return fail(RTG_ERR_INVALID_ARGUMENT, "%s: %s and %s overlap", fn, outs[o].name, outs[o2].name);
+        }
+    }
+    const MotionSampleArgs A{rot, root_t, vec, K, clip, time, N, local_rot_out, root_t_out, vec_out, g_rot, g_pos};
+    RTG_TRY(launch_motion_sample(topo->view(), MotionLibView{lib->d_clips, lib->C}, (flags & RTG_MOTION_NORMALIZE) != 0,
+                                 global, (flags & RTG_MOTION_STATE) != 0, A, as_stream(stream)),
+            "k_motion_sample");
     return RTG_OK;
 }
 

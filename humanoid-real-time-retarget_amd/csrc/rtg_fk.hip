@@ -136,75 +136,6 @@ __global__ __launch_bounds__(256) void k_dof_fk_walk(TopoView T, DofView D, cons
 // LDS per wave: F J 28 bytes plus the schedule (Hu: 13.9 + 1.3 KiB).  Inverse FK (kinematics.py:41-63) has no chain:
 // each record's parent is read from the image and its local rotation stored straight from the lane that loaded it.
 // ----------------------------------------------------------------------------
-// The FK tile's images; dof: the joint-angle model's per-joint {axis, lower, upper} table behind them
-struct FkImages {
-    f4v *rot;        // [F J] the local rotations, overwritten by the global ones
-    float *pos;      // [F J 3] the positions, the root's preset
-    GEnt *sch;       // [gsteps L] the schedule
-    UnitEnt *utab;   // the near-unit table
-    f4v *ntab;       // dof: [J]
-    size_t floats;
-    __host__ __device__ FkImages(float *base, int J, int F, int steps, bool dof)
-    {
-        LdsCarve c(base);
-        rot = c.take<f4v>((size_t)F * J);
-        pos = c.take<float>((size_t)3 * F * J);
-        sch = c.take<GEnt>((size_t)steps * (64 / F));
-        utab = c.take_unit_tab();
-        ntab = c.take<f4v>(dof ? J : 0);
-        floats = c.floats;
-    }
-};
-
-// The schedule's steps over the tile image (rot: global rotations written over the local ones; pos: positions, the
-// root's preset).  LQ(j, lq) gives joint j's local rotation from its image record (FK: the record itself, with the
-// tree quaternion when STATE; DOF FK: built from the joint angle).
-template <int F, typename LocalQ>
-RTG_DEV void group_compose(const TopoView &T, f4v *rot, float *pos, const GEnt *sch, int nfr, const UnitEnt *utab,
-                           const LocalQ &LQ)
-{
-    using G = Grp<F>;
-    const int J = T.J, lane = (int)threadIdx.x;
-    const int fr = lane >> G::LOG_L, sub = lane & (G::L - 1);
-    const bool live = fr < nfr;
-    const int base = fr * J;
-    for (int s = 0; s < T.gsteps; ++s) {
-        const GEnt e = sch[s * G::L + sub];
-        const int j = e.code & 0xFF, p = (e.code >> 8) & 0xFF;
-        if (live && j != 0xFF) {
-            const f4v lv = rot[base + j];
-            Q ng;
-            V nt;
-            if (j == 0) {   // root: global = local, unnormalised; position = the root translation (kinematics.py:27-29)
-                ng = q_of(lv);
-                nt = V{pos[3 * base], pos[3 * base + 1], pos[3 * base + 2]};
-            } else {
-                const Q lq = LQ(j, q_of(lv), e, fr);
-                const Q g = q_of(rot[base + p]);
-                const float *tp = pos + 3 * (base + p);
-                const V t{tp[0], tp[1], tp[2]};
-                const V rv = qrotate(g, V{e.lx, e.ly, e.lz});
-                ng = qmul_norm_tab(g, lq, utab);
-                nt = V{rv.x + t.x, rv.y + t.y, rv.z + t.z};
-            }
-            rot[base + j] = v_of(ng);
-            float *op = pos + 3 * (base + j);
-            op[0] = nt.x; op[1] = nt.y; op[2] = nt.z;
-        }
-        wave_sync();   // this step's records before the next step's parent reads (other lanes)
-    }
-}
-
-// the tile image out: rotations record-ordered, positions as consecutive pieces (PosRows)
-template <int F>
-RTG_DEV void group_store(const f4v *rot, const float *pos, int nrec, float *__restrict__ g_rot, float *__restrict__ g_pos)
-{
-    GroupRows<F> o;
-    o.load(rot, nrec);
-    o.out(g_rot, nrec);
-    PosRows<F>::out(pos, g_pos, 3 * nrec);
-}
-
 template <bool STATE, int F>
 RTG_DEV void fk_group_tile(const TopoView &T, const float *__restrict__ local_rot, const float *__restrict__ root_t,
                            int64_t B, int64_t f0, float *__restrict__ g_rot, float *__restrict__ g_pos, float *lds)

@@ -1,10 +1,12 @@
 // rtg_fk_group.cuh -- the lane-group tile kit shared by the forward kinematics kernels (rtg_fk.hip), their adjoints
-// (rtg_fk_grad.hip), the keypoint fit (rtg_dof_fit.hip) and retarget_to (rtg_retarget_to.hip): a tile is one wave, F
-// frames, 64 / F lanes per frame, rows moved as 1 KiB pieces through LDS images (the layout comment in rtg_fk.hip).
-// The parts: the LDS carve (LdsCarve: a kernel and its launcher call the same carve function), the row movers
-// (LaneRows as GroupRows: float4 records, and ScalarRows: scalars; PosRows: position rows), the table fills, the root preset, the
-// reverse sweep's child pull, the item split, the Q <-> f4v converters, the straight-through clamp and the launch
-// dispatch.  The multi-wave tile of rtg_rot_ingest.hip takes only the converters and the item split.
+// (rtg_fk_grad.hip), the keypoint fit (rtg_dof_fit.hip), retarget_to (rtg_retarget_to.hip) and the motion sampler
+// (rtg_motion_sample.hip): a tile is one wave, F frames, 64 / F lanes per frame, rows moved as 1 KiB pieces through
+// LDS images (the layout comment in rtg_fk.hip).  The parts: the LDS carve (LdsCarve: a kernel and its launcher call
+// the same carve function), the row movers (LaneRows as GroupRows: float4 records, and ScalarRows: scalars; PosRows:
+// position rows), the table fills, the root preset, the reverse sweep's child pull, the FK tile itself (FkImages,
+// group_compose, group_store: rtg_fk.hip and rtg_motion_sample.hip), the item split, the Q <-> f4v converters, the
+// straight-through clamp and the launch dispatch.  The multi-wave tile of rtg_rot_ingest.hip takes only the
+// converters and the item split.
 #pragma once
 #include "rtg_device.cuh"
 
@@ -256,6 +258,76 @@ RTG_DEV f4v child_pull(f4v a, const f4v *A, float *P, int base, int j, int first
     }
     pj[0] = pb.x; pj[1] = pb.y; pj[2] = pb.z;
     return a;
+}
+
+// ---------------------------------------------------------------------------------------------------- the FK tile
+// The FK tile's images; dof: the joint-angle model's per-joint {axis, lower, upper} table behind them
+struct FkImages {
+    f4v *rot;        // [F J] the local rotations, overwritten by the global ones
+    float *pos;      // [F J 3] the positions, the root's preset
+    GEnt *sch;       // [gsteps L] the schedule
+    UnitEnt *utab;   // the near-unit table
+    f4v *ntab;       // dof: [J]
+    size_t floats;
+    __host__ __device__ FkImages(float *base, int J, int F, int steps, bool dof)
+    {
+        LdsCarve c(base);
+        rot = c.take<f4v>((size_t)F * J);
+        pos = c.take<float>((size_t)3 * F * J);
+        sch = c.take<GEnt>((size_t)steps * (64 / F));
+        utab = c.take_unit_tab();
+        ntab = c.take<f4v>(dof ? J : 0);
+        floats = c.floats;
+    }
+};
+
+// The schedule's steps over the tile image (rot: global rotations written over the local ones; pos: positions, the
+// root's preset).  LQ(j, lq) gives joint j's local rotation from its image record (FK: the record itself, with the
+// tree quaternion when STATE; DOF FK: built from the joint angle).
+template <int F, typename LocalQ>
+RTG_DEV void group_compose(const TopoView &T, f4v *rot, float *pos, const GEnt *sch, int nfr, const UnitEnt *utab,
+                           const LocalQ &LQ)
+{
+    using G = Grp<F>;
+    const int J = T.J, lane = (int)threadIdx.x;
+    const int fr = lane >> G::LOG_L, sub = lane & (G::L - 1);
+    const bool live = fr < nfr;
+    const int base = fr * J;
+    for (int s = 0; s < T.gsteps; ++s) {
+        const GEnt e = sch[s * G::L + sub];
+        const int j = e.code & 0xFF, p = (e.code >> 8) & 0xFF;
+        if (live && j != 0xFF) {
+            const f4v lv = rot[base + j];
+            Q ng;
+            V nt;
+            if (j == 0) {   // root: global = local, unnormalised; position = the root translation (kinematics.py:27-29)
+                ng = q_of(lv);
+                nt = V{pos[3 * base], pos[3 * base + 1], pos[3 * base + 2]};
+            } else {
+                const Q lq = LQ(j, q_of(lv), e, fr);
+                const Q g = q_of(rot[base + p]);
+                const float *tp = pos + 3 * (base + p);
+                const V t{tp[0], tp[1], tp[2]};
+                const V rv = qrotate(g, V{e.lx, e.ly, e.lz});
+                ng = qmul_norm_tab(g, lq, utab);
+                nt = V{rv.x + t.x, rv.y + t.y, rv.z + t.z};
+            }
+            rot[base + j] = v_of(ng);
+            float *op = pos + 3 * (base + j);
+            op[0] = nt.x; op[1] = nt.y; op[2] = nt.z;
+        }
+        wave_sync();   // this step's records before the next step's parent reads (other lanes)
+    }
+}
+
+// the tile image out: rotations record-ordered, positions as consecutive pieces (PosRows)
+template <int F>
+RTG_DEV void group_store(const f4v *rot, const float *pos, int nrec, float *__restrict__ g_rot, float *__restrict__ g_pos)
+{
+    GroupRows<F> o;
+    o.load(rot, nrec);
+    o.out(g_rot, nrec);
+    PosRows<F>::out(pos, g_pos, 3 * nrec);
 }
 
 // ---------------------------------------------------------------------------------------------------- launch dispatch

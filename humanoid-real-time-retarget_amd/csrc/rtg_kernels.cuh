@@ -152,6 +152,28 @@ void rot_ingest_blob(int32_t J_in, int32_t J_out, const int32_t *src, const floa
                      std::vector<float> &blob, RotIngestView &view);
 hipError_t launch_rot_ingest_tab(float *blob_tab, hipStream_t s);
 hipError_t launch_rot_ingest(const RotIngestView &P, const float *q, int64_t B, int layout, float *out, hipStream_t s);
+// The motion sampler (rtg_motion_sample.hip): a library's clip table, one 16-byte entry per clip (device), and the
+// arguments of one launch (rtg.h's pointers; vec / vec_out, g_rot / g_pos nullptr when not asked for).
+struct alignas(16) MotionClip {
+    int64_t start;   // first row of the clip in the packed arrays
+    int32_t len;     // frames, >= 1
+    float fps;       // finite, > 0
+};
+struct MotionLibView {
+    const MotionClip *clips;   // device, (C)
+    int32_t C;
+};
+struct MotionSampleArgs {
+    const float *rot, *root_t, *vec;
+    int32_t K;
+    const int32_t *clip;
+    const float *time;
+    int64_t N;
+    float *local_rot_out, *root_t_out, *vec_out, *g_rot, *g_pos;
+};
+// lane groups only (T.gsched); g_rot / g_pos are written iff `global`, as rtg_state_fk_f32 (`state`) or rtg_fk_f32
+hipError_t launch_motion_sample(const TopoView &T, const MotionLibView &L, bool normalize, bool global, bool state,
+                                const MotionSampleArgs &A, hipStream_t s);
 hipError_t launch_rescale_motion(const TopoView &T, const float *motion, int64_t B, const float *dir, float *out,
                                  hipStream_t s);
 hipError_t launch_quat_between(const float *v1, const float *v2, int64_t n, float *out, float *ws, hipStream_t s);

@@ -416,6 +416,29 @@ class SkeletonMotion(SkeletonState):
         return cls.from_state_vector_and_velocity(skeleton_state.skeleton_tree, skeleton_state.tensor,
                                                   back(gv, dev), back(gav, dev), skeleton_state.is_local, fps)
 
+    def resample(self, fps) -> "SkeletonMotion":
+        """This motion at another frame rate (not in the reference, whose ``crop`` only decimates by an integer
+        factor): frames at ``float32(k / fps)`` seconds for k = 0 .. floor((L - 1) * fps / self.fps), each between the
+        two stored frames around it -- ``quat_slerp`` of the local rotations, then ``quat_normalize``; the root
+        translation blended linearly -- in one launch (rtg.motion).  The result is a local motion; its
+        velocities are not interpolated but recomputed by ``from_skeleton_state`` at the new rate."""
+        import math
+
+        from rtg.motion import MotionLibrary
+        if self.tensor.dim() != 2:
+            raise ValueError(f"resample needs a motion with exactly one batch dimension, got shape "
+                             f"{tuple(self.tensor.shape[:-1])}")
+        if not (math.isfinite(float(fps)) and float(fps) > 0):
+            raise ValueError(f"resample: fps must be finite and positive, got {fps!r}")
+        lib = MotionLibrary(self, with_velocity=False)
+        n = int(math.floor((len(self) - 1) * float(fps) / float(self.fps))) + 1
+        times = (np.arange(n, dtype=np.float64) / float(fps)).astype(np.float32)
+        s = lib.sample(np.zeros(n, np.int32), times, want_global=False, want_velocity=False, normalize=True)
+        dev = self.tensor.device
+        state = SkeletonState(SkeletonState._to_state_vector(back(s.local_rotation, dev), back(s.root_translation, dev)),
+                              self.skeleton_tree, True)
+        return SkeletonMotion.from_skeleton_state(state, fps)
+
     def retarget_to(self, joint_mapping: Dict[str, str], source_tpose_local_rotation, source_tpose_root_translation,
                     target_skeleton_tree: SkeletonTree, target_tpose_local_rotation, target_tpose_root_translation,
                     rotation_to_target_skeleton, scale_to_target_skeleton: float, z_up: bool = True) -> "SkeletonMotion":

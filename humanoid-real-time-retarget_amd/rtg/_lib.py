@@ -67,6 +67,11 @@ OP_PROJECT_QUAT = {"x": 27, "y": 28, "z": 29, "xy": 30, "xz": 31}
 
 MAX_SEGMENTS = 8
 
+# rtg_motion_flags
+MOTION_NORMALIZE = 1
+MOTION_GLOBAL = 2
+MOTION_STATE = 4
+
 
 class RtgError(RuntimeError):
     """A librtg_hip call returned a non-zero rtg_status."""
@@ -128,6 +133,10 @@ SIGNATURES = {
                                       POINTER(c_void_p)]),
     "rtg_rot_ingest_destroy": (None, [c_void_p]),
     "rtg_rot_ingest_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "rtg_motion_lib_create": (c_int, [POINTER(c_int64), POINTER(c_int32), POINTER(c_float), c_int32, c_int64,
+                                      POINTER(c_void_p)]),
+    "rtg_motion_lib_destroy": (None, [c_void_p]),
+    "rtg_motion_sample_f32": (c_int, [c_void_p] * 5 + [c_int32, c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 6),
     "rtg_solver_create": (c_int, [c_int, POINTER(c_float), POINTER(c_float), POINTER(c_int32), c_int32, c_int,
                                   POINTER(c_void_p)]),
     "rtg_solver_destroy": (c_int, [c_void_p]),

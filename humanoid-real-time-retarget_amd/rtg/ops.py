@@ -15,7 +15,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import check, lib
-from .runtime import (RetargetPlan, Topology, dev_f32, layout_code, ptr, require_gpu, require_gpu_rtg,
+from .runtime import (MotionLib, RetargetPlan, Topology, dev_f32, layout_code, ptr, require_gpu, require_gpu_rtg,
                       stream_handle)
 
 
@@ -293,6 +293,52 @@ def retarget_to(plan: RetargetPlan, rot, root_t, is_local: bool = True):
     check(lib().rtg_retarget_to_f32(plan.handle, ptr(r), ptr(t), int(bool(is_local)), B, ptr(out_rot), ptr(out_root),
                                     stream_handle()))
     return out_rot, out_root
+
+
+def motion_sample(topo: Topology, mlib: MotionLib, rot, root_t, clip_ids, times, vec=None, normalize: bool = False,
+                  want_global: bool = False, state: bool = False):
+    """Sample a motion library at (clip, time) pairs in one launch (rtg.h rtg_motion_sample_f32): per query the two
+    frames around ``time * fps`` of its clip, ``quat_slerp`` (transform3d.py:152-174) of every joint's local rotation
+    (``quat_normalize`` after it with ``normalize``), torch's ``(1 - b) * a + b * c`` on the root translation and the
+    ``vec`` rows, and with ``want_global`` the forward kinematics of the blended pose (SkeletonState's with ``state``).
+
+    rot (F_total, J, 4), root_t (F_total, 3) and vec (F_total, K, 3) | None are the library's packed arrays, clip_ids
+    (N) int32 and times (N) float32 the queries.  Returns (local_rot (N, J, 4), root_t (N, 3), vec (N, K, 3) | None,
+    g_rot (N, J, 4) | None, g_pos (N, J, 3) | None) on the device.  A query whose clip id is outside 0..C-1 gives NaN
+    rows.  Raises RtgError without a GPU: there is no CPU fallback."""
+    dev = require_gpu_rtg()
+    J, Ft = topo.num_joints, mlib.total_frames
+    r = dev_f32(rot, (J, 4), "rot")
+    t = dev_f32(root_t, (3,), "root_t")
+    if tuple(r.shape) != (Ft, J, 4) or tuple(t.shape) != (Ft, 3):
+        raise ValueError(f"rot / root_t must be ({Ft}, {J}, 4) / ({Ft}, 3), got {tuple(r.shape)} / {tuple(t.shape)}")
+    v, K = None, 0
+    if vec is not None:
+        v = dev_f32(vec, (3,), "vec")
+        if v.dim() != 3 or v.shape[0] != Ft or v.shape[1] < 1:
+            raise ValueError(f"vec must be ({Ft}, K, 3) with K >= 1, got {tuple(v.shape)}")
+        K = int(v.shape[1])
+    c = clip_ids if isinstance(clip_ids, torch.Tensor) else torch.as_tensor(clip_ids)
+    if c.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError(f"clip_ids must be integers, got {c.dtype}")
+    c = c.to(device=dev, dtype=torch.int32).contiguous()
+    tm = dev_f32(times)
+    if c.dim() != 1 or tm.shape != c.shape:
+        raise ValueError(f"clip_ids / times must be (N,) each, got {tuple(c.shape)} / {tuple(tm.shape)}")
+    if mlib.device != dev:
+        raise ValueError(f"the queries are on {dev}; this library lives on {mlib.device}")
+    N = int(c.shape[0])
+    out_rot = torch.empty((N, J, 4), device=dev, dtype=torch.float32)
+    out_root = torch.empty((N, 3), device=dev, dtype=torch.float32)
+    out_vec = torch.empty((N, K, 3), device=dev, dtype=torch.float32) if v is not None else None
+    g_rot = torch.empty((N, J, 4), device=dev, dtype=torch.float32) if want_global else None
+    g_pos = torch.empty((N, J, 3), device=dev, dtype=torch.float32) if want_global else None
+    flags = (_lib.MOTION_NORMALIZE if normalize else 0) | (_lib.MOTION_GLOBAL if want_global else 0) | \
+        (_lib.MOTION_STATE if state else 0)
+    check(lib().rtg_motion_sample_f32(topo.handle, mlib.handle, ptr(r), ptr(t), ptr(v), K, ptr(c), ptr(tm), N, flags,
+                                      ptr(out_rot), ptr(out_root), ptr(out_vec), ptr(g_rot), ptr(g_pos),
+                                      stream_handle()))
+    return out_rot, out_root, out_vec, g_rot, g_pos
 
 
 def dof_forward_kinematics(model, dof, root_rot, root_t, clip: bool = False):

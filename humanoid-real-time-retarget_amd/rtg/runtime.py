@@ -198,6 +198,39 @@ class RetargetPlan:
             self._h = None
 
 
+class MotionLib:
+    """The clip table of a motion library (``rtg_motion_lib_t``): per clip its first row in the packed arrays, its
+    length in frames and its frame rate.  The arrays themselves stay with the caller (``ops.motion_sample``).  The
+    table is validated on the host first: a bad one raises RtgError with the reason, GPU or not."""
+
+    def __init__(self, start, length, fps, total_frames: int):
+        s = np.ascontiguousarray(np.asarray(start, dtype=np.int64).reshape(-1))
+        n = _host_i32(length).reshape(-1)
+        f = _host_f32(fps).reshape(-1)
+        if not (s.shape == n.shape == f.shape):
+            raise ValueError("start / length / fps lengths differ")
+        h = ctypes.c_void_p()
+        check(lib().rtg_motion_lib_create(s.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                          n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                          f.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(s.shape[0]),
+                                          int(total_frames), ctypes.byref(h)))
+        self._h = h
+        self.num_clips = int(s.shape[0])
+        self.total_frames = int(total_frames)
+        self.start, self.length, self.fps = s, n, f
+        self.device = torch.device("cuda", torch.cuda.current_device())   # owns the table (rtg.h)
+
+    @property
+    def handle(self) -> ctypes.c_void_p:
+        return self._h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib._lib is not None:
+            _lib._lib.rtg_motion_lib_destroy(h)
+            self._h = None
+
+
 # Frames the reference raises on (rtg.h rtg_frame_error): the batched solve marks them -- every dof of the row NaN,
 # dof[f, 0] = RTG_FRAME_NAN | code -- and the per-frame calls raise what the reference raises.
 FRAME_ERRORS = {

@@ -263,6 +263,49 @@ void rtg_rot_ingest_destroy(rtg_rot_ingest_t h);
 int rtg_rot_ingest_f32(rtg_rot_ingest_t h, const float *q, int64_t B, int layout, float *out, rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Motion sampling: many clips of one skeleton, sampled at arbitrary (clip, time) pairs in ONE launch -- the index
+ * rule, the gather of the two frames, quat_slerp (transform3d.py:152-174) per joint, the linear blends and, when
+ * asked, the forward kinematics of the blended pose.
+ *
+ * A library is C clips packed frame-major into arrays the caller owns: rot (F_total,J,4) local rotations, root_t
+ * (F_total,3), optionally vec (F_total,K,3) vector rows (velocities, say), and per clip start[c] (first row), len[c]
+ * (frames) and fps[c].  For query n with c = clip[n], t = time[n] (seconds from the clip's first frame):
+ *   - the query is valid iff 0 <= c < C; every output element of an invalid query is the quiet NaN 0x7FC00000 and it
+ *     reads no library row;
+ *   - p = (double)t * (double)fps[c]; !(p > 0) -> p = 0 (NaN, -0, negatives);
+ *   - p >= len[c] - 1: i0 = i1 = len[c] - 1, b = 0; else i0 = trunc(p), i1 = i0 + 1, b = (float)(p - (double)i0).
+ *     No wrap-around; i1 never leaves the clip;
+ *   - local_rot_out[n, j] = RTG_OP_QUAT_SLERP(rot[start+i0, j], rot[start+i1, j], b) bit for bit (pairs whose half
+ *     angle's sine is below 0.001 return the midpoint whatever b is, as the reference has it), then
+ *     RTG_OP_QUAT_NORMALIZE with RTG_MOTION_NORMALIZE;
+ *   - root_t_out[n] and vec_out[n] = ((1.0f - b) * a) + (b * c) per component: four float32 roundings, no FMA;
+ *   - with RTG_MOTION_GLOBAL, g_rot / g_pos are what rtg_fk_f32 (rtg_state_fk_f32 with RTG_MOTION_STATE) gives on
+ *     local_rot_out[n], root_t_out[n].
+ * rtg_motion_lib_create takes HOST arrays, validates them (C >= 1, len >= 1, start >= 0, start + len <= F_total <
+ * 2^31, fps finite and positive, no NULL: RTG_ERR_INVALID_ARGUMENT before any HIP call, the reason in
+ * rtg_last_error()) and copies one table to the current device (synchronously); use the handle on that device only.
+ * ---------------------------------------------------------------------- */
+typedef struct rtg_motion_lib_s *rtg_motion_lib_t;
+typedef enum rtg_motion_flags {
+    RTG_MOTION_NORMALIZE = 1,   /* quat_normalize after the slerp */
+    RTG_MOTION_GLOBAL = 2,      /* also the forward kinematics: g_rot, g_pos */
+    RTG_MOTION_STATE = 4        /* with RTG_MOTION_GLOBAL: SkeletonState FK (the tree quaternions), rtg_state_fk_f32 */
+} rtg_motion_flags;
+int rtg_motion_lib_create(const int64_t *start, const int32_t *len, const float *fps, int32_t C, int64_t F_total,
+                          rtg_motion_lib_t *out);
+void rtg_motion_lib_destroy(rtg_motion_lib_t lib);
+/* rot / root_t / vec are the library's arrays (device), clip (N) int32 and time (N) float32 the queries; outputs
+ * local_rot_out (N,J,4), root_t_out (N,3), vec_out (N,K,3), g_rot (N,J,4), g_pos (N,J,3).  vec and vec_out are given
+ * together (K >= 1) or both NULL; g_rot and g_pos are both given with RTG_MOTION_GLOBAL and both NULL without it.
+ * rot, local_rot_out and g_rot are 16-byte aligned; no output overlaps an input.  Never allocates or synchronises;
+ * N == 0 is a no-op after the argument checks.  A topology of more than 64 joints is RTG_ERR_UNSUPPORTED; every
+ * other rejection is RTG_ERR_INVALID_ARGUMENT, decided before any HIP call. */
+int rtg_motion_sample_f32(rtg_topology_t topo, rtg_motion_lib_t lib, const float *rot, const float *root_t,
+                          const float *vec, int32_t K, const int32_t *clip, const float *time, int64_t N, int flags,
+                          float *local_rot_out, float *root_t_out, float *vec_out, float *g_rot, float *g_pos,
+                          rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Motion-level prep of the legacy motion path (retarget/main.py)
  * ---------------------------------------------------------------------- */
 /* Retarget.rescale_motion_to_standard_size (main.py:37-47) after coord_transform(p, dir=dir) (:170;

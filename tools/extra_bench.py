@@ -18,6 +18,12 @@
               interleaved rounds
   fit_traffic -- a few launches of each fused form and nothing else, for a counter run of its own (FETCH_SIZE or
               WRITE_SIZE, one per run) against the algorithmic bytes that `fit` prints
+  motion_sample -- the fused motion sampler (rtg_motion_sample_f32, C ABI, preallocated outputs; Hu v5, 64 clips x 4096
+              frames, N=262144 queries; uniform / random / frame-instant queries, with global outputs + velocities
+              and local only) against the composed chain (index rule in torch, index_select, quat_slerp,
+              quat_normalize, torch blends, forward_kinematics), interleaved rounds, the results compared bit for bit
+  motion_sample_traffic -- a few launches of the fused sampler and a 256 MiB copy of known bytes, for a counter run of
+              its own against the algorithmic bytes that `motion_sample` prints
 """
 from __future__ import annotations
 
@@ -519,6 +525,121 @@ def fit_traffic(B=262144, iters=32):
             call()
     torch.cuda.synchronize()
     return {"B": B, "launches": "4 x iters=0 (loss, grad out), then 4 x iters=%d (dof, loss out); grids equal" % iters}
+
+
+def motion_sample(N=262144, rounds=4, clips=64, frames=4096):
+    """The fused sampler (rtg_motion_sample_f32, C ABI, preallocated outputs; Hu v5, a library of 64 clips x 4096
+    frames at 30 fps, N = 262144 queries) against the same result composed from the launches that existed before it:
+    the index rule in torch, two index_selects per array, ops.quat_slerp, ops.quat_normalize, torch's blends,
+    ops.forward_kinematics(state=True).  Three query patterns (uniform resample: consecutive queries 0.4 frames apart;
+    random (clip, time); every query on a frame instant) x two output sets (global + velocities; local only),
+    interleaved rounds, the results compared bit for bit."""
+    from rtg.runtime import MotionLib, ptr, stream_handle
+    lib = _lib.lib()
+    T = topo("hu_v5")
+    J, K, fps = 31, 62, 30.0
+    Ft = clips * frames
+    gen = torch.Generator(device="cuda").manual_seed(23)
+    rot = torch.nn.functional.normalize(torch.randn((clips, 1, J, 4), device="cuda", generator=gen) +
+                                        0.02 * torch.randn((clips, frames, J, 4), device="cuda", generator=gen).cumsum(1),
+                                        dim=-1).reshape(Ft, J, 4).contiguous()
+    root = torch.randn((Ft, 3), device="cuda", generator=gen)
+    vec = torch.randn((Ft, K, 3), device="cuda", generator=gen)
+    start = np.arange(clips, dtype=np.int64) * frames
+    ML = MotionLib(start, np.full(clips, frames, np.int32), np.full(clips, fps, np.float32), Ft)
+    start_d = torch.as_tensor(start, device="cuda")
+    n = torch.arange(N, device="cuda", dtype=torch.float64)
+    per = int(frames / 0.4) // 16 * 16                        # queries per clip of the uniform pattern
+    patterns = {
+        "uniform": ((n // per).to(torch.int32) % clips, ((n % per) * 0.4 / fps).float()),
+        "random": (torch.randint(0, clips, (N,), device="cuda", generator=gen, dtype=torch.int32),
+                   (torch.rand((N,), device="cuda", generator=gen) * ((frames - 1) / fps)).float()),
+        "instants": (torch.randint(0, clips, (N,), device="cuda", generator=gen, dtype=torch.int32),
+                     (torch.randint(0, frames, (N,), device="cuda", generator=gen).double() / fps).float()),
+    }
+    o_lr, o_gr = torch.empty((N, J, 4), device="cuda"), torch.empty((N, J, 4), device="cuda")
+    o_rt, o_gp = torch.empty((N, 3), device="cuda"), torch.empty((N, J, 3), device="cuda")
+    o_v = torch.empty((N, K, 3), device="cuda")
+    res = {}
+    for pname, (clip, time) in patterns.items():
+        for full in (True, False):
+            flags = _lib.MOTION_NORMALIZE | ((_lib.MOTION_GLOBAL | _lib.MOTION_STATE) if full else 0)
+
+            def fused():
+                _lib.check(lib.rtg_motion_sample_f32(T.handle, ML.handle, ptr(rot), ptr(root), ptr(vec) if full else None,
+                                                     K if full else 0, ptr(clip), ptr(time), N, flags, ptr(o_lr), ptr(o_rt),
+                                                     ptr(o_v) if full else None, ptr(o_gr) if full else None,
+                                                     ptr(o_gp) if full else None, stream_handle()))
+
+            def composed():
+                p = (time.double() * fps).clamp_min(0.0).nan_to_num(0.0)
+                end = p >= frames - 1
+                i0 = torch.where(end, frames - 1, p.long())
+                b = torch.where(end, 0.0, p - i0).float()
+                r0 = start_d[clip.long()] + i0
+                r1 = r0 + (~end).long()
+                q = ops.quat_normalize(ops.quat_slerp(rot.index_select(0, r0), rot.index_select(0, r1),
+                                                      b[:, None].expand(N, J)))
+                rt = (1 - b)[:, None] * root.index_select(0, r0) + b[:, None] * root.index_select(0, r1)
+                if not full:
+                    return q, rt, None, None, None
+                v = (1 - b)[:, None, None] * vec.index_select(0, r0) + b[:, None, None] * vec.index_select(0, r1)
+                gr, gp = ops.forward_kinematics(T, q, rt, state=True)
+                return q, rt, v, gr, gp
+
+            fused()
+            c = composed()
+            torch.cuda.synchronize()
+            pairs = [(o_lr, c[0]), (o_rt, c[1])] + ([(o_v, c[2]), (o_gr, c[3]), (o_gp, c[4])] if full else [])
+            same = all(bool(torch.equal(a.view(torch.int32), b_.view(torch.int32))) for a, b_ in pairs)
+            del c
+            f_us, c_us = [], []
+            for _ in range(rounds):   # interleaved: both see the same box state
+                f_us.append(time_events(fused, reps=20, warm=3) * 1e3)
+                c_us.append(time_events(composed, reps=5, warm=1) * 1e3)
+            k = K if full else 0
+            rd, wr = 2 * (16 * J + 12 + 12 * k) + 8, 16 * J + 12 + 12 * k + (28 * J if full else 0)
+            res[f"{pname}_{'global_vec' if full else 'local_only'}"] = {
+                "N": N, "J": J, "K": k, "algorithmic_bytes_per_query": {"read": rd, "written": wr},
+                "fused_us": f_us, "composed_us": c_us,
+                "fused_TBs": [N * (rd + wr) / (u * 1e-6) / 1e12 for u in f_us],
+                "composed_equals_fused_bits": same, "every_fused_faster": max(f_us) < min(c_us)}
+    return res
+
+
+def motion_sample_traffic(N=262144, clips=64, frames=4096):
+    """A few launches of the fused sampler (random pattern; global + vec, then local only) and a 256 MiB device copy
+    of known bytes, nothing else: for a counter run of its own (FETCH_SIZE or WRITE_SIZE, one per run) against the
+    algorithmic bytes that `motion_sample` prints.  The copy calibrates the counters' unit."""
+    from rtg.runtime import MotionLib, ptr, stream_handle
+    lib = _lib.lib()
+    T = topo("hu_v5")
+    J, K, fps, Ft = 31, 62, 30.0, clips * frames
+    gen = torch.Generator(device="cuda").manual_seed(23)
+    rot = torch.nn.functional.normalize(torch.randn((Ft, J, 4), device="cuda", generator=gen), dim=-1)
+    root = torch.randn((Ft, 3), device="cuda", generator=gen)
+    vec = torch.randn((Ft, K, 3), device="cuda", generator=gen)
+    ML = MotionLib(np.arange(clips, dtype=np.int64) * frames, np.full(clips, frames, np.int32),
+                   np.full(clips, fps, np.float32), Ft)
+    clip = torch.randint(0, clips, (N,), device="cuda", generator=gen, dtype=torch.int32)
+    time_ = (torch.rand((N,), device="cuda", generator=gen) * ((frames - 1) / fps)).float()
+    o_lr, o_gr = torch.empty((N, J, 4), device="cuda"), torch.empty((N, J, 4), device="cuda")
+    o_rt, o_gp = torch.empty((N, 3), device="cuda"), torch.empty((N, J, 3), device="cuda")
+    o_v = torch.empty((N, K, 3), device="cuda")
+    src, dst = torch.randn(1 << 26, device="cuda", generator=gen), torch.empty(1 << 26, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(3):
+        dst.copy_(src)
+    for full in (True, False):
+        flags = _lib.MOTION_NORMALIZE | ((_lib.MOTION_GLOBAL | _lib.MOTION_STATE) if full else 0)
+        for _ in range(3):
+            _lib.check(lib.rtg_motion_sample_f32(T.handle, ML.handle, ptr(rot), ptr(root), ptr(vec) if full else None,
+                                                 K if full else 0, ptr(clip), ptr(time_), N, flags, ptr(o_lr), ptr(o_rt),
+                                                 ptr(o_v) if full else None, ptr(o_gr) if full else None,
+                                                 ptr(o_gp) if full else None, stream_handle()))
+    torch.cuda.synchronize()
+    return {"N": N, "copy_bytes_each_way": 4 << 26,
+            "launches": "3 x 256 MiB copy, 3 x global + vec (STATE), 3 x local only; random (clip, time)"}
 
 
 if __name__ == "__main__":

@@ -28,6 +28,9 @@ Fixtures (all float32 unless noted):
                              SkeletonMotion._compute_angular_velocity / _compute_velocity, smoothed and raw, fps 30 and 120
   kinematics_adversarial.npz the 18 hostile quaternion families (8 frames each) on Hu v5 and VTRDyn-59 through
                              cal_forward_kinematics / cal_local_rotation / SkeletonState FK and local_rotation
+  motion_sample.npz          8 queries per family of tests/motion_sample_ref.py (the hostile rotation sequences, the
+                             slerp threshold pairs, the time families) through quat_slerp, quat_normalize and torch's
+                             (1 - b) * a + b * c: the queries, the gathered rows and the reference's outputs
 """
 from __future__ import annotations
 
@@ -767,6 +770,41 @@ def gen_kinematics_adversarial(ref, torch, per_family=8):
     return out
 
 
+def gen_motion_sample(ref, torch):
+    """The reference's quat_slerp (transform3d.py:152-174), quat_normalize (rotation3d.py:92-98) and torch's
+    (1 - b) * a + b * c on the rows the index rule gathers, in chunks of 16 rows like the other fixtures.  Invalid
+    queries are recorded with rows 0 and are not compared beyond their flag (the reference has no such notion)."""
+    for d in ("tests", "oracle"):
+        sys.path.insert(0, os.path.join(REPO, d))
+    import motion_sample_ref as msr
+    r3, t3 = ref.rotation3d, ref.transform3d
+    out, J = {}, msr.FIXTURE_J
+    cases = msr.fixture_cases()
+    out["families"] = np.array(list(cases))
+    for fam, (lib, clip, time) in cases.items():
+        valid, i0, i1, b = msr.index_rule(clip, time, lib["len"], lib["fps"])
+        st = lib["start"][np.where(valid, clip.astype(np.int64), 0)]
+        r0, r1 = np.where(valid, st + i0, 0), np.where(valid, st + i1, 0)
+        q0, q1 = lib["rot"][r0].reshape(-1, 4), lib["rot"][r1].reshape(-1, 4)
+        bq = np.repeat(b, J).reshape(-1, 1).astype(np.float32)
+        sl = [t3.quat_slerp(torch.from_numpy(q0[i:i + 16].copy()), torch.from_numpy(q1[i:i + 16].copy()),
+                            torch.from_numpy(bq[i:i + 16].copy())) for i in range(0, len(q0), 16)]
+        nm = [r3.quat_normalize(x) for x in sl]
+        bt = torch.from_numpy(b.astype(np.float32))[:, None]
+        ra, rc = torch.from_numpy(lib["root_t"][r0]), torch.from_numpy(lib["root_t"][r1])
+        va, vc = torch.from_numpy(lib["vec"][r0]) if lib["vec"] is not None else None, None
+        out[f"{fam}_clip"], out[f"{fam}_time"] = clip.astype(np.int32), time.astype(np.float32)
+        out[f"{fam}_valid"], out[f"{fam}_row0"], out[f"{fam}_row1"] = valid, r0.astype(np.int64), r1.astype(np.int64)
+        out[f"{fam}_b"], out[f"{fam}_q0"], out[f"{fam}_q1"] = b.astype(np.float32), q0, q1
+        out[f"{fam}_slerp"] = np.concatenate([t2n(x) for x in sl]).reshape(-1, J, 4)
+        out[f"{fam}_slerp_norm"] = np.concatenate([t2n(x) for x in nm]).reshape(-1, J, 4)
+        out[f"{fam}_root_t"] = t2n((1 - bt) * ra + bt * rc)
+        if va is not None:
+            vc = torch.from_numpy(lib["vec"][r1])
+            out[f"{fam}_vec"] = t2n((1 - bt[:, None]) * va + bt[:, None] * vc)
+    return out
+
+
 def gen_kat(ref, torch):
     """retarget/rotation_test.py:95-152 restated as data: arm segments from known joint angles."""
     r3 = ref.rotation3d
@@ -827,6 +865,7 @@ def main() -> None:
         "other_solvers_adversarial": lambda: gen_other_solvers_adversarial(ref, torch),
         "motion_adversarial": lambda: gen_motion_adversarial(ref, torch),
         "kinematics_adversarial": lambda: gen_kinematics_adversarial(ref, torch),
+        "motion_sample": lambda: gen_motion_sample(ref, torch),
     }
     only = set(sys.argv[1:])
     for name, fn in jobs.items():
