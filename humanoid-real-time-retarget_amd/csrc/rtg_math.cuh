@@ -1239,6 +1239,25 @@ RTG_DEV void u_rot(Svd3 &z, bool p1, float c, float s)
         z.u[k + 6] = p1 ? y : z.u[k + 6];
     }
 }
+// la_rot on a pair of slots (lo, hi) held in chase order (la_bdsqr3), both directions as one instruction sequence
+// with fixed destinations.  Top to bottom (mir false) it is la_rot(lo, hi, c, s); bottom to top the pair is
+// (x, y) = (hi, lo) and the sine is negated (SBDSQR stores -SN): la_rot(hi, lo, c, -s).  Written out,
+//   !mir: lo' = fma(s, hi, c lo),      hi' = fma(c, hi, (-s) lo)
+//    mir: lo' = fma(c, lo, s hi),      hi' = fma(-s, lo, c hi)
+// i.e. lo' = fma(P, Q, R S), hi' = fma(P2, Q, R2 S) with Q = mir ? lo : hi, S = mir ? hi : lo; -(s x) and (-s) x
+// are the same bits.  Two selects per pair, four per rotation (shared by its three pairs), none on the outputs.
+struct SlotRot {
+    bool mir;
+    float P, R, P2, R2;
+    RTG_DEV SlotRot(bool mir_, float c, float s)   // s: the sine before SBDSQR's negation
+        : mir(mir_), P(mir_ ? c : s), R(mir_ ? s : c), P2(mir_ ? -s : c), R2(mir_ ? c : -s) {}
+    RTG_DEV void operator()(float &lo, float &hi) const
+    {
+        const float Q = mir ? lo : hi, S = mir ? hi : lo;
+        lo = __builtin_fmaf(P, Q, R * S);
+        hi = __builtin_fmaf(P2, Q, R2 * S);
+    }
+};
 // the end of SBDSQR: singular values made positive, then sorted decreasing, with their VT rows / U columns
 RTG_DEV void la_bdsqr3_sort(float &d1, float &d2, float &d3, Svd3 &z)
 {
@@ -1305,100 +1324,129 @@ RTG_DEV void la_bdsqr3(float &d1, float &d2, float &d3, float e1, float e2, Svd3
     sminoa = fdiv(sminoa, 1.73205078f);   // / sqrt(real(3))
     const float thresh = fmaxf(tol * sminoa, 6.0f * (3.0f * (3.0f * unfl)));
     int m = 3, iter = -1, iterdivn = 0;
-    bool mir = false, fresh = true;   // mir: IDIR = 2; fresh: (ll, m) = (1, 3) differs from (oldll, oldm)
+    // mir: IDIR = 2.  SBDSQR picks the direction when (ll, m) = (1, 3) is new, from |d1| >= |d3|; nothing changes d
+    // before the first sweep and m never returns to 3 after it, so the entry values decide it once.
+    const bool mir = !(fabsf(d1) >= fabsf(d3));
+    // The whole loop works in chase order: slot k of (D1, D2, D3), of VT's rows and columns and of U's rows and
+    // columns holds index mir ? 2 - k : k, and (E1, E2) = mir ? (e2, e1) : (e1, e2) -- the IDIR = 1 form of the
+    // (mirrored) bidiagonal.  U = VT = I on entry is its own mirror (rows and columns both reversed); rows of U
+    // and columns of VT are never mixed, so reversing them too costs nothing in the loop.  Index order returns
+    // once, after the loop.
+    float D1 = mir ? d3 : d1, D2 = d2, D3 = mir ? d1 : d3, E1 = mir ? e2 : e1, E2 = mir ? e1 : e2;
     // A lane whose last step is a 2x2 block leaves the loop with blk set, and the block (SLASV2 + its two
     // rotations) runs once after the loop for every such lane: the lanes of a wave finish at different sweeps,
     // and inside the loop the block would execute once per distinct exit sweep.  Same operations, same values.
-    bool blk = false, p1 = false;
-    for (;;) {
-        if (m <= 1) break;
-        if (iter >= 3) { iter -= 3; if (++iterdivn >= 18) break; }   // no convergence: INFO > 0 (never seen)
-        if (m == 2) {                       // block (1, 2)
-            if (fabsf(e1) <= thresh) break;
-            blk = true;
-            break;
+    bool blk = false, p1 = false, run = true;
+    // One structured loop (no break / continue: every exit carries the same live values, so the loop head holds no
+    // copies of the 18 U / VT entries): a pass classifies the lane, and only a lane that sweeps enters the body.
+    while (run) {
+        bool sweep = false;
+        float shift = 0.0f;
+        const float e1t = mir ? E2 : E1, e2t = mir ? E1 : E2;   // e1, e2 in index order
+        bool capped = false;
+        if (iter >= 3) { iter -= 3; capped = ++iterdivn >= 18; }   // no convergence: INFO > 0 (never seen)
+        if (capped) run = false;
+        else if (m == 2) {                       // block (1, 2)
+            blk = !(fabsf(e1t) <= thresh);
+            run = false;
         }
-        if (fabsf(e2) <= thresh) { e2 = 0.0f; m = 2; continue; }
-        if (fabsf(e1) <= thresh) { e1 = 0.0f; blk = true; p1 = true; break; }   // split at E(1): block (2, 3)
-        const float smax = fmaxf(fmaxf(fabsf(d3), fmaxf(fabsf(d2), fabsf(e2))), fmaxf(fabsf(d1), fabsf(e1)));
-        if (fresh) { mir = !(fabsf(d1) >= fabsf(d3)); fresh = false; }
-        // the IDIR = 1 form on (D1, D2, D3; E1, E2) = mir ? (d3, d2, d1; e2, e1) : (d1, d2, d3; e1, e2)
-        float D1 = mir ? d3 : d1, D2 = d2, D3 = mir ? d1 : d3, E1 = mir ? e2 : e1, E2 = mir ? e1 : e2;
-        bool zeroed = false;
-        float smin;
-        if (fabsf(E2) <= fabsf(tol) * fabsf(D3)) { E2 = 0.0f; zeroed = true; }
+        // deflation at E(2) and the split at E(1) store a zero that nothing reads again (the block (1, 2) reads e1
+        // alone, the block (2, 3) e2 alone): not stored
+        else if (fabsf(e2t) <= thresh) m = 2;
+        else if (fabsf(e1t) <= thresh) { blk = true; p1 = true; run = false; }   // split at E(1): block (2, 3)
         else {
-            float mu = fabsf(D1);
-            smin = mu;
-            if (fabsf(E1) <= tol * mu) { E1 = 0.0f; zeroed = true; }
+            // max over a set (a NaN only ever yields to the other operand): the same value in either order
+            const float smax = fmaxf(fmaxf(fabsf(D3), fmaxf(fabsf(D2), fabsf(E2))), fmaxf(fabsf(D1), fabsf(E1)));
+            bool zeroed = false;
+            float smin;
+            if (fabsf(E2) <= fabsf(tol) * fabsf(D3)) { E2 = 0.0f; zeroed = true; }
             else {
-                mu = fabsf(D2) * fdiv(mu, mu + fabsf(E1));
-                smin = fminf(smin, mu);
-                if (fabsf(E2) <= tol * mu) { E2 = 0.0f; zeroed = true; }
+                float mu = fabsf(D1);
+                smin = mu;
+                if (fabsf(E1) <= tol * mu) { E1 = 0.0f; zeroed = true; }
                 else {
-                    mu = fabsf(D3) * fdiv(mu, mu + fabsf(E2));
+                    mu = fabsf(D2) * fdiv(mu, mu + fabsf(E1));
                     smin = fminf(smin, mu);
+                    if (fabsf(E2) <= tol * mu) { E2 = 0.0f; zeroed = true; }
+                    else {
+                        mu = fabsf(D3) * fdiv(mu, mu + fabsf(E2));
+                        smin = fminf(smin, mu);
+                    }
+                }
+            }
+            if (!zeroed) {   // a zeroed lane is done with this pass (its e is already in place)
+                sweep = true;
+                if (!((3.0f * tol) * fdiv(smin, smax) <= fmaxf(eps, 0.01f * tol))) {
+                    const float sll = fabsf(D1);
+                    shift = la_las2_min(D2, E2, D3);
+                    if (sll > 0.0f) { const float q = fdiv(shift, sll); if (q * q < eps) shift = 0.0f; }
                 }
             }
         }
-        if (zeroed) {
-            e1 = mir ? E2 : E1;
-            e2 = mir ? E1 : E2;
-            continue;
+        if (sweep) {
+            iter += 2;
+            // rotations of the two steps: (ac, as) / (bc, bs) at the first, (cc, cs) / (dc, ds) at the second
+            float ac, as, bc, bs, cc, cs, dc, ds;
+            if (shift == 0.0f) {
+                float r, h;
+                la_lartg(D1, E1, ac, as, r);                 // cs = 1
+                la_lartg(r, D2 * as, bc, bs, D1);            // oldcs = 1
+                la_lartg(D2 * ac, E2, cc, cs, r);
+                E1 = bs * r;
+                la_lartg(bc * r, D3 * cs, dc, ds, D2);
+                h = D3 * cc;
+                D3 = h * dc;
+                E2 = h * ds;
+            } else {
+                float f = (fabsf(D1) - shift) * (__builtin_copysignf(1.0f, D1) + fdiv(shift, D1)), g = E1, r;
+                la_lartg(f, g, ac, as, r);
+                f = ac * D1 + as * E1;
+                E1 = ac * E1 - as * D1;
+                g = as * D2;
+                D2 = ac * D2;
+                la_lartg(f, g, bc, bs, r);
+                D1 = r;
+                f = bc * E1 + bs * D2;
+                D2 = bc * D2 - bs * E1;
+                g = bs * E2;
+                E2 = bc * E2;
+                la_lartg(f, g, cc, cs, r);
+                E1 = r;
+                f = cc * D2 + cs * E2;
+                E2 = cc * E2 - cs * D2;
+                g = cs * D3;
+                D3 = cc * D3;
+                la_lartg(f, g, dc, ds, r);
+                D2 = r;
+                f = dc * E2 + ds * D3;
+                D3 = dc * D3 - ds * E2;
+                E2 = f;
+            }
+            if (fabsf(E2) <= thresh) E2 = 0.0f;
+            // IDIR = 1: VT pairs (1,2) then (2,3) by (a, c), U by (b, d).  IDIR = 2: VT (2,3) then (1,2) by (b, d),
+            // U by (a, c), sines negated.  In chase order both are slots (0,1) then (1,2).
+            const SlotRot va(mir, mir ? bc : ac, mir ? bs : as), vc(mir, mir ? dc : cc, mir ? ds : cs);
+            const SlotRot ub(mir, mir ? ac : bc, mir ? as : bs), ud(mir, mir ? cc : dc, mir ? cs : ds);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) va(z.vt[3 * k], z.vt[1 + 3 * k]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) vc(z.vt[1 + 3 * k], z.vt[2 + 3 * k]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ub(z.u[k], z.u[k + 3]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ud(z.u[k + 3], z.u[k + 6]);
         }
-        float shift = 0.0f;
-        if (!((3.0f * tol) * fdiv(smin, smax) <= fmaxf(eps, 0.01f * tol))) {
-            const float sll = fabsf(D1);
-            shift = la_las2_min(D2, E2, D3);
-            if (sll > 0.0f) { const float q = fdiv(shift, sll); if (q * q < eps) shift = 0.0f; }
-        }
-        iter += 2;
-        // rotations of the two steps: (ac, as) / (bc, bs) at the first, (cc, cs) / (dc, ds) at the second
-        float ac, as, bc, bs, cc, cs, dc, ds;
-        if (shift == 0.0f) {
-            float r, h;
-            la_lartg(D1, E1, ac, as, r);                 // cs = 1
-            la_lartg(r, D2 * as, bc, bs, D1);            // oldcs = 1
-            la_lartg(D2 * ac, E2, cc, cs, r);
-            E1 = bs * r;
-            la_lartg(bc * r, D3 * cs, dc, ds, D2);
-            h = D3 * cc;
-            D3 = h * dc;
-            E2 = h * ds;
-        } else {
-            float f = (fabsf(D1) - shift) * (__builtin_copysignf(1.0f, D1) + fdiv(shift, D1)), g = E1, r;
-            la_lartg(f, g, ac, as, r);
-            f = ac * D1 + as * E1;
-            E1 = ac * E1 - as * D1;
-            g = as * D2;
-            D2 = ac * D2;
-            la_lartg(f, g, bc, bs, r);
-            D1 = r;
-            f = bc * E1 + bs * D2;
-            D2 = bc * D2 - bs * E1;
-            g = bs * E2;
-            E2 = bc * E2;
-            la_lartg(f, g, cc, cs, r);
-            E1 = r;
-            f = cc * D2 + cs * E2;
-            E2 = cc * E2 - cs * D2;
-            g = cs * D3;
-            D3 = cc * D3;
-            la_lartg(f, g, dc, ds, r);
-            D2 = r;
-            f = dc * E2 + ds * D3;
-            D3 = dc * D3 - ds * E2;
-            E2 = f;
-        }
-        if (fabsf(E2) <= thresh) E2 = 0.0f;
-        d1 = mir ? D3 : D1; d2 = D2; d3 = mir ? D1 : D3;
-        e1 = mir ? E2 : E1; e2 = mir ? E1 : E2;
-        // IDIR = 1: VT pairs (1,2) then (2,3) by (a, c), U by (b, d).  IDIR = 2: VT (2,3) then (1,2) by (b, d),
-        // U by (a, c), sines negated.
-        vt_rot(z, mir, mir ? bc : ac, mir ? -bs : as);
-        vt_rot(z, !mir, mir ? dc : cc, mir ? -ds : cs);
-        u_rot(z, mir, mir ? ac : bc, mir ? -as : bs);
-        u_rot(z, !mir, mir ? cc : dc, mir ? -cs : ds);
+    }
+    // back to index order: (d, e) unmirrored, U and VT turned by half a turn (rows and columns both reversed)
+    d1 = mir ? D3 : D1; d2 = D2; d3 = mir ? D1 : D3;
+    e1 = mir ? E2 : E1; e2 = mir ? E1 : E2;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float v0 = z.vt[i], v1 = z.vt[8 - i], u0 = z.u[i], u1 = z.u[8 - i];
+        z.vt[i] = mir ? v1 : v0;
+        z.vt[8 - i] = mir ? v0 : v1;
+        z.u[i] = mir ? u1 : u0;
+        z.u[8 - i] = mir ? u0 : u1;
     }
     if (blk) {   // 2x2 block (p1 ? 2 : 1, +1)
         float sigmn, sigmx, sinr, cosr, sinl, cosl;
