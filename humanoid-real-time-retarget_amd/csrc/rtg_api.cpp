@@ -463,6 +463,59 @@ int rtg_dof_fit_f32(rtg_dof_model_t m, const float *target_pos, const float *wei
     return RTG_OK;
 }
 
+int rtg_dof_fit_root_f32(rtg_dof_model_t m, const float *target_pos, const float *weight, const float *root_rot,
+                         const float *root_t, const float *dof_in, int64_t B, int clip, int32_t fit_root, int32_t iters,
+                         float lr, float lr_root_t, float lr_root_rot, float beta1, float beta2, float eps,
+                         int32_t step0, float *mom1, float *mom2, float *root_state, float *dof_out,
+                         float *root_rot_out, float *root_t_out, float *loss, float *grad, float *grad_root,
+                         rtg_stream_t stream)
+{
+    const char *fn = "rtg_dof_fit_root_f32";
+    // everything that needs no handle first
+    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)B);
+    if (fit_root & ~(RTG_FIT_ROOT_T | RTG_FIT_ROOT_ROT))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: fit_root=%d has unknown bits", fn, fit_root);
+    if (iters < 0 || iters > RTG_DOF_FIT_MAX_ITERS)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: iters=%d is outside 0..%d", fn, iters, RTG_DOF_FIT_MAX_ITERS);
+    if (step0 < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: step0=%d < 0", fn, step0);
+    if (!std::isfinite(lr) || !std::isfinite(eps))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: lr=%g, eps=%g must be finite", fn, (double)lr, (double)eps);
+    if (!std::isfinite(lr_root_t) || !std::isfinite(lr_root_rot) || lr_root_t < 0.0f || lr_root_rot < 0.0f)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: lr_root_t=%g, lr_root_rot=%g must be finite and not negative", fn,
+                    (double)lr_root_t, (double)lr_root_rot);
+    if (!std::isfinite(beta1) || !std::isfinite(beta2) || beta1 < 0.0f || beta1 >= 1.0f || beta2 < 0.0f || beta2 >= 1.0f)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: betas (%g, %g) must lie in [0, 1)", fn, (double)beta1, (double)beta2);
+    if ((mom1 == nullptr) != (mom2 == nullptr))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both Adam moment buffers (m, v) or neither", fn);
+    if ((root_state == nullptr) != (mom1 == nullptr))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give root_state with the Adam moment buffers (m, v), or none of them", fn);
+    if (B > 0) {   // empty buffers have no address to give
+        if (!dof_out && !root_rot_out && !root_t_out && !loss && !grad && !grad_root)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: every output is NULL", fn);
+        if (!target_pos || !root_rot || !root_t) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    }
+    if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL model", fn);
+    if (clip && !m->has_limits)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: clip_angles requested but the model has no DOF limits", fn);
+    const int J = m->topo->J;
+    if (J > kGroupMaxJ)
+        return fail(RTG_ERR_UNSUPPORTED, "%s: serves models of 1..%d joints (this one has %d)", fn, kGroupMaxJ, J);
+    if (B == 0) return RTG_OK;
+    if (J > 1 && !dof_in) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    if (J == 1) {   // no angles: only the root can step; the kernel's unconditional first-element loads get readable memory
+        dof_in = root_rot;
+        mom1 = mom2 = dof_out = grad = nullptr;
+        if (!fit_root) iters = 0;
+        if (!root_rot_out && !root_t_out && !loss && !grad_root) return RTG_OK;
+    }
+    const DofView D{m->d_axis, m->d_lower, m->d_upper};
+    const DofFitArgs A{target_pos, weight, root_rot, root_t, dof_in, B, iters, step0, lr, beta1, beta2, eps,
+                       mom1, mom2, dof_out, loss, grad};
+    const DofFitRootArgs R{fit_root, lr_root_t, lr_root_rot, root_state, root_rot_out, root_t_out, grad_root};
+    RTG_TRY(launch_dof_fit_root(m->topo->view(), D, clip != 0, A, R, as_stream(stream)), "k_dof_fit_root");
+    return RTG_OK;
+}
+
 // ---------------------------------------------------------------- SkeletonState.retarget_to
 int rtg_retarget_plan_tables(const int32_t *src_parents, int32_t Js, const int32_t *tgt_parents, int32_t Jt,
                              const int32_t *src_joint, const int32_t *tgt_joint, int32_t K, int32_t *kept_src,

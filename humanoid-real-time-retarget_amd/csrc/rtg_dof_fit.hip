@@ -10,11 +10,20 @@
 // backwards (k_fk_bwd_group's sweep with ROT = false: a joint's contribution to its parent's rotation adjoint goes
 // into its own G row, a parent pulls its children's rows in ascending index order -- one order per sum, no atomics).
 // The lane that finishes joint j's reverse step holds d L / d a_j and owns that angle: it takes the Adam step for it
-// on the spot, so there is no gradient image and no separate update pass.  The root is given, not fitted: its rows
-// are written once and the reverse sweep stops above it.
+// on the spot, so there is no gradient image and no separate update pass.  In k_dof_fit_group the root is given, not
+// fitted: its rows are written once and the reverse sweep stops above it.
+//
+// k_dof_fit_root_group (rtg_dof_fit_root_f32) is the same tile with the floating base among the parameters (ROOT):
+// the root translation t and rotation q of a frame and their moments live in a root image of 21 floats per frame.  The
+// lane the schedule gives the root presets G_0 = q / max(|q|, 1e-9) (no sign flip; a given rotation stays as it is)
+// and P_0 = t at the top of each forward sweep, the residual adjoint of row 0 is kept, and the reverse sweep ends at
+// the root: that lane pulls its children (k_fk_bwd_group's j == 0), holds dL/dt and dL/dG_0, applies the
+// normalisation's adjoint (g - (g.G_0) G_0) / |q| and takes the 3 + 4 Adam steps, renormalising q after its step.
+// The fit_root mask is a launch argument (wave-uniform branches in that one lane's work).
 //
 // LDS images of a tile: FitImages below (every image starts 16-byte aligned).
 // 33-link Hu, F = 16 (10 steps): 29.3 KiB; a 64-joint chain, F = 8, 64 steps: 43.9 KiB (the largest: gsteps <= J).
+// With the root image and the two more step sizes per Adam step: 31.1 KiB (still 5 tiles per CU) and 45.1 KiB.
 //
 // Arithmetic: as in rtg_fk_grad.hip no operation order is owed to a reference (explicit fmaf, the device sincosf,
 // -ffp-contract=fast); the forward here is the float32 restatement of rtg_dof_fk_f32's, not its bit-exact f64 sincos.
@@ -29,7 +38,7 @@
 
 namespace rtg {
 
-constexpr size_t kFitMaxLdsBytes = 64 * 1024;   // the dynamic-LDS attribute the launcher sets (J = 64, 64 steps: 43.9 KiB)
+constexpr size_t kFitMaxLdsBytes = 64 * 1024;   // the dynamic-LDS attribute the launcher sets (J = 64, 64 steps: 45.1 KiB)
 
 // beta^t in float64 by squaring: a function of (beta, t) alone, so a launch that starts at step0 = k takes the very
 // step the k-th iteration of a longer launch takes
@@ -54,9 +63,14 @@ struct FitImages {
     GEnt *sch;       // [gsteps L] the schedule
     int *nsib;       // [J] the next-sibling table
     float *lossp;    // [64] loss partials
-    float *adam;     // [128] {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} of 64 steps
+    float *adam;     // [128] {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} of 64 steps; root: [256], with
+                     // {lr_root_t, lr_root_rot} / (1 - beta1^t) behind them
+    f4v *Rq;         // root: [F] the root rotations, the iterate where fitted (as given until the first step)
+    float *Rt;       // root: [F 3] the root translations, likewise
+    float *Rs;       // root: [F 14] root_state's rows {m_t, m_q, v_t, v_q}; in the evaluation sweep after the last step
+                     // (the moments are out by then) [F 7]: grad_root's rows {dL/dt, dL/dq}
     size_t floats;
-    __host__ __device__ FitImages(float *base, int J, int F, int steps)
+    __host__ __device__ FitImages(float *base, int J, int F, int steps, bool root)
     {
         LdsCarve c(base);
         G = c.take<f4v>((size_t)F * J);
@@ -69,14 +83,27 @@ struct FitImages {
         sch = c.take<GEnt>((size_t)steps * (64 / F));
         nsib = c.take<int>(J);
         lossp = c.take<float>(64);
-        adam = c.take<float>(128);
+        adam = c.take<float>(root ? 256 : 128);
+        Rq = c.take<f4v>(root ? F : 0);
+        Rt = c.take<float>(root ? 3 * F : 0);
+        Rs = c.take<float>(root ? 14 * F : 0);
         floats = c.floats;
     }
 };
 
-// the forward sweep: G and P of every joint below the root from the angles (the root's rows stay as loaded)
-template <bool CLIP, int F>
-RTG_DEV void fit_forward(const FitImages &I, int J, int gsteps, bool live, int fr, int sub)
+// G_0 = q / max(|q|, 1e-9) of a fitted root rotation: no sign flip (q and -q are one rotation and the iterate stays
+// continuous); NaN passes
+RTG_DEV f4v root_unit(f4v q)
+{
+    const float n = __builtin_sqrtf(fdot4(q_of(q), q_of(q)));
+    const float rn = 1.0f / (n < 1e-9f ? 1e-9f : n);
+    return f4v{q.x * rn, q.y * rn, q.z * rn, q.w * rn};
+}
+
+// the forward sweep: G and P of every joint below the root from the angles (the root's rows stay as loaded; ROOT: the
+// lane with the root's entry presets them from the root image, the rotation normalised where it is fitted)
+template <bool CLIP, int F, bool ROOT>
+RTG_DEV void fit_forward(const FitImages &I, int J, int gsteps, bool live, int fr, int sub, int fit_root)
 {
     using G = Grp<F>;
     const int base = fr * J, nd = J - 1;
@@ -85,6 +112,13 @@ RTG_DEV void fit_forward(const FitImages &I, int J, int gsteps, bool live, int f
         const GEnt e = en;
         if (s + 1 < gsteps) en = I.sch[(s + 1) * G::L + sub];   // the next step's entry: its latency under this step
         const int j = e.code & 0xFF, p = (e.code >> 8) & 0xFF;
+        if (ROOT && live && j == 0) {
+            const f4v q = I.Rq[fr];
+            I.G[base] = (fit_root & RTG_FIT_ROOT_ROT) ? root_unit(q) : q;
+            float *p0 = I.P + 3 * base;
+            const float *t0 = I.Rt + 3 * fr;
+            p0[0] = t0[0]; p0[1] = t0[1]; p0[2] = t0[2];
+        }
         if (live && j != 0xFF && j != 0) {
             const f4v t = I.tab[j];
             const AngleRot r = angle_rot<CLIP>(I.A[fr * nd + j - 1], __float_as_int(t.x), t.y, t.z);
@@ -102,9 +136,9 @@ RTG_DEV void fit_forward(const FitImages &I, int J, int gsteps, bool live, int f
     }
 }
 
-// positions -> residual adjoints in place (the root's row stays: it is not fitted); returns this lane's part of the
-// frame's loss, its joints in index order
-template <int F>
+// positions -> residual adjoints in place (the root's row stays where the root's adjoint is not taken; ROOT: it is
+// dL/dt's own term); returns this lane's part of the frame's loss, its joints in index order
+template <int F, bool ROOT>
 RTG_DEV float fit_residual(const FitImages &I, int J, bool live, int fr, int sub)
 {
     using G = Grp<F>;
@@ -116,7 +150,7 @@ RTG_DEV float fit_residual(const FitImages &I, int J, bool live, int fr, int sub
             const float *tj = I.T + 3 * (fr * J + j);
             const V d{pj[0] - tj[0], pj[1] - tj[1], pj[2] - tj[2]};
             acc = __builtin_fmaf(w, fdot3(d, d), acc);
-            if (j != 0) {
+            if (ROOT || j != 0) {
                 const float w2 = 2.0f * w;
                 pj[0] = w2 * d.x; pj[1] = w2 * d.y; pj[2] = w2 * d.z;
             }
@@ -129,12 +163,65 @@ RTG_DEV float fit_residual(const FitImages &I, int J, bool live, int fr, int sub
 struct AdamStep {
     float b1, omb1, b2, omb2, eps;
     float step, rbc2s;   // lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)
+    float step_t, step_q;   // ROOT: lr_root_t / (1 - beta1^t), lr_root_rot / (1 - beta1^t)
 };
 
+// torch.optim.Adam's step on one parameter: the moments in place, returns the new value
+RTG_DEV float adam_step(const AdamStep &S, float step, float g, float &m, float &v, float x)
+{
+    m = __builtin_fmaf(S.omb1, g, S.b1 * m);
+    v = __builtin_fmaf(S.omb2 * g, g, S.b2 * v);
+    return __builtin_fmaf(-step, m / __builtin_fmaf(__builtin_sqrtf(v), S.rbc2s, S.eps), x);
+}
+
+// The root's reverse step (one lane per frame): its children's rows pulled as k_fk_bwd_group's j == 0 does, giving
+// dL/dt (the root's own residual included) and dL/dG_0; a fitted rotation's gradient goes through G_0 = q / |q|: it is
+// tangent, (g - (g.G_0) G_0) / |q| (under the norm's clamp the divisor is a constant), a given one's is dL/dG_0 itself
+// (the unnormalised model, as rtg_dof_fk_backward_f32 reports it).  EVAL: grad_root's row into the Rs image, else the
+// Adam steps of the fitted blocks, q renormalised after its step.
+template <bool EVAL>
+RTG_DEV void fit_root_reverse(const FitImages &I, int J, int fr, int first_child, int fit_root, const AdamStep &S)
+{
+    const int base = fr * J;
+    V pb;
+    f4v g = child_pull(f4v{0.0f, 0.0f, 0.0f, 0.0f}, I.G, I.P, base, 0, first_child, I.nsib, pb);
+    const f4v q = I.Rq[fr];
+    if (fit_root & RTG_FIT_ROOT_ROT) {
+        const float n = __builtin_sqrtf(fdot4(q_of(q), q_of(q)));
+        if (!(n < 1e-9f)) {   // NaN takes the regular path and stays NaN
+            const f4v G0 = I.G[base];
+            const float r = 1.0f / n, d = fdot4(q_of(g), q_of(G0));
+            g = f4v{r * __builtin_fmaf(-d, G0.x, g.x), r * __builtin_fmaf(-d, G0.y, g.y), r * __builtin_fmaf(-d, G0.z, g.z),
+                    r * __builtin_fmaf(-d, G0.w, g.w)};
+        } else {
+            g = f4v{1e9f * g.x, 1e9f * g.y, 1e9f * g.z, 1e9f * g.w};
+        }
+    }
+    if (EVAL) {
+        float *o = I.Rs + 7 * fr;
+        o[0] = pb.x; o[1] = pb.y; o[2] = pb.z;
+        o[3] = g.x; o[4] = g.y; o[5] = g.z; o[6] = g.w;
+        return;
+    }
+    float *st = I.Rs + 14 * fr;   // {m_t(3), m_q(4), v_t(3), v_q(4)}
+    if (fit_root & RTG_FIT_ROOT_T) {
+        float *t = I.Rt + 3 * fr;
+        t[0] = adam_step(S, S.step_t, pb.x, st[0], st[7], t[0]);
+        t[1] = adam_step(S, S.step_t, pb.y, st[1], st[8], t[1]);
+        t[2] = adam_step(S, S.step_t, pb.z, st[2], st[9], t[2]);
+    }
+    if (fit_root & RTG_FIT_ROOT_ROT) {
+        const f4v u{adam_step(S, S.step_q, g.x, st[3], st[10], q.x), adam_step(S, S.step_q, g.y, st[4], st[11], q.y),
+                    adam_step(S, S.step_q, g.z, st[5], st[12], q.z), adam_step(S, S.step_q, g.w, st[6], st[13], q.w)};
+        I.Rq[fr] = root_unit(u);
+    }
+}
+
 // the reverse sweep; EVAL: the gradient rows into the M image, else the Adam step of each angle where its gradient
-// appears
-template <bool CLIP, bool EVAL, int F>
-RTG_DEV void fit_reverse(const FitImages &I, int J, int gsteps, bool live, int fr, int sub, const AdamStep &S)
+// appears; ROOT: the sweep ends with the root's step (fit_root_reverse)
+template <bool CLIP, bool EVAL, int F, bool ROOT>
+RTG_DEV void fit_reverse(const FitImages &I, int J, int gsteps, bool live, int fr, int sub, const AdamStep &S,
+                         int fit_root)
 {
     using G = Grp<F>;
     const int base = fr * J, nd = J - 1;
@@ -165,12 +252,17 @@ RTG_DEV void fit_reverse(const FitImages &I, int J, int gsteps, bool live, int f
                 I.A[i] = __builtin_fmaf(-S.step, m / __builtin_fmaf(__builtin_sqrtf(v), S.rbc2s, S.eps), ang);
             }
         }
+        if (ROOT && live && j == 0) fit_root_reverse<EVAL>(I, J, fr, (e.code >> 16) & 0xFF, fit_root, S);
         wave_sync();   // this step's rows before the next step's parents pull them (other lanes)
     }
 }
 
-template <bool CLIP, int F>
-__global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, DofFitArgs A)
+using RootStateRows = LaneRows<float, 4>;   // a tile's root_state rows: 14 F <= 256 floats
+
+// one tile of the fit; ROOT: the root's rows come from the root image and its adjoints are taken (R: the root's
+// arguments, not looked at otherwise)
+template <bool CLIP, int F, bool ROOT>
+RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs &A, const DofFitRootArgs &R)
 {
     extern __shared__ __attribute__((aligned(16))) float ft_lds[];
     using G = Grp<F>;
@@ -178,17 +270,21 @@ __global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, Dof
     const int64_t f0 = (int64_t)blockIdx.x * F;
     const int nfr = tile_frames<F>(A.B, f0);
     const int npos = 3 * nfr * J, nang = nfr * nd;
-    const FitImages I(ft_lds, J, F, T.gsteps);
+    const FitImages I(ft_lds, J, F, T.gsteps, ROOT);
     float *lossp = I.lossp, *adam = I.adam;
+    const int fit_root = ROOT ? R.fit_root : 0;
 
     // every global load of the tile first (a lane past the rows re-reads element 0), then the LDS images
     const bool state = A.m != nullptr;
+    const bool rstate = ROOT && fit_root != 0 && R.state != nullptr;   // nothing fitted: not read, not written
     ScalarRows<F> ang, m0 = {}, v0 = {};
+    RootStateRows rs = {};
     ang.load(A.dof_in + f0 * nd, nang);   // J = 1: no angles, the host passes a readable dummy
     if (state) {
         m0.load(A.m + f0 * nd, nang);
         v0.load(A.v + f0 * nd, nang);
     }
+    if (rstate) rs.load(R.state + f0 * 14, 14 * nfr);
     const float *trow = A.target_pos + f0 * J * 3;
     PosRows<F> tp;
     tp.load(trow, npos);
@@ -200,7 +296,13 @@ __global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, Dof
     m0.store(I.M, nang);
     v0.store(I.V, nang);
     tp.to_lds(I.T, trow, npos);
-    root_preset(I.G, I.P, J, nfr, rr, rt);   // the root rotation, unnormalised (hu_forward_model.py:24)
+    if (ROOT) {   // the root image; fit_forward presets the root's rows from it
+        if (lane < nfr) I.Rq[lane] = rr;
+        if (lane < 3 * nfr) I.Rt[lane] = rt;
+        rs.store(I.Rs, 14 * nfr);
+    } else {
+        root_preset(I.G, I.P, J, nfr, rr, rt);   // the root rotation, unnormalised (hu_forward_model.py:24)
+    }
     wave_sync();
 
     const int fr = lane >> G::LOG_L, sub = lane & (G::L - 1);
@@ -213,18 +315,31 @@ __global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, Dof
     S.eps = A.eps;
     S.step = 0.0f;
     S.rbc2s = 0.0f;
+    S.step_t = 0.0f;
+    S.step_q = 0.0f;
     for (int k = 1; k <= A.iters; ++k) {   // wave-uniform; no global memory traffic inside
         if (((k - 1) & 63) == 0) {   // the bias corrections of the next 64 steps, one step per lane (float64)
             const int t = A.step0 + k + lane;
-            adam[2 * lane] = (float)((double)A.lr / (1.0 - pow_int((double)A.beta1, t)));
+            if (ROOT) {
+                const double bc1 = 1.0 - pow_int((double)A.beta1, t);
+                adam[2 * lane] = (float)((double)A.lr / bc1);
+                adam[128 + 2 * lane] = (float)((double)R.lr_t / bc1);
+                adam[128 + 2 * lane + 1] = (float)((double)R.lr_rot / bc1);
+            } else {
+                adam[2 * lane] = (float)((double)A.lr / (1.0 - pow_int((double)A.beta1, t)));
+            }
             adam[2 * lane + 1] = (float)(1.0 / __builtin_sqrt(1.0 - pow_int((double)A.beta2, t)));
             wave_sync();
         }
         S.step = adam[2 * ((k - 1) & 63)];
         S.rbc2s = adam[2 * ((k - 1) & 63) + 1];
-        fit_forward<CLIP, F>(I, J, T.gsteps, live, fr, sub);
-        (void)fit_residual<F>(I, J, live, fr, sub);
-        fit_reverse<CLIP, false, F>(I, J, T.gsteps, live, fr, sub, S);
+        if (ROOT) {
+            S.step_t = adam[128 + 2 * ((k - 1) & 63)];
+            S.step_q = adam[128 + 2 * ((k - 1) & 63) + 1];
+        }
+        fit_forward<CLIP, F, ROOT>(I, J, T.gsteps, live, fr, sub, fit_root);
+        (void)fit_residual<F, ROOT>(I, J, live, fr, sub);
+        fit_reverse<CLIP, false, F, ROOT>(I, J, T.gsteps, live, fr, sub, S, fit_root);
     }
 
     // the iterate and its state out (coalesced), then loss and gradient there by one more sweep
@@ -233,10 +348,15 @@ __global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, Dof
         ScalarRows<F>::copy_out(I.M, A.m + f0 * nd, nang);
         ScalarRows<F>::copy_out(I.V, A.v + f0 * nd, nang);
     }
-    if (!A.loss && !A.grad) return;
+    if (ROOT) {   // a given block, or iters == 0: the input's bits
+        if (R.rot_out && lane < nfr) reinterpret_cast<f4v *>(R.rot_out)[f0 + lane] = I.Rq[lane];
+        if (R.t_out && lane < 3 * nfr) R.t_out[f0 * 3 + lane] = I.Rt[lane];
+        if (rstate) RootStateRows::copy_out(I.Rs, R.state + f0 * 14, 14 * nfr);
+    }
+    if (!A.loss && !A.grad && !(ROOT && R.grad)) return;
     wave_sync();   // the M image is read out before the evaluation sweep writes gradients into it
-    fit_forward<CLIP, F>(I, J, T.gsteps, live, fr, sub);
-    const float part = fit_residual<F>(I, J, live, fr, sub);
+    fit_forward<CLIP, F, ROOT>(I, J, T.gsteps, live, fr, sub, fit_root);
+    const float part = fit_residual<F, ROOT>(I, J, live, fr, sub);
     if (A.loss) {
         lossp[lane] = part;
         wave_sync();
@@ -247,26 +367,58 @@ __global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, Dof
             A.loss[f0 + lane] = l;
         }
     }
-    if (A.grad) {
-        fit_reverse<CLIP, true, F>(I, J, T.gsteps, live, fr, sub, S);
-        ScalarRows<F>::copy_out(I.M, A.grad + f0 * nd, nang);
+    if (A.grad || (ROOT && R.grad)) {
+        fit_reverse<CLIP, true, F, ROOT>(I, J, T.gsteps, live, fr, sub, S, fit_root);
+        if (A.grad) ScalarRows<F>::copy_out(I.M, A.grad + f0 * nd, nang);
+        if (ROOT && R.grad) RootStateRows::copy_out(I.Rs, R.grad + f0 * 7, 7 * nfr);
     }
+}
+
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, DofFitArgs A)
+{
+    dof_fit_tile<CLIP, F, false>(T, D, A, DofFitRootArgs{});
+}
+
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_root_group(TopoView T, DofView D, DofFitArgs A, DofFitRootArgs R)
+{
+    dof_fit_tile<CLIP, F, true>(T, D, A, R);
+}
+
+template <bool ROOT>
+static hipError_t launch_fit(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A, const DofFitRootArgs &R,
+                             hipStream_t s)
+{
+    if (!T.gsched) return hipErrorInvalidValue;   // J > kGroupMaxJ: the caller reports it as unsupported
+    const int F = T.gF;
+    const size_t lds = sizeof(float) * FitImages(nullptr, T.J, F, T.gsteps, ROOT).floats;
+    if (lds > kFitMaxLdsBytes) return hipErrorInvalidValue;
+    hipError_t attr = hipSuccess;
+    group_dispatch(F, [&](auto f, auto cl) {
+        if constexpr (ROOT) {
+            attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_root_group<cl(), f()>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
+            if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_root_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A, R);
+        } else {
+            attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_group<cl(), f()>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
+            if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A);
+        }
+    }, clip);
+    if (attr != hipSuccess) return attr;
+    return hipGetLastError();
 }
 
 hipError_t launch_dof_fit(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A, hipStream_t s)
 {
-    if (!T.gsched) return hipErrorInvalidValue;   // J > kGroupMaxJ: the caller reports it as unsupported
-    const int F = T.gF;
-    const size_t lds = sizeof(float) * FitImages(nullptr, T.J, F, T.gsteps).floats;
-    if (lds > kFitMaxLdsBytes) return hipErrorInvalidValue;
-    hipError_t attr = hipSuccess;
-    group_dispatch(F, [&](auto f, auto cl) {
-        attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_group<cl(), f()>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
-        if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A);
-    }, clip);
-    if (attr != hipSuccess) return attr;
-    return hipGetLastError();
+    return launch_fit<false>(T, D, clip, A, DofFitRootArgs{}, s);
+}
+
+hipError_t launch_dof_fit_root(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
+                               const DofFitRootArgs &R, hipStream_t s)
+{
+    return launch_fit<true>(T, D, clip, A, R, s);
 }
 
 }  // namespace rtg

@@ -104,6 +104,15 @@ struct DofFitArgs {
     float *m, *v, *dof_out, *loss, *grad;
 };
 hipError_t launch_dof_fit(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A, hipStream_t s);
+// rtg_dof_fit_root_f32: the same launch with the floating base among the parameters.  A's root_rot / root_t are the
+// start (or given) values; fit_root: RTG_FIT_ROOT_* bits; state: root_state (B,14); grad: grad_root (B,7)
+struct DofFitRootArgs {
+    int32_t fit_root;
+    float lr_t, lr_rot;
+    float *state, *rot_out, *t_out, *grad;
+};
+hipError_t launch_dof_fit_root(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
+                               const DofFitRootArgs &R, hipStream_t s);
 // SkeletonState.retarget_to (poselib skeleton3d.py:742-889) as one launch, rtg_retarget_to.hip.
 // The host tables of a mapping of K (source joint, target joint) pairs: S_red / T_red are the trees with only the
 // mapped joints kept, each hung from its nearest kept ancestor (drop_nodes_by_names, :226-259).

@@ -70,6 +70,29 @@ class HuForwardModel(BaseForwardModel):
         out = (shaped(dof), loss.to(dev), new_state)
         return out + (shaped(res[3]),) if return_grad else out
 
+    def fit_pose(self, target_positions, motion_root_translation, motion_root_rotation, motion_joint_angles=None,
+                 weight=None, iters=32, lr=0.02, lr_root_t=None, lr_root_rot=None, fit_root_t=True, fit_root_rot=True,
+                 betas=(0.9, 0.999), eps=1e-8, clip_angles=True, state=None, return_grad=False):
+        """fit_keypoints with the floating base among the parameters (ops.pose_fit): mocap keypoints come from a body
+        of other proportions, and with the root pinned the legs cannot reach them.  (L, J, 3) targets, (L, 3) root
+        translation and (L, 1, 4) root rotation to start from (or given, where fit_root_t / fit_root_rot is False),
+        (L, J-1, 1) starting angles (default: zeros) -> ((L, J-1, 1) angles, (L, 3) root translation, (L, 1, 4) root
+        rotation, (L,) loss, state[, (L, J-1, 1) gradient, (L, 7) root gradient {dL/dt, dL/dq}]); ``state`` from an
+        earlier call continues its optimiser.  The fitted rotation comes back unit."""
+        if clip_angles and not self._model.has_limits:
+            raise ValueError("clip_angles needs DOF limits with one entry per DOF")
+        dev = home_device(target_positions, motion_root_translation, motion_root_rotation)
+        n = self.num_joints - 1
+        res = ops.pose_fit(self._model, target_positions, motion_root_rotation, motion_root_translation,
+                           dof0=motion_joint_angles, weight=weight, iters=iters, lr=lr, lr_root_t=lr_root_t,
+                           lr_root_rot=lr_root_rot, fit_root_t=fit_root_t, fit_root_rot=fit_root_rot, betas=betas,
+                           eps=eps, clip=bool(clip_angles), state=state, return_grad=return_grad)
+        lead = tuple(res.loss.shape)
+        shaped = lambda a: a.reshape(lead + (n, 1)).to(dev)
+        out = (shaped(res.dof), res.root_t.to(dev), res.root_rot.reshape(lead + (1, 4)).to(dev), res.loss.to(dev),
+               res.state)
+        return out + (shaped(res.grad), res.grad_root.to(dev)) if return_grad else out
+
     def _clip_angles(self, motion_joint_angles):
         """:27-33, forward value: (clamp(a, lo, hi) - a) + a, elementwise on the angles' device."""
         a = motion_joint_angles

@@ -6,6 +6,7 @@ per op; all arithmetic happens in librtg_hip.so.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import functools
 from typing import Sequence
@@ -515,6 +516,107 @@ class _KeypointLoss(torch.autograd.Function):
     def backward(ctx, grad_loss):
         (grad,) = ctx.saved_tensors
         return None, None, grad * grad_loss.unsqueeze(-1), None, None, None, None
+
+
+FIT_ROOT_T, FIT_ROOT_ROT = 1, 2   # rtg.h RTG_FIT_ROOT_*
+
+PoseFit = collections.namedtuple("PoseFit", "dof root_rot root_t loss state")
+PoseFitGrad = collections.namedtuple("PoseFitGrad", "dof root_rot root_t loss state grad grad_root")
+
+
+def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_root_t=0.0, lr_root_rot=0.0,
+                 betas=(0.9, 0.999), eps=1e-8, step0=0, m=None, v=None, root_state=None, want_iterate=False,
+                 want_loss=True, want_grad=False):
+    """rtg_dof_fit_root_f32 on prepared tensors; m, v, root_state are updated in place.  Returns (dof_out, root_rot_out,
+    root_t_out, loss, grad, grad_root), None where not asked for."""
+    lead = tuple(tp.shape[:-2])
+    B = int(torch.Size(lead).numel())
+    new = lambda like, *tail: torch.empty(lead + tail, device=like.device, dtype=torch.float32)
+    out, rr_out, rt_out = (torch.empty_like(d), torch.empty_like(rr), torch.empty_like(rt)) if want_iterate else (None,) * 3
+    loss = new(d) if want_loss else None
+    grad, grad_root = (torch.empty_like(d), new(d, 7)) if want_grad else (None, None)
+    check(lib().rtg_dof_fit_root_f32(model.handle, ptr(tp), ptr(w), ptr(rr), ptr(rt), ptr(d), B, int(bool(clip)),
+                                     int(fit_root), int(iters), float(lr), float(lr_root_t), float(lr_root_rot),
+                                     float(betas[0]), float(betas[1]), float(eps), int(step0), ptr(m), ptr(v),
+                                     ptr(root_state), ptr(out), ptr(rr_out), ptr(rt_out), ptr(loss), ptr(grad),
+                                     ptr(grad_root), stream_handle()))
+    return out, rr_out, rt_out, loss, grad, grad_root
+
+
+def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iters: int = 32, lr: float = 0.02,
+             lr_root_t=None, lr_root_rot=None, fit_root_t: bool = True, fit_root_rot: bool = True, betas=(0.9, 0.999),
+             eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False):
+    """dof_fit with the floating base among the parameters: the joint angles and -- where ``fit_root_t`` /
+    ``fit_root_rot`` -- the root translation and rotation of every frame, fitted to target keypoints by ``iters`` steps
+    of torch.optim.Adam with three parameter groups (``lr`` for the angles, ``lr_root_t``, ``lr_root_rot``; None: ``lr``)
+    in ONE launch (rtg_dof_fit_root_f32).  A fitted rotation enters the forward model as q / |q| (no sign flip), its
+    gradient goes through that normalisation and the iterate is renormalised after each step; a block that is not
+    fitted is given, as in dof_fit (a given rotation is used unnormalised).
+
+    target_pos (..., J, 3); root_rot0 (..., 4) [or (..., 1, 4)] / root_t0 (..., 3): the start; dof0 (..., J-1) [or
+    (..., J-1, 1)], default zeros; weight (J,) or None.  ``state`` is ``(m, v, root_state, step)`` from an earlier call
+    (None: a fresh optimiser), root_state (..., 14) = {m_t, m_q, v_t, v_q}; it is returned updated, and calls chain:
+    two calls of n steps give the bits of one call of 2n.
+
+    Returns the named tuple ``(dof, root_rot, root_t, loss, state)`` -- the iterate after the last step (root_rot
+    (..., 4), unit where fitted), the per-frame loss there -- plus ``grad`` (dof's shape) and ``grad_root`` (..., 7) =
+    {dL/dt, dL/dq} there when ``return_grad``.  ``iters=0`` only evaluates.  Raises RtgError without a GPU: there is
+    no CPU fallback."""
+    tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot0, root_t0, dof0, weight)
+    iters = int(iters)
+    if not 0 <= iters <= DOF_FIT_MAX_ITERS:
+        raise ValueError(f"iters must be in 0..{DOF_FIT_MAX_ITERS}, got {iters}")
+    lead = tuple(tp.shape[:-2])
+    if state is None:
+        m, v, step = torch.zeros_like(d), torch.zeros_like(d), 0
+        rs = torch.zeros(lead + (14,), device=d.device, dtype=torch.float32)
+    else:
+        m, v, rs, step = state
+        m, v = (dev_f32(x, (model.num_dofs,), "state").reshape(d.shape).clone() for x in (m, v))
+        rs = dev_f32(rs, (14,), "root_state").reshape(lead + (14,)).clone()
+        step = int(step)
+    fit_root = (FIT_ROOT_T if fit_root_t else 0) | (FIT_ROOT_ROT if fit_root_rot else 0)
+    # (a one-joint model has no angle moments: their arguments only say that a state is given)
+    out, rr_out, rt_out, loss, grad, grad_root = _pose_launch(
+        model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach(), iters, lr,
+        lr if lr_root_t is None else lr_root_t, lr if lr_root_rot is None else lr_root_rot, betas, eps, step,
+        m if m.numel() else rs, v if v.numel() else rs, rs, want_iterate=True, want_grad=bool(return_grad))
+    if dof0 is not None and tuple(_as_tensor(dof0).shape) == tuple(d.shape) + (1,):
+        out = out.unsqueeze(-1)
+        grad = None if grad is None else grad.unsqueeze(-1)
+    new_state = (m, v, rs, step + iters)
+    if return_grad:
+        return PoseFitGrad(out, rr_out, rt_out, loss, new_state, grad, grad_root)
+    return PoseFit(out, rr_out, rt_out, loss, new_state)
+
+
+def pose_loss(model, dof, root_rot, root_t, target_pos, weight=None, clip: bool = False, normalize_root: bool = True):
+    """The per-frame keypoint loss of pose_fit, (...), as the evaluate-only launch of rtg_dof_fit_root_f32,
+    differentiable in ``dof``, ``root_rot`` and ``root_t``: the launch computes the three gradients along with the
+    loss and backward scales their rows by the upstream cotangent -- for callers who keep their own optimiser.
+    ``normalize_root``: the root rotation enters as q / |q| and its gradient is tangent (pose_fit's model of a fitted
+    rotation); False: as given, like keypoint_loss.  Under no_grad, or when no input requires grad, it is the plain
+    launch without the gradients."""
+    tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof, weight)
+    fit_root = FIT_ROOT_ROT if normalize_root else 0   # no step is taken: the mask only selects the model
+    if torch.is_grad_enabled() and (d.requires_grad or rr.requires_grad or rt.requires_grad):
+        return _PoseLoss.apply(model, bool(clip), fit_root, d, rr, rt, tp, w)
+    return _pose_launch(model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach())[3]
+
+
+class _PoseLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, clip, fit_root, d, rr, rt, tp, w):
+        _, _, _, loss, grad, grad_root = _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, want_grad=True)
+        ctx.save_for_backward(grad, grad_root)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        grad, grad_root = ctx.saved_tensors
+        c = grad_loss.unsqueeze(-1)
+        return None, None, None, grad * c, grad_root[..., 3:] * c, grad_root[..., :3] * c, None, None
 
 
 def rescale_motion(topo: Topology, motion, dir=None):

@@ -28,8 +28,8 @@
 extern "C" {
 #endif
 
-#define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*); rtg_dof_fit_f32 came
-                                  later as a new symbol only -- nothing that existed changed, so the version stays 7;
+#define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*); rtg_dof_fit_f32 and
+                                  rtg_dof_fit_root_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
                                6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
                                5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
                                4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
@@ -191,6 +191,40 @@ int rtg_dof_fit_f32(rtg_dof_model_t model, const float *target_pos, const float 
                     const float *root_t, const float *dof_in, int64_t B, int clip, int32_t iters, float lr, float beta1,
                     float beta2, float eps, int32_t step0, float *m, float *v, float *dof_out, float *loss, float *grad,
                     rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * rtg_dof_fit_f32 with the floating base among the parameters (a new symbol under ABI 7): per frame the angles a, and
+ * -- selected by the fit_root bit mask -- the root translation t (3) and the root rotation q (4, [x, y, z, w]).  Mocap
+ * keypoints come from a body of other proportions; with the root pinned the legs cannot reach them.
+ *   A block whose bit is clear is given, exactly as in rtg_dof_fit_f32 (a given rotation is used unnormalised).
+ *   RTG_FIT_ROOT_ROT: the forward model uses G_0 = q / max(|q|, 1e-9) -- no sign flip, q and -q are one rotation and
+ *   the iterate stays continuous; the gradient goes through that normalisation (it is tangent: (g - (g.G_0) G_0) / |q|)
+ *   and after each Adam step q is renormalised the same way: root_rot_out is unit, and feeding it back continues the
+ *   run.  RTG_FIT_ROOT_T: dL/dt = sum_j 2 weight[j] (P_j - target_pos[f,j]), the root's own residual included.
+ * Loss, Adam formulas, bias corrections, step0, the iters cap and the clip are rtg_dof_fit_f32's; the three blocks
+ * have their own step sizes lr (angles), lr_root_t, lr_root_rot and share betas and eps: torch.optim.Adam with three
+ * parameter groups.
+ *   root_rot (B,4), root_t (B,3): the start, or the given values; root_state (B,14): the root's moments {m_t(3),
+ *   m_q(4), v_t(3), v_q(4)}, read and written in place -- NULL exactly when m and v are NULL (start at 0, not written);
+ *   with fit_root == 0 it is neither read nor written;
+ *   -> dof_out, loss, grad as in rtg_dof_fit_f32; root_rot_out (B,4), root_t_out (B,3) (they may alias the inputs;
+ *   with iters == 0, or for a given block, they carry the input's bits); grad_root (B,7) = {dL/dt, dL/dq} at the
+ *   outputs -- for a given rotation dL/dq is that of the unnormalised model, as rtg_dof_fk_backward_f32 reports it.
+ *   Each output may be NULL, not all six.  root_rot and root_rot_out are 16-byte aligned rows.  A one-joint model
+ *   has no angles: dof_in, dof_out, grad, m and v are not dereferenced (m, v still say whether a state is given).
+ * rtg_dof_fit_f32's guarantees hold: a frame depends on its own rows alone, runs are bit-identical, n launches of one
+ * step that carry (m, v, root_state, step0) equal one launch of n steps, DOFs over zero-weight subtrees keep their
+ * bits; with every weight zero a fitted t keeps its bits; and fit_root == 0 gives rtg_dof_fit_f32's outputs bit for bit.
+ * Errors: rtg_dof_fit_f32's, and unknown fit_root bits, lr_root_* not finite or negative, root_state given without
+ * m, v or the reverse -> RTG_ERR_INVALID_ARGUMENT; more than 64 joints -> RTG_ERR_UNSUPPORTED.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------- */
+#define RTG_FIT_ROOT_T 1     /* fit the root translation */
+#define RTG_FIT_ROOT_ROT 2   /* fit the root rotation */
+int rtg_dof_fit_root_f32(rtg_dof_model_t model, const float *target_pos, const float *weight, const float *root_rot,
+                         const float *root_t, const float *dof_in, int64_t B, int clip, int32_t fit_root, int32_t iters,
+                         float lr, float lr_root_t, float lr_root_rot, float beta1, float beta2, float eps,
+                         int32_t step0, float *m, float *v, float *root_state, float *dof_out, float *root_rot_out,
+                         float *root_t_out, float *loss, float *grad, float *grad_root, rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * SkeletonState.retarget_to (poselib skeleton3d.py:742-889): the generic skeleton-to-skeleton retarget, rotations

@@ -4,7 +4,8 @@ builds, interleaved like tools/ab_small.py: each build runs in its own process (
 Bits: every output of the lane-group entry points on fixed seeded inputs at small ragged shapes (B = F + 1 for both
 tile shapes, F = 16 and 8) is hashed per case, and every hash must equal the first build's -- also where no oracle pins
 the bits (the gradient and fit kernels are built with -ffp-contract=fast and their tests only bound the error).
-Time: device events at B = 262144 on the shapes of tools/extra_bench.py's modes fk, retarget_to and fit.  A build passes
+Time: device events at B = 262144 on the shapes of tools/extra_bench.py's modes fk, retarget_to, fit and pose_fit.  A
+base build from before an entry point existed is served: the cases and times it cannot give are left out.  A build passes
 when each of its medians is at most the first build's median plus the first build's own max - min over its rounds.
 
   python tools/ab_groups.py base=.../variants/parent.so new=humanoid-real-time-retarget_amd/librtg_hip.so [--rounds 4]
@@ -48,8 +49,12 @@ def child():
     import torch
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import extra_bench as xb
+    import ctypes
     from rtg import _lib, ops
     from rtg.runtime import DofModel, Topology, ptr, stream_handle
+    older = ctypes.CDLL(_lib.LIB_PATH)   # a base build from before a symbol existed: its cases are left out
+    for name in [n for n in _lib.SIGNATURES if not hasattr(older, n)]:
+        del _lib.SIGNATURES[name]
     lib, check, sh = _lib.lib(), _lib.check, stream_handle()
     gen = torch.Generator(device="cuda").manual_seed(14)
     rnd = lambda *s: torch.randn(s, device="cuda", generator=gen)
@@ -110,6 +115,15 @@ def child():
                 check(lib.rtg_dof_fit_f32(M.handle, ptr(tgt), ptr(w), ptr(rr), ptr(rt), ptr(dof), B, 1, iters, 0.02,
                                           0.9, 0.999, 1e-8, 0, ptr(m), ptr(v), ptr(out), ptr(loss), ptr(grad), sh))
                 put(f"dof_fit_F{F}_iters{iters}_state{int(state)}", out, loss, grad, *([m, v] if state else []))
+                if "rtg_dof_fit_root_f32" not in _lib.SIGNATURES:
+                    continue
+                for mask in (0, 3):
+                    m, v, rs = (torch.zeros(B, n, device="cuda") for n in (J - 1, J - 1, 14)) if state else (None,) * 3
+                    outs = [empty(B, J - 1), empty(B, 4), empty(B, 3), empty(B), empty(B, J - 1), empty(B, 7)]
+                    check(lib.rtg_dof_fit_root_f32(M.handle, ptr(tgt), ptr(w), ptr(rr), ptr(rt), ptr(dof), B, 1, mask,
+                                                   iters, 0.02, 0.01, 0.03, 0.9, 0.999, 1e-8, 0, ptr(m), ptr(v), ptr(rs),
+                                                   *(ptr(o) for o in outs), sh))
+                    put(f"pose_fit_F{F}_mask{mask}_iters{iters}_state{int(state)}", *outs, *([m, v, rs] if state else []))
     fk_out, inv_out = ops.kinematics_multi(segs, [(T, ops.forward_kinematics(T, lr, rt)[0]) for T, lr, rt in segs])
     put("kinematics_multi", *[x for pair in fk_out for x in pair], *inv_out)
     for tag in ("vtrdyn_hu_v5_local", "vtrdyn_full_hu"):
@@ -131,6 +145,10 @@ def child():
     M, tgt, rr, rt, start = xb._fit_setup(B)
     out, loss = torch.empty((B, 32), device="cuda"), torch.empty((B,), device="cuda")
     t["fit_32_iters_262144"] = xb.time_events(xb._fit_call(M, tgt, rr, rt, start, B, 32, out, loss, None), reps=10, warm=2) * 1e3
+    if "rtg_dof_fit_root_f32" in _lib.SIGNATURES:
+        outs = (out, torch.empty((B, 4), device="cuda"), torch.empty((B, 3), device="cuda"), loss, None, None)
+        t["pose_fit_32_iters_262144"] = xb.time_events(xb._pose_fit_call(M, tgt, rr, rt, start, B, 32, 3, outs), reps=10,
+                                                       warm=2) * 1e3
     print(json.dumps({"kernel_us": t, "hashes": hashes}))
 
 
@@ -160,6 +178,8 @@ def main():
         us = {k: sorted(round(r["kernel_us"][k], 2) for r in runs) for k in runs[0]["kernel_us"]}
         slow = {}
         for k, v in us.items():
+            if k not in base[0]["kernel_us"]:   # the base build has no such kernel
+                continue
             b = sorted(r["kernel_us"][k] for r in base)
             bound = statistics.median(b) + (b[-1] - b[0])
             if statistics.median(v) > bound:

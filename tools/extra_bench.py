@@ -18,6 +18,11 @@
               interleaved rounds
   fit_traffic -- a few launches of each fused form and nothing else, for a counter run of its own (FETCH_SIZE or
               WRITE_SIZE, one per run) against the algorithmic bytes that `fit` prints
+  pose_fit -- the keypoint fit with the floating base (rtg_dof_fit_root_f32, fit_root = 3; same shapes as `fit`, the
+              start's root 0.2 m and 0.3 rad off) per iteration, against rtg_dof_fit_f32 from the same start -- this
+              build's, and that of another build named by RTG_PARENT_LIB -- and the composed iteration with the root
+              among torch's parameters, interleaved rounds
+  pose_fit_traffic -- a few launches of rtg_dof_fit_root_f32 and nothing else, for a counter run of its own
   motion_sample -- the fused motion sampler (rtg_motion_sample_f32, C ABI, preallocated outputs; Hu v5, 64 clips x 4096
               frames, N=262144 queries; uniform / random / frame-instant queries, with global outputs + velocities
               and local only) against the composed chain (index rule in torch, index_select, quat_slerp,
@@ -525,6 +530,120 @@ def fit_traffic(B=262144, iters=32):
             call()
     torch.cuda.synchronize()
     return {"B": B, "launches": "4 x iters=0 (loss, grad out), then 4 x iters=%d (dof, loss out); grids equal" % iters}
+
+
+def _other_build_fit(path, tgt, rr, rt, start, B, iters, out, loss):
+    """rtg_dof_fit_f32 of another build of the library (its own handles), for a same-session comparison."""
+    import ctypes
+    import importlib
+    from rtg.runtime import ptr, stream_handle
+    hu = importlib.import_module("retarget.robot_config.Hu")
+    other = ctypes.CDLL(os.path.abspath(path))
+    for name in ("rtg_topology_create", "rtg_dof_model_create", "rtg_dof_fit_f32"):
+        getattr(other, name).restype, getattr(other, name).argtypes = _lib.SIGNATURES[name]
+    i32, f32 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+    host = lambda a, dt: np.ascontiguousarray(np.asarray(a), dt)
+    par, lt, tq = host(assets.parents("hu"), np.int32), host(assets.local_translation("hu"), np.float32), \
+        host(assets.tree_quat("hu"), np.float32)
+    ax, lo, hi = host(hu.Hu_DOF_AXIS, np.int32), host(hu.Hu_DOF_LOWER.numpy(), np.float32), \
+        host(hu.Hu_DOF_UPPER.numpy(), np.float32)
+    th, mh = ctypes.c_void_p(), ctypes.c_void_p()
+    assert other.rtg_topology_create(par.ctypes.data_as(i32), lt.ctypes.data_as(f32), tq.ctypes.data_as(f32), len(par),
+                                     ctypes.byref(th)) == 0
+    assert other.rtg_dof_model_create(th, ax.ctypes.data_as(i32), lo.ctypes.data_as(f32), hi.ctypes.data_as(f32),
+                                      ctypes.byref(mh)) == 0
+    args = (mh, ptr(tgt), None, ptr(rr), ptr(rt), ptr(start), B, 1, iters, 0.02, 0.9, 0.999, 1e-8, 0, None, None,
+            ptr(out), ptr(loss), None, stream_handle())
+    assert other.rtg_dof_fit_f32(*args) == 0
+    return lambda: other.rtg_dof_fit_f32(*args)
+
+
+def _pose_fit_setup(B):
+    """_fit_setup's reachable targets; the start has the root 0.2 m and 0.3 rad off."""
+    M, tgt, rr, rt, start = _fit_setup(B)
+    gen = torch.Generator(device="cuda").manual_seed(18)
+    unit = lambda n: torch.nn.functional.normalize(torch.randn((B, n), device="cuda", generator=gen), dim=-1)
+    off = torch.cat([unit(3) * float(np.sin(0.15)), torch.full((B, 1), float(np.cos(0.15)), device="cuda")], dim=-1)
+    x1, y1, z1, w1 = rr.unbind(-1)
+    x2, y2, z2, w2 = off.unbind(-1)
+    rr0 = torch.stack([w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2, w1 * y2 + y1 * w2 + z1 * x2 - x1 * z2,
+                       w1 * z2 + z1 * w2 + x1 * y2 - y1 * x2, w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2], dim=-1).contiguous()
+    rt0 = (rt + 0.2 * unit(3)).contiguous()
+    return M, tgt, rr0, rt0, start
+
+
+def _pose_fit_call(M, tgt, rr0, rt0, start, B, iters, mask, outs, state=(None, None, None)):
+    from rtg.runtime import ptr, stream_handle
+    f = _lib.lib().rtg_dof_fit_root_f32
+    args = (M.handle, ptr(tgt), None, ptr(rr0), ptr(rt0), ptr(start), B, 1, mask, iters, 0.02, 0.02, 0.02, 0.9, 0.999,
+            1e-8, 0, *(ptr(s) for s in state), *(ptr(o) for o in outs), stream_handle())
+    _lib.check(f(*args))
+    return lambda: f(*args)
+
+
+def pose_fit(B=262144, rounds=4, iters=32):
+    """The keypoint fit with the floating base (rtg_dof_fit_root_f32, fit_root = 3, C ABI, preallocated outputs, 33-link
+    Hu, clip on) per iteration, against rtg_dof_fit_f32 of this build, of the build RTG_PARENT_LIB names (when set),
+    and the composed iteration with the root among torch's parameters (ops.dof_forward_kinematics on the normalised
+    root, the torch loss, backward(), torch.optim.Adam(fused=True) with three groups, the renormalisation);
+    interleaved rounds."""
+    M, tgt, rr0, rt0, start = _pose_fit_setup(B)
+    J = 33
+    new = lambda *s: torch.empty(s, device="cuda")
+    out, rr_out, rt_out, loss = new(B, 32), new(B, 4), new(B, 3), new(B)
+    m, v, rs = (torch.zeros(s, device="cuda") for s in ((B, 32), (B, 32), (B, 14)))
+    outs = (out, rr_out, rt_out, loss, None, None)
+    root = _pose_fit_call(M, tgt, rr0, rt0, start, B, iters, 3, outs)
+    root_state = _pose_fit_call(M, tgt, rr0, rt0, start, B, iters, 3, outs, (m, v, rs))
+    mask0 = _pose_fit_call(M, tgt, rr0, rt0, start, B, iters, 0, outs)
+    angles = _fit_call(M, tgt, rr0, rt0, start, B, iters, out, loss, None)
+    parent = os.environ.get("RTG_PARENT_LIB")
+    angles_parent = _other_build_fit(parent, tgt, rr0, rt0, start, B, iters, out, loss) if parent else None
+    a, q, t = (x.clone().requires_grad_(True) for x in (start, rr0, rt0))
+    opt = torch.optim.Adam([dict(params=[a]), dict(params=[t]), dict(params=[q])], lr=0.02, fused=True)
+
+    def composed():
+        opt.zero_grad(set_to_none=True)
+        gp = ops.dof_forward_kinematics(M, a, torch.nn.functional.normalize(q, dim=-1, eps=1e-9), t, clip=True)[1]
+        (gp - tgt).square().sum().backward()
+        opt.step()
+        with torch.no_grad():
+            q.copy_(torch.nn.functional.normalize(q, dim=-1, eps=1e-9))
+
+    res = {k: [] for k in ("root_us_per_iteration", "root_with_state_us_per_iteration", "fit_root_0_us_per_iteration",
+                           "dof_fit_us_per_iteration", "parent_dof_fit_us_per_iteration", "composed_us_per_iteration")}
+    for _ in range(rounds):   # interleaved: all see the same box state
+        res["root_us_per_iteration"].append(time_events(root, reps=5, warm=1) * 1e3 / iters)
+        res["root_with_state_us_per_iteration"].append(time_events(root_state, reps=5, warm=1) * 1e3 / iters)
+        res["fit_root_0_us_per_iteration"].append(time_events(mask0, reps=5, warm=1) * 1e3 / iters)
+        res["dof_fit_us_per_iteration"].append(time_events(angles, reps=5, warm=1) * 1e3 / iters)
+        if angles_parent:
+            res["parent_dof_fit_us_per_iteration"].append(time_events(angles_parent, reps=5, warm=1) * 1e3 / iters)
+        res["composed_us_per_iteration"].append(time_events(composed, reps=10, warm=2) * 1e3)
+    rd, wr = J * 12 + (J - 1) * 4 + 28, (J - 1) * 4 + 4 + 28
+    return {"B": B, "J": J, "iters": iters, **res, "parent_lib": parent,
+            "algorithmic_bytes_per_frame": {"read": rd, "written": wr, "state_rows_each_way": 2 * (J - 1) * 4 + 56}}
+
+
+def pose_fit_traffic(B=262144, iters=32):
+    """A few launches of rtg_dof_fit_root_f32 (fit_root = 3: without a state, then with one) and nothing else, for a
+    counter run of its own (FETCH_SIZE or WRITE_SIZE, one per run) against the algorithmic bytes `pose_fit` prints."""
+    M, tgt, rr0, rt0, start = _pose_fit_setup(B)
+    new = lambda *s: torch.empty(s, device="cuda")
+    outs = (new(B, 32), new(B, 4), new(B, 3), new(B), None, None)
+    m, v, rs = (torch.zeros(s, device="cuda") for s in ((B, 32), (B, 32), (B, 14)))
+    src, dst = torch.randn(1 << 26, device="cuda"), torch.empty(1 << 26, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(3):   # known bytes: the counters' unit
+        dst.copy_(src)
+    for call in (_pose_fit_call(M, tgt, rr0, rt0, start, B, iters, 3, outs),
+                 _pose_fit_call(M, tgt, rr0, rt0, start, B, iters, 3, outs, (m, v, rs))):
+        for _ in range(3):
+            call()
+    torch.cuda.synchronize()
+    return {"B": B, "copy_bytes_each_way": 4 << 26,
+            "launches": "3 x 256 MiB copy, 4 x iters=%d without a state (dof, root, loss out), then 4 x with (m, v, "
+                        "root_state); grids equal" % iters}
 
 
 def motion_sample(N=262144, rounds=4, clips=64, frames=4096):
