@@ -3,6 +3,11 @@
 // Host-side only: argument validation (mirroring the reference's assertions),
 // handle lifetime, and stream-ordered launches.  Launch entry points never
 // allocate, copy or synchronise, so callers may capture them into hipGraphs.
+//
+// Device resources live in the owner types below (DevBuf, PinnedWord, Event): a handle struct holds owners, so a
+// constructor that fails part-way just returns and `delete handle` is the whole destructor.  Argument checks whose
+// text agrees up to the function's name are written once (check_tree, check_layout, check_overlap, parse_seq, ...).
+// Every message here is pinned by tests/api_message_cases.py: a new entry point adds its cases there.
 #include <immintrin.h>
 #include <hip/hip_runtime.h>
 
@@ -11,7 +16,9 @@
 #include <cstdio>
 #include <cstring>
 #include <ctime>
+#include <memory>
 #include <new>
+#include <type_traits>
 #include <vector>
 #include <string>
 #include <utility>
@@ -19,57 +26,6 @@
 #include "rtg_kernels.cuh"
 
 using namespace rtg;
-
-struct rtg_topology_s {
-    int32_t J = 0;
-    int32_t *d_parents = nullptr;
-    V *d_local_t = nullptr;
-    Q *d_tree_quat = nullptr;
-    GEnt *d_gsched = nullptr;   // lane-group FK schedule (J <= kGroupMaxJ), see fk_group_schedule
-    int32_t gF = 0, gsteps = 0;
-    std::vector<int32_t> h_parents;   // host copies, for the plans built over this tree (rtg_retarget_plan_create)
-    std::vector<Q> h_tree_quat;
-    TopoView view() const
-    {
-        return TopoView{d_parents, d_local_t, d_tree_quat, J, d_gsched, gF, gsteps};
-    }
-};
-
-// HuForwardModel: the topology is borrowed (it must outlive the model); axis / limits are owned.
-struct rtg_dof_model_s {
-    rtg_topology_t topo = nullptr;
-    int32_t *d_axis = nullptr;
-    float *d_lower = nullptr;
-    float *d_upper = nullptr;
-    bool has_limits = false;
-};
-
-// SkeletonState.retarget_to: the view (layout, R, scale, roots) and the device blob it points into.
-struct rtg_retarget_plan_s {
-    RetargetView view{};
-    float *d_blob = nullptr;
-};
-
-// The zero-pose transform of mocap rotations: the view and the device blob it points into.
-struct rtg_rot_ingest_s {
-    RotIngestView view{};
-    float *d_blob = nullptr;
-};
-
-// A motion library's clip table on the device; F_total bounds the caller's arrays (the overlap checks).
-struct rtg_motion_lib_s {
-    MotionClip *d_clips = nullptr;
-    int32_t C = 0;
-    int64_t F_total = 0;
-};
-
-struct rtg_solver_s {
-    int kind = 0;
-    int precise = 0;
-    SolverConsts consts{};
-    uint32_t *d_ang_tab = nullptr;   // exp-map angle table (consts.ang_tab), device of creation
-    uint32_t *h_err = nullptr;       // the device error word (consts.err is its device alias), pinned host memory
-};
 
 namespace {
 
@@ -94,14 +50,166 @@ int hip_check(hipError_t e, const char *what)
                 hipGetErrorString(e));
 }
 
-#define RTG_TRY(expr, what)                          \
+// a HIP call, or anything else that returns an rtg_status: leave with it unless it is RTG_OK
+#define RTG_TRY(expr, what) RTG_CHECK(hip_check((expr), (what)))
+#define RTG_CHECK(expr)                              \
     do {                                             \
-        int rc_ = hip_check((expr), (what));         \
+        int rc_ = (expr);                            \
         if (rc_ != RTG_OK) return rc_;               \
     } while (0)
 
+// ---------------------------------------------------------------- owners
+// What a handle (or a constructor that may still fail) holds of the device: released with its owner, move-only.
+struct DevFree { void operator()(void *p) const { (void)hipFree(p); } };
+struct PinnedFree { void operator()(void *p) const { (void)hipHostFree(p); } };
+struct EventFree { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+
+// Device memory (hipMalloc) of n elements of T.
+template <class T>
+struct DevBuf {
+    std::unique_ptr<T, DevFree> p;
+    T *get() const { return p.get(); }
+    int alloc(size_t n, const char *what)
+    {
+        T *raw = nullptr;
+        RTG_TRY(hipMalloc(&raw, sizeof(T) * n), what);
+        p.reset(raw);
+        return RTG_OK;
+    }
+    int upload(const T *src, size_t n, const char *what = "hipMemcpy")
+    {
+        return hip_check(hipMemcpy(p.get(), src, sizeof(T) * n, hipMemcpyHostToDevice), what);
+    }
+    int alloc_upload(const T *src, size_t n, const char *what)
+    {
+        RTG_CHECK(alloc(n, what));
+        return upload(src, n);
+    }
+};
+
+// One zeroed word of host-mapped pinned memory (a solver's device error word).
+struct PinnedWord {
+    std::unique_ptr<uint32_t, PinnedFree> p;
+    uint32_t *get() const { return p.get(); }
+    int alloc(const char *what)
+    {
+        void *raw = nullptr;
+        RTG_TRY(hipHostMalloc(&raw, sizeof(uint32_t), hipHostMallocMapped), what);
+        p.reset(static_cast<uint32_t *>(raw));
+        *p = 0;
+        return RTG_OK;
+    }
+};
+
+struct Event {
+    std::unique_ptr<std::remove_pointer<hipEvent_t>::type, EventFree> e;
+    hipEvent_t get() const { return e.get(); }
+    int create()
+    {
+        hipEvent_t raw = nullptr;
+        RTG_TRY(hipEventCreate(&raw), "hipEventCreate");
+        e.reset(raw);
+        return RTG_OK;
+    }
+};
+
+}  // namespace
+
+struct rtg_topology_s {
+    int32_t J = 0;
+    DevBuf<int32_t> parents;
+    DevBuf<V> local_t;
+    DevBuf<Q> tree_quat;
+    DevBuf<GEnt> gsched;   // lane-group FK schedule (J <= kGroupMaxJ), see fk_group_schedule
+    int32_t gF = 0, gsteps = 0;
+    std::vector<int32_t> h_parents;   // host copies, for the plans built over this tree (rtg_retarget_plan_create)
+    std::vector<Q> h_tree_quat;
+    TopoView view() const
+    {
+        return TopoView{parents.get(), local_t.get(), tree_quat.get(), J, gsched.get(), gF, gsteps};
+    }
+};
+
+// HuForwardModel: the topology is borrowed (it must outlive the model); axis / limits are owned.
+struct rtg_dof_model_s {
+    rtg_topology_t topo = nullptr;
+    DevBuf<int32_t> axis;
+    DevBuf<float> lower, upper;
+    bool has_limits = false;
+    DofView view() const { return DofView{axis.get(), lower.get(), upper.get()}; }
+};
+
+// SkeletonState.retarget_to: the view (layout, R, scale, roots) and the device blob it points into.
+struct rtg_retarget_plan_s {
+    RetargetView view{};
+    DevBuf<float> blob;
+};
+
+// The zero-pose transform of mocap rotations: the view and the device blob it points into.
+struct rtg_rot_ingest_s {
+    RotIngestView view{};
+    DevBuf<float> blob;
+};
+
+// A motion library's clip table on the device; F_total bounds the caller's arrays (the overlap checks).
+struct rtg_motion_lib_s {
+    DevBuf<MotionClip> clips;
+    int32_t C = 0;
+    int64_t F_total = 0;
+};
+
+struct rtg_solver_s {
+    int kind = 0;
+    int precise = 0;
+    SolverConsts consts{};
+    DevBuf<uint32_t> ang_tab;   // exp-map angle table (consts.ang_tab), device of creation
+    PinnedWord err;             // the device error word (consts.err is its device alias)
+};
+
+namespace {
+
 inline hipStream_t as_stream(rtg_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 inline V v3(const float *p, int j) { return V{p[3 * j], p[3 * j + 1], p[3 * j + 2]}; }
+
+// ---------------------------------------------------------------- shared checks (the text agrees up to fn)
+// parent-indexed tree in topological order (skeleton3d.py:87-88 asserts equal lengths; the FK loop kinematics.py:27
+// requires parents before children)
+int check_tree(const char *fn, const int32_t *parents, int J)
+{
+    if (J >= 1 && parents[0] != -1) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: joint 0 must be the root", fn);
+    for (int j = 1; j < J; ++j)
+        if (parents[j] < 0 || parents[j] >= j)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: parents[%d]=%d is not < %d", fn, j, parents[j], j);
+    return RTG_OK;
+}
+
+int check_layout(const char *fn, int layout)
+{
+    if (layout != RTG_LAYOUT_AOS && layout != RTG_LAYOUT_SOA)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: bad layout %d", fn, layout);
+    return RTG_OK;
+}
+
+// No span of a[] may share a byte with a span of b[] or with a later span of a[]; NULL spans are skipped.
+struct Span {
+    const void *p;
+    uint64_t bytes;
+    const char *name;
+};
+int check_overlap(const char *fn, const Span *a, size_t na, const Span *b, size_t nb)
+{
+    auto hit = [](const Span &x, const Span &y) {
+        const uintptr_t px = reinterpret_cast<uintptr_t>(x.p), py = reinterpret_cast<uintptr_t>(y.p);
+        return x.p && y.p && px < py + y.bytes && py < px + x.bytes;
+    };
+    for (size_t i = 0; i < na; ++i) {
+        for (size_t k = 0; k < nb; ++k)
+            if (hit(a[i], b[k])) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: %s and %s overlap", fn, a[i].name, b[k].name);
+        for (size_t k = i + 1; k < na; ++k)
+            if (hit(a[i], a[k])) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: %s and %s overlap", fn, a[i].name, a[k].name);
+    }
+    return RTG_OK;
+}
 
 int axis_of(char c, int *ax, int *lower)
 {
@@ -114,6 +222,146 @@ int axis_of(char c, int *ax, int *lower)
     case 'Z': *ax = 2; *lower = 0; return 1;
     default: return 0;
     }
+}
+
+// scipy's Euler sequence: 3 chars of xyz (extrinsic) or XYZ (intrinsic), consecutive axes different
+int parse_seq(const char *fn, const char *seq, int ax[3], int *extrinsic)
+{
+    if (!seq || std::strlen(seq) != 3) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: seq must have 3 axes", fn);
+    int lower[3];
+    for (int i = 0; i < 3; ++i)
+        if (!axis_of(seq[i], &ax[i], &lower[i])) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: bad axis '%c'", fn, seq[i]);
+    if (lower[0] != lower[1] || lower[1] != lower[2])
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: mixed intrinsic/extrinsic seq '%s'", fn, seq);
+    if (ax[0] == ax[1] || ax[1] == ax[2])
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: consecutive axes must differ ('%s')", fn, seq);
+    *extrinsic = lower[0];
+    return RTG_OK;
+}
+
+int check_fk(rtg_topology_t t, const void *a, const void *b, const void *c, const void *d, int64_t B, const char *fn)
+{
+    if (!t) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL topology", fn);
+    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: negative batch %lld", fn, (long long)B);
+    if (B > 0 && (!a || !b || !c || !d)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    return RTG_OK;
+}
+
+int run_fk(const char *fn, bool state, rtg_topology_t t, const float *local_rot, const float *root_t, int64_t B,
+           float *g_rot, float *g_pos, rtg_stream_t stream)
+{
+    int rc = check_fk(t, local_rot, root_t, g_rot, g_pos, B, fn);
+    if (rc != RTG_OK || B == 0) return rc;
+    RTG_TRY(launch_fk(t->view(), state, local_rot, root_t, B, g_rot, g_pos, as_stream(stream)),
+            state ? "k_fk<state>" : "k_fk");
+    return RTG_OK;
+}
+
+int run_local_rotation(const char *fn, bool state, rtg_topology_t t, const float *g_rot, int64_t B, float *local_rot,
+                       rtg_stream_t stream)
+{
+    int rc = check_fk(t, g_rot, local_rot, g_rot, local_rot, B, fn);
+    if (rc != RTG_OK || B == 0) return rc;
+    RTG_TRY(launch_local_rotation(t->view(), state, g_rot, B, local_rot, as_stream(stream)),
+            state ? "k_local_rotation<state>" : "k_local_rotation");
+    return RTG_OK;
+}
+
+// the FK segments of a mixed launch, checked, into dst[0..n)
+int fill_fk_segments(const char *fn, const rtg_fk_segment *segs, int n, FkSeg *dst)
+{
+    for (int i = 0; i < n; ++i) {
+        const rtg_fk_segment &s = segs[i];
+        RTG_CHECK(check_fk(s.topo, s.local_rot, s.root_t, s.g_rot, s.g_pos, s.B, fn));
+        dst[i] = FkSeg{s.topo->view(), s.local_rot, s.root_t, s.g_rot, s.g_pos, s.B, 0};
+    }
+    return RTG_OK;
+}
+
+// the argument checks both backward entry points share (everything that needs no handle first)
+int check_fk_backward(const char *fn, int64_t B, const void *grad_g_rot, const void *grad_g_pos, bool any_out)
+{
+    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)B);
+    if (B == 0) return RTG_OK;   // empty buffers have no address to give
+    if (!grad_g_rot && !grad_g_pos)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: both upstream gradients are NULL", fn);
+    if (!any_out) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: every output is NULL", fn);
+    return RTG_OK;
+}
+
+// rtg_dof_fit_f32 (R == nullptr) and rtg_dof_fit_root_f32 (R: the root block): one checked path, two kernels
+int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const DofFitRootArgs *R, rtg_stream_t stream)
+{
+    // everything that needs no handle first
+    if (A.B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)A.B);
+    if (R && (R->fit_root & ~(RTG_FIT_ROOT_T | RTG_FIT_ROOT_ROT)))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: fit_root=%d has unknown bits", fn, R->fit_root);
+    if (A.iters < 0 || A.iters > RTG_DOF_FIT_MAX_ITERS)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: iters=%d is outside 0..%d", fn, A.iters, RTG_DOF_FIT_MAX_ITERS);
+    if (A.step0 < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: step0=%d < 0", fn, A.step0);
+    if (!std::isfinite(A.lr) || !std::isfinite(A.eps))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: lr=%g, eps=%g must be finite", fn, (double)A.lr, (double)A.eps);
+    if (R && (!std::isfinite(R->lr_t) || !std::isfinite(R->lr_rot) || R->lr_t < 0.0f || R->lr_rot < 0.0f))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: lr_root_t=%g, lr_root_rot=%g must be finite and not negative", fn,
+                    (double)R->lr_t, (double)R->lr_rot);
+    if (!std::isfinite(A.beta1) || !std::isfinite(A.beta2) || A.beta1 < 0.0f || A.beta1 >= 1.0f || A.beta2 < 0.0f ||
+        A.beta2 >= 1.0f)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: betas (%g, %g) must lie in [0, 1)", fn, (double)A.beta1, (double)A.beta2);
+    if ((A.m == nullptr) != (A.v == nullptr))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both Adam moment buffers (m, v) or neither", fn);
+    if (R && (R->state == nullptr) != (A.m == nullptr))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give root_state with the Adam moment buffers (m, v), or none of them", fn);
+    const bool root_out = R && (R->rot_out || R->t_out || R->grad);
+    if (A.B > 0) {   // empty buffers have no address to give
+        if (!A.dof_out && !A.loss && !A.grad && !root_out)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: every output is NULL", fn);
+        if (!A.target_pos || !A.root_rot || !A.root_t) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    }
+    if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL model", fn);
+    if (clip && !m->has_limits)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: clip_angles requested but the model has no DOF limits", fn);
+    const int J = m->topo->J;
+    if (J > kGroupMaxJ)
+        return fail(RTG_ERR_UNSUPPORTED, "%s: serves models of 1..%d joints (this one has %d)", fn, kGroupMaxJ, J);
+    if (A.B == 0) return RTG_OK;
+    if (J > 1 && !A.dof_in) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    if (J == 1) {   // no angles: only a fitted root can step; the kernel's unconditional first-element loads get readable memory
+        A.dof_in = A.root_rot;
+        A.m = A.v = A.dof_out = A.grad = nullptr;
+        if (!R || !R->fit_root) A.iters = 0;
+        if (!A.loss && !root_out) return RTG_OK;
+    }
+    if (R)
+        RTG_TRY(launch_dof_fit_root(m->topo->view(), m->view(), clip != 0, A, *R, as_stream(stream)), "k_dof_fit_root");
+    else
+        RTG_TRY(launch_dof_fit(m->topo->view(), m->view(), clip != 0, A, as_stream(stream)), "k_dof_fit");
+    return RTG_OK;
+}
+
+// what a mapping that retarget_tables refuses returns: more than kGroupMaxJ joints is a limit of ours, the rest the caller's
+int fail_tables(const char *fn, int Js, int Jt, const std::string &err)
+{
+    return fail(Js > kGroupMaxJ || Jt > kGroupMaxJ ? RTG_ERR_UNSUPPORTED : RTG_ERR_INVALID_ARGUMENT, "%s: %s", fn, err.c_str());
+}
+
+int make_taps(const double *w, int32_t radius, GaussTaps *taps, const char *fn)
+{
+    if (!w) return RTG_OK;
+    if (radius < 0 || radius > RTG_MAX_FILTER_RADIUS)
+        return fail(RTG_ERR_UNSUPPORTED, "%s: filter radius %d (max %d)", fn, radius, RTG_MAX_FILTER_RADIUS);
+    taps->radius = radius;
+    for (int i = 0; i < 2 * radius + 1; ++i) taps->w[i] = w[i];
+    return RTG_OK;
+}
+
+// A device error a previous launch of this solver reported (rtg.h RTG_DEVERR_*): returned once, then cleared.
+int take_device_error(uint32_t *word, const char *fn)
+{
+    const uint32_t e = word ? __atomic_exchange_n(word, 0u, __ATOMIC_ACQ_REL) : 0u;
+    if (e == 0) return RTG_OK;
+    return fail(RTG_ERR_DEVICE, "%s: a previous launch reported device error 0x%x%s", fn, e,
+                (e & RTG_DEVERR_HANDOVER_TIMEOUT) ? " (a wave hand-over timed out: that launch's outputs are not valid)"
+                                                  : "");
 }
 
 }  // namespace
@@ -135,73 +383,46 @@ int rtg_device_count(void)
 int rtg_topology_create(const int32_t *parents, const float *local_t, const float *tree_quat, int32_t J,
                         rtg_topology_t *out)
 {
-    if (!out) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_topology_create: out is NULL");
+    const char *fn = "rtg_topology_create";
+    if (!out) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: out is NULL", fn);
     *out = nullptr;
-    if (!parents || !local_t) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_topology_create: NULL parents/local_t");
-    if (J < 1 || J > 1024) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_topology_create: J=%d out of range", J);
-    // parent-indexed tree in topological order (skeleton3d.py:87-88 asserts equal lengths;
-    // the FK loop kinematics.py:27 requires parents before children)
-    if (parents[0] != -1) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_topology_create: joint 0 must be the root");
-    for (int j = 1; j < J; ++j)
-        if (parents[j] < 0 || parents[j] >= j)
-            return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_topology_create: parents[%d]=%d is not < %d", j, parents[j], j);
-    rtg_topology_s *t = new (std::nothrow) rtg_topology_s();
-    if (!t) return fail(RTG_ERR_OUT_OF_MEMORY, "rtg_topology_create: host allocation failed");
+    if (!parents || !local_t) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL parents/local_t", fn);
+    if (J < 1 || J > 1024) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: J=%d out of range", fn, J);
+    RTG_CHECK(check_tree(fn, parents, J));
+    std::unique_ptr<rtg_topology_s> t(new (std::nothrow) rtg_topology_s());
+    if (!t) return fail(RTG_ERR_OUT_OF_MEMORY, "%s: host allocation failed", fn);
     t->J = J;
-    Q *tq = new (std::nothrow) Q[J];
-    if (!tq) {
-        delete t;
-        return fail(RTG_ERR_OUT_OF_MEMORY, "rtg_topology_create: host allocation failed");
-    }
+    t->h_parents.assign(parents, parents + J);
+    std::vector<Q> &tq = t->h_tree_quat;
+    tq.resize(J);
     for (int j = 0; j < J; ++j)
         tq[j] = tree_quat ? Q{tree_quat[4 * j], tree_quat[4 * j + 1], tree_quat[4 * j + 2], tree_quat[4 * j + 3]}
                           : Q{0.f, 0.f, 0.f, 1.f};
-    int rc = hip_check(hipMalloc(&t->d_parents, sizeof(int32_t) * J), "hipMalloc(parents)");
-    if (rc == RTG_OK) rc = hip_check(hipMalloc(&t->d_local_t, sizeof(V) * J), "hipMalloc(local_t)");
-    if (rc == RTG_OK) rc = hip_check(hipMalloc(&t->d_tree_quat, sizeof(Q) * J), "hipMalloc(tree_quat)");
-    if (rc == RTG_OK)
-        rc = hip_check(hipMemcpy(t->d_parents, parents, sizeof(int32_t) * J, hipMemcpyHostToDevice), "hipMemcpy");
-    if (rc == RTG_OK)
-        rc = hip_check(hipMemcpy(t->d_local_t, local_t, sizeof(V) * J, hipMemcpyHostToDevice), "hipMemcpy");
-    if (rc == RTG_OK) rc = hip_check(hipMemcpy(t->d_tree_quat, tq, sizeof(Q) * J, hipMemcpyHostToDevice), "hipMemcpy");
+    std::vector<V> lt(J);
+    for (int j = 0; j < J; ++j) lt[j] = v3(local_t, j);
+    RTG_CHECK(t->parents.alloc(J, "hipMalloc(parents)"));
+    RTG_CHECK(t->local_t.alloc(J, "hipMalloc(local_t)"));
+    RTG_CHECK(t->tree_quat.alloc(J, "hipMalloc(tree_quat)"));
+    RTG_CHECK(t->parents.upload(parents, J));
+    RTG_CHECK(t->local_t.upload(lt.data(), J));
+    RTG_CHECK(t->tree_quat.upload(tq.data(), J));
     // the lane-group schedule (rtg_fk.hip): J <= kGroupMaxJ, at most J steps
     const int gF = group_frames(J);
-    if (rc == RTG_OK && gF > 0) {
-        std::vector<V> lt(J);
-        for (int j = 0; j < J; ++j) lt[j] = v3(local_t, j);
+    if (gF > 0) {
         std::vector<GEnt> gs((size_t)J * (64 / gF));
-        const int steps = fk_group_schedule(parents, lt.data(), tq, J, gF, gs.data(), J);
+        const int steps = fk_group_schedule(parents, lt.data(), tq.data(), J, gF, gs.data(), J);
         if (steps > 0) {
-            rc = hip_check(hipMalloc(&t->d_gsched, sizeof(GEnt) * steps * (64 / gF)), "hipMalloc(group schedule)");
-            if (rc == RTG_OK)
-                rc = hip_check(hipMemcpy(t->d_gsched, gs.data(), sizeof(GEnt) * steps * (64 / gF), hipMemcpyHostToDevice),
-                               "hipMemcpy");
+            RTG_CHECK(t->gsched.alloc_upload(gs.data(), (size_t)steps * (64 / gF), "hipMalloc(group schedule)"));
             t->gF = gF;
             t->gsteps = steps;
         }
     }
-    t->h_parents.assign(parents, parents + J);
-    t->h_tree_quat.assign(tq, tq + J);
-    delete[] tq;
-    if (rc != RTG_OK) {
-        (void)hipFree(t->d_parents);
-        (void)hipFree(t->d_local_t);
-        (void)hipFree(t->d_tree_quat);
-        (void)hipFree(t->d_gsched);
-        delete t;
-        return rc;
-    }
-    *out = t;
+    *out = t.release();
     return RTG_OK;
 }
 
 int rtg_topology_destroy(rtg_topology_t t)
 {
-    if (!t) return RTG_OK;
-    (void)hipFree(t->d_parents);
-    (void)hipFree(t->d_local_t);
-    (void)hipFree(t->d_tree_quat);
-    (void)hipFree(t->d_gsched);
     delete t;
     return RTG_OK;
 }
@@ -209,63 +430,39 @@ int rtg_topology_destroy(rtg_topology_t t)
 int rtg_topology_num_joints(rtg_topology_t t) { return t ? t->J : -1; }
 
 // ---------------------------------------------------------------- kinematics
-static int check_fk(rtg_topology_t t, const void *a, const void *b, const void *c, const void *d, int64_t B,
-                    const char *fn)
-{
-    if (!t) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL topology", fn);
-    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: negative batch %lld", fn, (long long)B);
-    if (B > 0 && (!a || !b || !c || !d)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
-    return RTG_OK;
-}
-
 int rtg_fk_f32(rtg_topology_t t, const float *local_rot, const float *root_t, int64_t B, float *g_rot, float *g_pos,
                rtg_stream_t stream)
 {
-    int rc = check_fk(t, local_rot, root_t, g_rot, g_pos, B, "rtg_fk_f32");
-    if (rc != RTG_OK || B == 0) return rc;
-    RTG_TRY(launch_fk(t->view(), false, local_rot, root_t, B, g_rot, g_pos, as_stream(stream)), "k_fk");
-    return RTG_OK;
+    return run_fk("rtg_fk_f32", false, t, local_rot, root_t, B, g_rot, g_pos, stream);
 }
 
 int rtg_state_fk_f32(rtg_topology_t t, const float *local_rot, const float *root_t, int64_t B, float *g_rot,
                      float *g_pos, rtg_stream_t stream)
 {
-    int rc = check_fk(t, local_rot, root_t, g_rot, g_pos, B, "rtg_state_fk_f32");
-    if (rc != RTG_OK || B == 0) return rc;
-    RTG_TRY(launch_fk(t->view(), true, local_rot, root_t, B, g_rot, g_pos, as_stream(stream)), "k_fk<state>");
-    return RTG_OK;
+    return run_fk("rtg_state_fk_f32", true, t, local_rot, root_t, B, g_rot, g_pos, stream);
 }
 
 int rtg_local_rotation_f32(rtg_topology_t t, const float *g_rot, int64_t B, float *local_rot, rtg_stream_t stream)
 {
-    int rc = check_fk(t, g_rot, local_rot, g_rot, local_rot, B, "rtg_local_rotation_f32");
-    if (rc != RTG_OK || B == 0) return rc;
-    RTG_TRY(launch_local_rotation(t->view(), false, g_rot, B, local_rot, as_stream(stream)), "k_local_rotation");
-    return RTG_OK;
+    return run_local_rotation("rtg_local_rotation_f32", false, t, g_rot, B, local_rot, stream);
 }
 
 int rtg_state_local_rotation_f32(rtg_topology_t t, const float *g_rot, int64_t B, float *local_rot,
                                  rtg_stream_t stream)
 {
-    int rc = check_fk(t, g_rot, local_rot, g_rot, local_rot, B, "rtg_state_local_rotation_f32");
-    if (rc != RTG_OK || B == 0) return rc;
-    RTG_TRY(launch_local_rotation(t->view(), true, g_rot, B, local_rot, as_stream(stream)), "k_local_rotation<state>");
-    return RTG_OK;
+    return run_local_rotation("rtg_state_local_rotation_f32", true, t, g_rot, B, local_rot, stream);
 }
 
+// (not a forward to rtg_kinematics_multi_f32: the messages name the function and count the segments differently)
 int rtg_fk_multi_f32(const rtg_fk_segment *segs, int32_t n, rtg_stream_t stream)
 {
+    const char *fn = "rtg_fk_multi_f32";
     if (n < 0 || n > RTG_MAX_SEGMENTS)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_fk_multi_f32: %d segments (max %d)", n, RTG_MAX_SEGMENTS);
-    if (n > 0 && !segs) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_fk_multi_f32: NULL segments");
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: %d segments (max %d)", fn, n, RTG_MAX_SEGMENTS);
+    if (n > 0 && !segs) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL segments", fn);
     FkMultiArgs A{};
     A.n = n;
-    for (int i = 0; i < n; ++i) {
-        const rtg_fk_segment &s = segs[i];
-        int rc = check_fk(s.topo, s.local_rot, s.root_t, s.g_rot, s.g_pos, s.B, "rtg_fk_multi_f32");
-        if (rc != RTG_OK) return rc;
-        A.seg[i] = FkSeg{s.topo->view(), s.local_rot, s.root_t, s.g_rot, s.g_pos, s.B, 0};
-    }
+    RTG_CHECK(fill_fk_segments(fn, segs, n, A.seg));
     RTG_TRY(launch_fk_multi(A, as_stream(stream)), "k_fk_multi");
     return RTG_OK;
 }
@@ -273,23 +470,16 @@ int rtg_fk_multi_f32(const rtg_fk_segment *segs, int32_t n, rtg_stream_t stream)
 int rtg_kinematics_multi_f32(const rtg_fk_segment *fk, int32_t n_fk, const rtg_local_rotation_segment *inv,
                              int32_t n_inv, rtg_stream_t stream)
 {
+    const char *fn = "rtg_kinematics_multi_f32";
     if (n_fk < 0 || n_inv < 0 || n_fk + n_inv > RTG_MAX_SEGMENTS)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_kinematics_multi_f32: %d + %d segments (max %d in total)", n_fk,
-                    n_inv, RTG_MAX_SEGMENTS);
-    if ((n_fk > 0 && !fk) || (n_inv > 0 && !inv))
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_kinematics_multi_f32: NULL segments");
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: %d + %d segments (max %d in total)", fn, n_fk, n_inv, RTG_MAX_SEGMENTS);
+    if ((n_fk > 0 && !fk) || (n_inv > 0 && !inv)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL segments", fn);
     FkMultiArgs A{};
     A.n = n_fk + n_inv;
-    for (int i = 0; i < n_fk; ++i) {
-        const rtg_fk_segment &s = fk[i];
-        int rc = check_fk(s.topo, s.local_rot, s.root_t, s.g_rot, s.g_pos, s.B, "rtg_kinematics_multi_f32");
-        if (rc != RTG_OK) return rc;
-        A.seg[i] = FkSeg{s.topo->view(), s.local_rot, s.root_t, s.g_rot, s.g_pos, s.B, 0};
-    }
+    RTG_CHECK(fill_fk_segments(fn, fk, n_fk, A.seg));
     for (int i = 0; i < n_inv; ++i) {
         const rtg_local_rotation_segment &s = inv[i];
-        int rc = check_fk(s.topo, s.g_rot, s.local_rot, s.g_rot, s.local_rot, s.B, "rtg_kinematics_multi_f32");
-        if (rc != RTG_OK) return rc;
+        RTG_CHECK(check_fk(s.topo, s.g_rot, s.local_rot, s.g_rot, s.local_rot, s.B, fn));
         A.seg[n_fk + i] = FkSeg{s.topo->view(), s.g_rot, nullptr, s.local_rot, nullptr, s.B, 1};
     }
     RTG_TRY(launch_fk_multi(A, as_stream(stream)), "k_fk_multi");
@@ -315,38 +505,25 @@ int rtg_dof_model_create(rtg_topology_t topo, const int32_t *axis, const float *
             return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_dof_model_create: axis[%d]=%d is not 0, 1 or 2", k, axis[k]);
     if ((lower == nullptr) != (upper == nullptr))
         return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_dof_model_create: give both DOF limit arrays or neither");
-    rtg_dof_model_s *m = new (std::nothrow) rtg_dof_model_s();
+    std::unique_ptr<rtg_dof_model_s> m(new (std::nothrow) rtg_dof_model_s());
     if (!m) return fail(RTG_ERR_OUT_OF_MEMORY, "rtg_dof_model_create: host allocation failed");
     m->topo = topo;
     m->has_limits = lower != nullptr;
-    const size_t na = sizeof(int32_t) * (n > 0 ? n : 1), nf = sizeof(float) * (n > 0 ? n : 1);
-    int rc = hip_check(hipMalloc(&m->d_axis, na), "hipMalloc(axis)");
-    if (rc == RTG_OK && n > 0) rc = hip_check(hipMemcpy(m->d_axis, axis, sizeof(int32_t) * n, hipMemcpyHostToDevice), "hipMemcpy");
-    if (rc == RTG_OK && m->has_limits) {
-        rc = hip_check(hipMalloc(&m->d_lower, nf), "hipMalloc(lower)");
-        if (rc == RTG_OK) rc = hip_check(hipMalloc(&m->d_upper, nf), "hipMalloc(upper)");
-        if (rc == RTG_OK && n > 0)
-            rc = hip_check(hipMemcpy(m->d_lower, lower, sizeof(float) * n, hipMemcpyHostToDevice), "hipMemcpy");
-        if (rc == RTG_OK && n > 0)
-            rc = hip_check(hipMemcpy(m->d_upper, upper, sizeof(float) * n, hipMemcpyHostToDevice), "hipMemcpy");
+    const size_t cap = n > 0 ? n : 1;   // a one-joint model still owns (unread) tables
+    RTG_CHECK(m->axis.alloc(cap, "hipMalloc(axis)"));
+    if (n > 0) RTG_CHECK(m->axis.upload(axis, n));
+    if (m->has_limits) {
+        RTG_CHECK(m->lower.alloc(cap, "hipMalloc(lower)"));
+        RTG_CHECK(m->upper.alloc(cap, "hipMalloc(upper)"));
+        if (n > 0) RTG_CHECK(m->lower.upload(lower, n));
+        if (n > 0) RTG_CHECK(m->upper.upload(upper, n));
     }
-    if (rc != RTG_OK) {
-        (void)hipFree(m->d_axis);
-        (void)hipFree(m->d_lower);
-        (void)hipFree(m->d_upper);
-        delete m;
-        return rc;
-    }
-    *out = m;
+    *out = m.release();
     return RTG_OK;
 }
 
 int rtg_dof_model_destroy(rtg_dof_model_t m)
 {
-    if (!m) return RTG_OK;
-    (void)hipFree(m->d_axis);
-    (void)hipFree(m->d_lower);
-    (void)hipFree(m->d_upper);
     delete m;
     return RTG_OK;
 }
@@ -362,31 +539,19 @@ int rtg_dof_fk_f32(rtg_dof_model_t m, const float *dof, const float *root_rot, c
     if ((m->topo->J > 1 && !dof) || !root_rot || !root_t || !g_rot || !g_pos)
         return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_dof_fk_f32: NULL buffer");
     if (m->topo->J == 1) dof = root_rot;   // no angles: the kernel's unconditional first-element load gets readable memory
-    const DofView D{m->d_axis, m->d_lower, m->d_upper};
-    RTG_TRY(launch_dof_fk(m->topo->view(), D, clip != 0, dof, root_rot, root_t, B, g_rot, g_pos, as_stream(stream)),
+    RTG_TRY(launch_dof_fk(m->topo->view(), m->view(), clip != 0, dof, root_rot, root_t, B, g_rot, g_pos,
+                          as_stream(stream)),
             "k_dof_fk");
     return RTG_OK;
 }
 
 // ---------------------------------------------------------------- gradients of the kinematics
-// the argument checks both backward entry points share (everything that needs no handle first)
-static int check_fk_backward(const char *fn, int64_t B, const void *grad_g_rot, const void *grad_g_pos, bool any_out)
-{
-    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)B);
-    if (B == 0) return RTG_OK;   // empty buffers have no address to give
-    if (!grad_g_rot && !grad_g_pos)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: both upstream gradients are NULL", fn);
-    if (!any_out) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: every output is NULL", fn);
-    return RTG_OK;
-}
-
 int rtg_dof_fk_backward_f32(rtg_dof_model_t m, const float *dof, const float *g_rot, const float *grad_g_rot,
                             const float *grad_g_pos, int64_t B, int clip, float *grad_dof, float *grad_root_rot,
                             float *grad_root_t, rtg_stream_t stream)
 {
-    int rc = check_fk_backward("rtg_dof_fk_backward_f32", B, grad_g_rot, grad_g_pos,
-                               grad_dof || grad_root_rot || grad_root_t);
-    if (rc != RTG_OK) return rc;
+    RTG_CHECK(check_fk_backward("rtg_dof_fk_backward_f32", B, grad_g_rot, grad_g_pos,
+                                grad_dof || grad_root_rot || grad_root_t));
     if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_dof_fk_backward_f32: NULL model");
     if (clip && !m->has_limits)
         return fail(RTG_ERR_INVALID_ARGUMENT,
@@ -398,7 +563,7 @@ int rtg_dof_fk_backward_f32(rtg_dof_model_t m, const float *dof, const float *g_
         dof = g_rot;
         grad_dof = nullptr;
     }
-    const DofView D{m->d_axis, m->d_lower, m->d_upper};
+    const DofView D = m->view();
     RTG_TRY(launch_fk_backward(m->topo->view(), &D, clip != 0, dof, g_rot, grad_g_rot, grad_g_pos, B, grad_dof,
                                grad_root_rot, grad_root_t, as_stream(stream)),
             "k_fk_bwd<dof>");
@@ -409,8 +574,7 @@ int rtg_fk_backward_f32(rtg_topology_t t, const float *local_rot, const float *g
                         const float *grad_g_pos, int64_t B, float *grad_local_rot, float *grad_root_t,
                         rtg_stream_t stream)
 {
-    int rc = check_fk_backward("rtg_fk_backward_f32", B, grad_g_rot, grad_g_pos, grad_local_rot || grad_root_t);
-    if (rc != RTG_OK) return rc;
+    RTG_CHECK(check_fk_backward("rtg_fk_backward_f32", B, grad_g_rot, grad_g_pos, grad_local_rot || grad_root_t));
     if (!t) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_fk_backward_f32: NULL topology");
     if (B == 0) return RTG_OK;
     if (!local_rot || !g_rot) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_fk_backward_f32: NULL buffer");
@@ -426,41 +590,9 @@ int rtg_dof_fit_f32(rtg_dof_model_t m, const float *target_pos, const float *wei
                     float beta2, float eps, int32_t step0, float *mom1, float *mom2, float *dof_out, float *loss,
                     float *grad, rtg_stream_t stream)
 {
-    const char *fn = "rtg_dof_fit_f32";
-    // everything that needs no handle first
-    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)B);
-    if (iters < 0 || iters > RTG_DOF_FIT_MAX_ITERS)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: iters=%d is outside 0..%d", fn, iters, RTG_DOF_FIT_MAX_ITERS);
-    if (step0 < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: step0=%d < 0", fn, step0);
-    if (!std::isfinite(lr) || !std::isfinite(eps))
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: lr=%g, eps=%g must be finite", fn, (double)lr, (double)eps);
-    if (!std::isfinite(beta1) || !std::isfinite(beta2) || beta1 < 0.0f || beta1 >= 1.0f || beta2 < 0.0f || beta2 >= 1.0f)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: betas (%g, %g) must lie in [0, 1)", fn, (double)beta1, (double)beta2);
-    if ((mom1 == nullptr) != (mom2 == nullptr))
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both Adam moment buffers (m, v) or neither", fn);
-    if (B > 0) {   // empty buffers have no address to give
-        if (!dof_out && !loss && !grad) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: every output is NULL", fn);
-        if (!target_pos || !root_rot || !root_t) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
-    }
-    if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL model", fn);
-    if (clip && !m->has_limits)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: clip_angles requested but the model has no DOF limits", fn);
-    const int J = m->topo->J;
-    if (J > kGroupMaxJ)
-        return fail(RTG_ERR_UNSUPPORTED, "%s: serves models of 1..%d joints (this one has %d)", fn, kGroupMaxJ, J);
-    if (B == 0) return RTG_OK;
-    if (J > 1 && !dof_in) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
-    if (J == 1) {   // no angles: nothing to step; the kernel's unconditional first-element loads get readable memory
-        dof_in = root_rot;
-        mom1 = mom2 = dof_out = grad = nullptr;
-        iters = 0;
-        if (!loss) return RTG_OK;
-    }
-    const DofView D{m->d_axis, m->d_lower, m->d_upper};
     const DofFitArgs A{target_pos, weight, root_rot, root_t, dof_in, B, iters, step0, lr, beta1, beta2, eps,
                        mom1, mom2, dof_out, loss, grad};
-    RTG_TRY(launch_dof_fit(m->topo->view(), D, clip != 0, A, as_stream(stream)), "k_dof_fit");
-    return RTG_OK;
+    return run_dof_fit("rtg_dof_fit_f32", m, clip, A, nullptr, stream);
 }
 
 int rtg_dof_fit_root_f32(rtg_dof_model_t m, const float *target_pos, const float *weight, const float *root_rot,
@@ -470,50 +602,10 @@ int rtg_dof_fit_root_f32(rtg_dof_model_t m, const float *target_pos, const float
                          float *root_rot_out, float *root_t_out, float *loss, float *grad, float *grad_root,
                          rtg_stream_t stream)
 {
-    const char *fn = "rtg_dof_fit_root_f32";
-    // everything that needs no handle first
-    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)B);
-    if (fit_root & ~(RTG_FIT_ROOT_T | RTG_FIT_ROOT_ROT))
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: fit_root=%d has unknown bits", fn, fit_root);
-    if (iters < 0 || iters > RTG_DOF_FIT_MAX_ITERS)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: iters=%d is outside 0..%d", fn, iters, RTG_DOF_FIT_MAX_ITERS);
-    if (step0 < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: step0=%d < 0", fn, step0);
-    if (!std::isfinite(lr) || !std::isfinite(eps))
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: lr=%g, eps=%g must be finite", fn, (double)lr, (double)eps);
-    if (!std::isfinite(lr_root_t) || !std::isfinite(lr_root_rot) || lr_root_t < 0.0f || lr_root_rot < 0.0f)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: lr_root_t=%g, lr_root_rot=%g must be finite and not negative", fn,
-                    (double)lr_root_t, (double)lr_root_rot);
-    if (!std::isfinite(beta1) || !std::isfinite(beta2) || beta1 < 0.0f || beta1 >= 1.0f || beta2 < 0.0f || beta2 >= 1.0f)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: betas (%g, %g) must lie in [0, 1)", fn, (double)beta1, (double)beta2);
-    if ((mom1 == nullptr) != (mom2 == nullptr))
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both Adam moment buffers (m, v) or neither", fn);
-    if ((root_state == nullptr) != (mom1 == nullptr))
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give root_state with the Adam moment buffers (m, v), or none of them", fn);
-    if (B > 0) {   // empty buffers have no address to give
-        if (!dof_out && !root_rot_out && !root_t_out && !loss && !grad && !grad_root)
-            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: every output is NULL", fn);
-        if (!target_pos || !root_rot || !root_t) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
-    }
-    if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL model", fn);
-    if (clip && !m->has_limits)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: clip_angles requested but the model has no DOF limits", fn);
-    const int J = m->topo->J;
-    if (J > kGroupMaxJ)
-        return fail(RTG_ERR_UNSUPPORTED, "%s: serves models of 1..%d joints (this one has %d)", fn, kGroupMaxJ, J);
-    if (B == 0) return RTG_OK;
-    if (J > 1 && !dof_in) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
-    if (J == 1) {   // no angles: only the root can step; the kernel's unconditional first-element loads get readable memory
-        dof_in = root_rot;
-        mom1 = mom2 = dof_out = grad = nullptr;
-        if (!fit_root) iters = 0;
-        if (!root_rot_out && !root_t_out && !loss && !grad_root) return RTG_OK;
-    }
-    const DofView D{m->d_axis, m->d_lower, m->d_upper};
     const DofFitArgs A{target_pos, weight, root_rot, root_t, dof_in, B, iters, step0, lr, beta1, beta2, eps,
                        mom1, mom2, dof_out, loss, grad};
     const DofFitRootArgs R{fit_root, lr_root_t, lr_root_rot, root_state, root_rot_out, root_t_out, grad_root};
-    RTG_TRY(launch_dof_fit_root(m->topo->view(), D, clip != 0, A, R, as_stream(stream)), "k_dof_fit_root");
-    return RTG_OK;
+    return run_dof_fit("rtg_dof_fit_root_f32", m, clip, A, &R, stream);
 }
 
 // ---------------------------------------------------------------- SkeletonState.retarget_to
@@ -522,22 +614,14 @@ int rtg_retarget_plan_tables(const int32_t *src_parents, int32_t Js, const int32
                              int32_t *src_reduced_parents, int32_t *kept_tgt, int32_t *tgt_reduced_parents,
                              int32_t *perm, int32_t *src_of)
 {
-    if (!src_parents || !tgt_parents)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_plan_tables: NULL parents");
-    for (int side = 0; side < 2; ++side) {   // the trees rtg_topology_create accepts
-        const int32_t *p = side ? tgt_parents : src_parents;
-        const int J = side ? Jt : Js;
-        if (J >= 1 && p[0] != -1)
-            return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_plan_tables: joint 0 must be the root");
-        for (int j = 1; j < J; ++j)
-            if (p[j] < 0 || p[j] >= j)
-                return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_plan_tables: parents[%d]=%d is not < %d", j, p[j], j);
-    }
+    const char *fn = "rtg_retarget_plan_tables";
+    if (!src_parents || !tgt_parents) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL parents", fn);
+    RTG_CHECK(check_tree(fn, src_parents, Js));   // the trees rtg_topology_create accepts
+    RTG_CHECK(check_tree(fn, tgt_parents, Jt));
     RetargetTables T;
     std::string err;
     if (!retarget_tables(src_parents, Js, tgt_parents, Jt, src_joint, tgt_joint, K, T, err))
-        return fail(Js > kGroupMaxJ || Jt > kGroupMaxJ ? RTG_ERR_UNSUPPORTED : RTG_ERR_INVALID_ARGUMENT,
-                    "rtg_retarget_plan_tables: %s", err.c_str());
+        return fail_tables(fn, Js, Jt, err);
     auto put = [](int32_t *dst, const std::vector<int32_t> &v) {
         if (dst) memcpy(dst, v.data(), sizeof(int32_t) * v.size());
     };
@@ -566,9 +650,8 @@ int rtg_retarget_plan_create(rtg_topology_t src, rtg_topology_t tgt, const int32
     RetargetTables T;
     std::string err;
     if (!retarget_tables(src->h_parents.data(), Js, tgt->h_parents.data(), Jt, src_joint, tgt_joint, K, T, err))
-        return fail(Js > kGroupMaxJ || Jt > kGroupMaxJ ? RTG_ERR_UNSUPPORTED : RTG_ERR_INVALID_ARGUMENT, "%s: %s", fn,
-                    err.c_str());
-    rtg_retarget_plan_s *p = new (std::nothrow) rtg_retarget_plan_s();
+        return fail_tables(fn, Js, Jt, err);
+    std::unique_ptr<rtg_retarget_plan_s> p(new (std::nothrow) rtg_retarget_plan_s());
     if (!p) return fail(RTG_ERR_OUT_OF_MEMORY, "%s: host allocation failed", fn);
     std::vector<float> blob;
     RetargetView &V_ = p->view;
@@ -589,50 +672,36 @@ int rtg_retarget_plan_create(rtg_topology_t src, rtg_topology_t tgt, const int32
     memcpy(&h[o_sraw], src_tpose_local_rot, sizeof(float) * 4 * Js);
     memcpy(&h[o_st], src_tpose_root_t, sizeof(float) * 3);
     memcpy(&h[o_traw], tgt_tpose_local_rot, sizeof(float) * 4 * Jt);
-    float *ws = nullptr;
-    int rc = hip_check(hipMalloc(&ws, sizeof(float) * n_ws), "hipMalloc(plan scratch)");
-    if (rc == RTG_OK) rc = hip_check(hipMalloc(&p->d_blob, sizeof(float) * blob.size()), "hipMalloc(plan blob)");
-    if (rc == RTG_OK) rc = hip_check(hipMemcpy(ws, h.data(), sizeof(float) * n_ws, hipMemcpyHostToDevice), "hipMemcpy");
-    if (rc == RTG_OK)
-        rc = hip_check(hipMemcpy(p->d_blob, blob.data(), sizeof(float) * blob.size(), hipMemcpyHostToDevice), "hipMemcpy");
-    V_.blob = p->d_blob;
-    if (rc == RTG_OK)
-        rc = hip_check(launch_quat_op(RTG_OP_QUAT_NORMALIZE, ws + o_sraw, nullptr, nullptr, Js, ws + o_sr, nullptr),
-                       "quat_normalize(source t-pose)");
-    if (rc == RTG_OK)
-        rc = hip_check(launch_quat_op(RTG_OP_QUAT_NORMALIZE, ws + o_traw, nullptr, nullptr, Jt, ws + o_tr, nullptr),
-                       "quat_normalize(target t-pose)");
-    if (rc == RTG_OK)
-        rc = hip_check(launch_retarget_to(V_, true, ws + o_sr, ws + o_st, 1, nullptr, nullptr, ws + o_d, nullptr),
-                       "k_retarget_to(t-pose)");
-    if (rc == RTG_OK)
-        rc = hip_check(launch_fk(tgt->view(), true, ws + o_tr, ws + o_tt, 1, ws + o_g, ws + o_p, nullptr),
-                       "k_fk<state>(target t-pose)");
-    if (rc == RTG_OK) rc = hip_check(hipMemcpy(h.data(), ws, sizeof(float) * n_ws, hipMemcpyDeviceToHost), "hipMemcpy");
-    if (rc == RTG_OK) {
-        for (int k = 0; k < K; ++k) {
-            float *cg = &blob[4 * ((size_t)V_.o_cg + k)], *tg = &blob[4 * ((size_t)V_.o_tg + k)];
-            const float *g = &h[o_d + 4 * (size_t)k], *t = &h[o_g + 4 * (size_t)T.kept_t[k]];
-            cg[0] = -g[0], cg[1] = -g[1], cg[2] = -g[2], cg[3] = g[3];   // quat_inverse = the conjugate (:214-219)
-            memcpy(tg, t, sizeof(float) * 4);
-        }
-        V_.t_tp = V{h[o_d + 4 * (size_t)K], h[o_d + 4 * (size_t)K + 1], h[o_d + 4 * (size_t)K + 2]};
-        rc = hip_check(hipMemcpy(p->d_blob, blob.data(), sizeof(float) * blob.size(), hipMemcpyHostToDevice), "hipMemcpy");
+    DevBuf<float> scratch;   // gone when this function returns
+    RTG_CHECK(scratch.alloc(n_ws, "hipMalloc(plan scratch)"));
+    RTG_CHECK(p->blob.alloc(blob.size(), "hipMalloc(plan blob)"));
+    RTG_CHECK(scratch.upload(h.data(), n_ws));
+    RTG_CHECK(p->blob.upload(blob.data(), blob.size()));
+    V_.blob = p->blob.get();
+    float *ws = scratch.get();
+    RTG_TRY(launch_quat_op(RTG_OP_QUAT_NORMALIZE, ws + o_sraw, nullptr, nullptr, Js, ws + o_sr, nullptr),
+            "quat_normalize(source t-pose)");
+    RTG_TRY(launch_quat_op(RTG_OP_QUAT_NORMALIZE, ws + o_traw, nullptr, nullptr, Jt, ws + o_tr, nullptr),
+            "quat_normalize(target t-pose)");
+    RTG_TRY(launch_retarget_to(V_, true, ws + o_sr, ws + o_st, 1, nullptr, nullptr, ws + o_d, nullptr),
+            "k_retarget_to(t-pose)");
+    RTG_TRY(launch_fk(tgt->view(), true, ws + o_tr, ws + o_tt, 1, ws + o_g, ws + o_p, nullptr),
+            "k_fk<state>(target t-pose)");
+    RTG_TRY(hipMemcpy(h.data(), ws, sizeof(float) * n_ws, hipMemcpyDeviceToHost), "hipMemcpy");
+    for (int k = 0; k < K; ++k) {
+        float *cg = &blob[4 * ((size_t)V_.o_cg + k)], *tg = &blob[4 * ((size_t)V_.o_tg + k)];
+        const float *g = &h[o_d + 4 * (size_t)k], *t = &h[o_g + 4 * (size_t)T.kept_t[k]];
+        cg[0] = -g[0], cg[1] = -g[1], cg[2] = -g[2], cg[3] = g[3];   // quat_inverse = the conjugate (:214-219)
+        memcpy(tg, t, sizeof(float) * 4);
     }
-    (void)hipFree(ws);
-    if (rc != RTG_OK) {
-        (void)hipFree(p->d_blob);
-        delete p;
-        return rc;
-    }
-    *out = p;
+    V_.t_tp = V{h[o_d + 4 * (size_t)K], h[o_d + 4 * (size_t)K + 1], h[o_d + 4 * (size_t)K + 2]};
+    RTG_CHECK(p->blob.upload(blob.data(), blob.size()));
+    *out = p.release();
     return RTG_OK;
 }
 
 int rtg_retarget_plan_destroy(rtg_retarget_plan_t p)
 {
-    if (!p) return RTG_OK;
-    (void)hipFree(p->d_blob);
     delete p;
     return RTG_OK;
 }
@@ -656,8 +725,7 @@ int rtg_ingest_vtrdyn_f32(const float *bp, const float *lhp, const float *rhp, i
                           float *lh, float *rh, uint8_t *valid, rtg_stream_t stream)
 {
     if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_ingest_vtrdyn_f32: B < 0");
-    if (layout != RTG_LAYOUT_AOS && layout != RTG_LAYOUT_SOA)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_ingest_vtrdyn_f32: bad layout %d", layout);
+    RTG_CHECK(check_layout("rtg_ingest_vtrdyn_f32", layout));
     if (B == 0) return RTG_OK;
     if (!bp || !lhp || !rhp || !body || !lh || !rh || !valid)
         return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_ingest_vtrdyn_f32: NULL buffer");
@@ -680,31 +748,19 @@ int rtg_rot_ingest_create(int32_t J_in, int32_t J_out, const int32_t *src, const
     for (int j = 0; src && j < J_out; ++j)
         if (src[j] < 0 || src[j] >= J_in)
             return fail(RTG_ERR_INVALID_ARGUMENT, "%s: src[%d] = %d outside 0..%d", fn, j, src[j], J_in - 1);
-    rtg_rot_ingest_s *h = new (std::nothrow) rtg_rot_ingest_s();
+    std::unique_ptr<rtg_rot_ingest_s> h(new (std::nothrow) rtg_rot_ingest_s());
     if (!h) return fail(RTG_ERR_OUT_OF_MEMORY, "%s: host allocation failed", fn);
     std::vector<float> blob;
     rot_ingest_blob(J_in, J_out, src, pre, post, blob, h->view);
-    int rc = hip_check(hipMalloc(&h->d_blob, sizeof(float) * blob.size()), "hipMalloc(rot ingest blob)");
-    if (rc == RTG_OK)
-        rc = hip_check(hipMemcpy(h->d_blob, blob.data(), sizeof(float) * blob.size(), hipMemcpyHostToDevice), "hipMemcpy");
-    if (rc == RTG_OK) rc = hip_check(launch_rot_ingest_tab(h->d_blob + 4 * h->view.o_tab, nullptr), "k_rot_ingest_tab");
-    if (rc == RTG_OK) rc = hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
-    if (rc != RTG_OK) {
-        (void)hipFree(h->d_blob);
-        delete h;
-        return rc;
-    }
-    h->view.blob = h->d_blob;
-    *out = h;
+    RTG_CHECK(h->blob.alloc_upload(blob.data(), blob.size(), "hipMalloc(rot ingest blob)"));
+    RTG_TRY(launch_rot_ingest_tab(h->blob.get() + 4 * h->view.o_tab, nullptr), "k_rot_ingest_tab");
+    RTG_TRY(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+    h->view.blob = h->blob.get();
+    *out = h.release();
     return RTG_OK;
 }
 
-void rtg_rot_ingest_destroy(rtg_rot_ingest_t h)
-{
-    if (!h) return;
-    (void)hipFree(h->d_blob);
-    delete h;
-}
+void rtg_rot_ingest_destroy(rtg_rot_ingest_t h) { delete h; }
 
 int rtg_rot_ingest_f32(rtg_rot_ingest_t h, const float *q, int64_t B, int layout, float *out, rtg_stream_t stream)
 {
@@ -712,15 +768,14 @@ int rtg_rot_ingest_f32(rtg_rot_ingest_t h, const float *q, int64_t B, int layout
     // what does not depend on the handle first: a caller (and a test on a machine without a GPU) sees these reasons
     // whatever the handle is
     if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B < 0", fn);
-    if (layout != RTG_LAYOUT_AOS && layout != RTG_LAYOUT_SOA)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: bad layout %d", fn, layout);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(q), b = reinterpret_cast<uintptr_t>(out);
+    RTG_CHECK(check_layout(fn, layout));
     if (B > 0 && (!q || !out)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
-    if (B > 0 && ((a | b) & 15)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: q / out not 16-byte aligned", fn);
+    if (B > 0 && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(out)) & 15))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: q / out not 16-byte aligned", fn);
     if (!h) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL handle", fn);
     if (B == 0) return RTG_OK;
-    const uint64_t na = (uint64_t)B * h->view.J_in * 16, nb = (uint64_t)B * h->view.J_out * 16;
-    if (a < b + nb && b < a + na) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: q and out overlap", fn);
+    const Span in{q, (uint64_t)B * h->view.J_in * 16, "q"}, o{out, (uint64_t)B * h->view.J_out * 16, "out"};
+    RTG_CHECK(check_overlap(fn, &in, 1, &o, 1));
     RTG_TRY(launch_rot_ingest(h->view, q, B, layout, out, as_stream(stream)), "k_rot_ingest");
     return RTG_OK;
 }
@@ -747,28 +802,16 @@ int rtg_motion_lib_create(const int64_t *start, const int32_t *len, const float 
             return fail(RTG_ERR_INVALID_ARGUMENT, "%s: fps[%d]=%g must be finite and positive", fn, c, (double)fps[c]);
         tab[c] = MotionClip{start[c], len[c], fps[c]};
     }
-    rtg_motion_lib_s *h = new (std::nothrow) rtg_motion_lib_s();
+    std::unique_ptr<rtg_motion_lib_s> h(new (std::nothrow) rtg_motion_lib_s());
     if (!h) return fail(RTG_ERR_OUT_OF_MEMORY, "%s: host allocation failed", fn);
-    int rc = hip_check(hipMalloc(&h->d_clips, sizeof(MotionClip) * C), "hipMalloc(motion clip table)");
-    if (rc == RTG_OK)
-        rc = hip_check(hipMemcpy(h->d_clips, tab.data(), sizeof(MotionClip) * C, hipMemcpyHostToDevice), "hipMemcpy");
-    if (rc != RTG_OK) {
-        (void)hipFree(h->d_clips);
-        delete h;
-        return rc;
-    }
+    RTG_CHECK(h->clips.alloc_upload(tab.data(), C, "hipMalloc(motion clip table)"));
     h->C = C;
     h->F_total = F_total;
-    *out = h;
+    *out = h.release();
     return RTG_OK;
 }
 
-void rtg_motion_lib_destroy(rtg_motion_lib_t h)
-{
-    if (!h) return;
-    (void)hipFree(h->d_clips);
-    delete h;
-}
+void rtg_motion_lib_destroy(rtg_motion_lib_t h) { delete h; }
 
 int rtg_motion_sample_f32(rtg_topology_t topo, rtg_motion_lib_t lib, const float *rot, const float *root_t,
                           const float *vec, int32_t K, const int32_t *clip, const float *time, int64_t N, int flags,
@@ -801,31 +844,21 @@ int rtg_motion_sample_f32(rtg_topology_t topo, rtg_motion_lib_t lib, const float
     if (!topo) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL topology", fn);
     if (!lib) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL library", fn);
     const int J = topo->J;
-    if (J > kGroupMaxJ || !topo->d_gsched)
+    if (J > kGroupMaxJ || !topo->gsched.get())
         return fail(RTG_ERR_UNSUPPORTED, "%s: serves skeletons of 1..%d joints (this one has %d)", fn, kGroupMaxJ, J);
     if (N == 0) return RTG_OK;
     {   // no output may overlap an input (or another output)
-        struct Span { const void *p; uint64_t n; const char *name; };
         const uint64_t Ft = (uint64_t)lib->F_total, n = (uint64_t)N, j = (uint64_t)J, k = (uint64_t)K;
         const Span in[] = {{rot, Ft * j * 16, "rot"}, {root_t, Ft * 12, "root_t"}, {vec, Ft * k * 12, "vec"},
                            {clip, n * 4, "clip"}, {time, n * 4, "time"}};
         const Span outs[] = {{local_rot_out, n * j * 16, "local_rot_out"}, {root_t_out, n * 12, "root_t_out"},
                              {vec_out, n * k * 12, "vec_out"}, {g_rot, n * j * 16, "g_rot"}, {g_pos, n * j * 12, "g_pos"}};
-        auto hit = [](const Span &a, const Span &b) {
-            const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
-            return a.p && b.p && x < y + b.n && y < x + a.n;
-        };
-        for (size_t o = 0; o < 5; ++o) {
-            for (const Span &i : in)
-                if (hit(outs[o], i)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: %s and %s overlap", fn, outs[o].name, i.name);
-            for (size_t o2 = o + 1; o2 < 5; ++o2)
-                if (hit(outs[o], outs[o2]))
-                    return fail(RTG_ERR_INVALID_ARGUMENT, "%s: %s and %s overlap", fn, outs[o].name, outs[o2].name);
-        }
+        RTG_CHECK(check_overlap(fn, outs, 5, in, 5));
     }
     const MotionSampleArgs A{rot, root_t, vec, K, clip, time, N, local_rot_out, root_t_out, vec_out, g_rot, g_pos};
-    RTG_TRY(launch_motion_sample(topo->view(), MotionLibView{lib->d_clips, lib->C}, (flags & RTG_MOTION_NORMALIZE) != 0,
-                                 global, (flags & RTG_MOTION_STATE) != 0, A, as_stream(stream)),
+    RTG_TRY(launch_motion_sample(topo->view(), MotionLibView{lib->clips.get(), lib->C},
+                                 (flags & RTG_MOTION_NORMALIZE) != 0, global, (flags & RTG_MOTION_STATE) != 0, A,
+                                 as_stream(stream)),
             "k_motion_sample");
     return RTG_OK;
 }
@@ -916,75 +949,47 @@ int rtg_solver_create(int kind, const float *zl, const float *zg, const int32_t 
     default:
         return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_solver_create: unknown solver kind %d", kind);
     }
-    SolverConsts *d = nullptr;
-    RTG_TRY(hipMalloc(&d, sizeof(SolverConsts)), "hipMalloc(solver consts)");
-    int rc = hip_check(hipMemcpy(d, &C, sizeof C, hipMemcpyHostToDevice), "hipMemcpy(consts)");
-    if (rc == RTG_OK && kind != RTG_SOLVER_BODY_ROT) rc = hip_check(launch_solver_prep(d, nullptr), "k_solver_prep");
-    if (rc == RTG_OK) rc = hip_check(hipMemcpy(&C, d, sizeof C, hipMemcpyDeviceToHost), "hipMemcpy(consts)");
-    (void)hipFree(d);
-    if (rc != RTG_OK) return rc;
+    {   // the zero-pose-only terms: evaluated on the device, read back
+        DevBuf<SolverConsts> d;
+        RTG_CHECK(d.alloc(1, "hipMalloc(solver consts)"));
+        RTG_CHECK(d.upload(&C, 1, "hipMemcpy(consts)"));
+        if (kind != RTG_SOLVER_BODY_ROT) RTG_TRY(launch_solver_prep(d.get(), nullptr), "k_solver_prep");
+        RTG_TRY(hipMemcpy(&C, d.get(), sizeof C, hipMemcpyDeviceToHost), "hipMemcpy(consts)");
+    }
     // exp-map angle table: built once per solver on the current device (6.7 MiB), read by every launch
-    uint32_t *tab = nullptr;
-    RTG_TRY(hipMalloc(&tab, kAngTabWords * sizeof(uint32_t)), "hipMalloc(exp-map angle table)");
-    rc = hip_check(launch_build_ang_tab(tab, nullptr), "k_build_ang_tab");
-    if (rc == RTG_OK) rc = hip_check(hipStreamSynchronize(nullptr), "k_build_ang_tab");
-    if (rc != RTG_OK) {
-        (void)hipFree(tab);
-        return rc;
-    }
-    C.ang_tab = tab;
+    DevBuf<uint32_t> tab;
+    RTG_CHECK(tab.alloc(kAngTabWords, "hipMalloc(exp-map angle table)"));
+    RTG_TRY(launch_build_ang_tab(tab.get(), nullptr), "k_build_ang_tab");
+    RTG_TRY(hipStreamSynchronize(nullptr), "k_build_ang_tab");
+    C.ang_tab = tab.get();
     // the error word: host-mapped, so the device's report is read on the next call without a HIP call
-    uint32_t *h_err = nullptr;
-    rc = hip_check(hipHostMalloc(reinterpret_cast<void **>(&h_err), sizeof(uint32_t), hipHostMallocMapped),
-                   "hipHostMalloc(error word)");
-    if (rc == RTG_OK) {
-        *h_err = 0;
-        rc = hip_check(hipHostGetDevicePointer(reinterpret_cast<void **>(&C.err), h_err, 0), "hipHostGetDevicePointer");
-    }
-    rtg_solver_s *s = rc == RTG_OK ? new (std::nothrow) rtg_solver_s() : nullptr;
-    if (!s) {
-        (void)hipFree(tab);
-        if (h_err) (void)hipHostFree(h_err);
-        return rc != RTG_OK ? rc : fail(RTG_ERR_OUT_OF_MEMORY, "rtg_solver_create: host allocation failed");
-    }
+    PinnedWord err;
+    RTG_CHECK(err.alloc("hipHostMalloc(error word)"));
+    RTG_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&C.err), err.get(), 0), "hipHostGetDevicePointer");
+    std::unique_ptr<rtg_solver_s> s(new (std::nothrow) rtg_solver_s());
+    if (!s) return fail(RTG_ERR_OUT_OF_MEMORY, "rtg_solver_create: host allocation failed");
     s->kind = kind;
     s->precise = precise_gripper ? 1 : 0;
     s->consts = C;
-    s->d_ang_tab = tab;
-    s->h_err = h_err;
-    *out = s;
+    s->ang_tab = std::move(tab);
+    s->err = std::move(err);
+    *out = s.release();
     return RTG_OK;
 }
 
 int rtg_solver_destroy(rtg_solver_t s)
 {
-    if (s) {
-        (void)hipFree(s->d_ang_tab);
-        if (s->h_err) (void)hipHostFree(s->h_err);
-    }
     delete s;
     return RTG_OK;
-}
-
-// A device error a previous launch of this solver reported (rtg.h RTG_DEVERR_*): returned once, then cleared.
-static int take_device_error(uint32_t *word, const char *fn)
-{
-    const uint32_t e = word ? __atomic_exchange_n(word, 0u, __ATOMIC_ACQ_REL) : 0u;
-    if (e == 0) return RTG_OK;
-    return fail(RTG_ERR_DEVICE, "%s: a previous launch reported device error 0x%x%s", fn, e,
-                (e & RTG_DEVERR_HANDOVER_TIMEOUT) ? " (a wave hand-over timed out: that launch's outputs are not valid)"
-                                                  : "");
 }
 
 int rtg_retarget_f32(rtg_solver_t s, const float *in0, const float *in1, const float *in2, const float *in3,
                      int64_t B, int layout, float *dof, float *local_rot, float *body_rot, rtg_stream_t stream)
 {
     if (!s) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_f32: NULL solver");
-    int rc = take_device_error(s->h_err, "rtg_retarget_f32");
-    if (rc != RTG_OK) return rc;
+    RTG_CHECK(take_device_error(s->err.get(), "rtg_retarget_f32"));
     if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_f32: negative batch");
-    if (layout != RTG_LAYOUT_AOS && layout != RTG_LAYOUT_SOA)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_f32: bad layout %d", layout);
+    RTG_CHECK(check_layout("rtg_retarget_f32", layout));
     if (B == 0) return RTG_OK;
     if (B > (int64_t)0x7fffffff * 256) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_f32: batch too large");
     if (!dof) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_retarget_f32: NULL dof");
@@ -1027,6 +1032,7 @@ static void store_inbox_seq(float *in, uint32_t word)
     _mm_sfence();   // ... and the word itself out now
 }
 
+// (the inbox is handed to the caller raw: no owner here)
 int rtg_server_inbox_alloc(float **inbox)
 {
     if (!inbox) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_server_inbox_alloc: NULL inbox");
@@ -1125,52 +1131,30 @@ int rtg_cal_joint_quat_f32(const float *Z, const float *M, int32_t npts, int64_t
 
 int rtg_quat_in_xyz_axis_f32(const float *q, const char *seq, int64_t n, float *out, rtg_stream_t stream)
 {
-    if (!seq || std::strlen(seq) != 3) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_in_xyz_axis_f32: seq must have 3 axes");
-    int ax[3], lower[3];
-    for (int i = 0; i < 3; ++i)
-        if (!axis_of(seq[i], &ax[i], &lower[i]))
-            return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_in_xyz_axis_f32: bad axis '%c'", seq[i]);
-    if (lower[0] != lower[1] || lower[1] != lower[2])
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_in_xyz_axis_f32: mixed intrinsic/extrinsic seq '%s'", seq);
-    if (ax[0] == ax[1] || ax[1] == ax[2])
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_in_xyz_axis_f32: consecutive axes must differ ('%s')", seq);
-    if (n < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_in_xyz_axis_f32: negative n");
+    const char *fn = "rtg_quat_in_xyz_axis_f32";
+    int ax[3], extrinsic;
+    RTG_CHECK(parse_seq(fn, seq, ax, &extrinsic));
+    if (n < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: negative n", fn);
     if (n == 0) return RTG_OK;
-    if (!q || !out) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_in_xyz_axis_f32: NULL buffer");
-    RTG_TRY(launch_quat_in_xyz_axis(q, ax[0], ax[1], ax[2], lower[0], n, out, as_stream(stream)), "k_quat_in_xyz_axis");
+    if (!q || !out) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    RTG_TRY(launch_quat_in_xyz_axis(q, ax[0], ax[1], ax[2], extrinsic, n, out, as_stream(stream)), "k_quat_in_xyz_axis");
     return RTG_OK;
 }
 
 int rtg_quat_as_euler_f64(const float *q, const char *seq, int degrees, int64_t n, double *out, rtg_stream_t stream)
 {
-    if (!seq || std::strlen(seq) != 3) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_as_euler_f64: seq must have 3 axes");
-    int ax[3], lower[3];
-    for (int i = 0; i < 3; ++i)
-        if (!axis_of(seq[i], &ax[i], &lower[i]))
-            return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_as_euler_f64: bad axis '%c'", seq[i]);
-    if (lower[0] != lower[1] || lower[1] != lower[2])
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_as_euler_f64: mixed intrinsic/extrinsic seq '%s'", seq);
-    if (ax[0] == ax[1] || ax[1] == ax[2])
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_as_euler_f64: consecutive axes must differ ('%s')", seq);
-    if (n < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_as_euler_f64: negative n");
+    const char *fn = "rtg_quat_as_euler_f64";
+    int ax[3], extrinsic;
+    RTG_CHECK(parse_seq(fn, seq, ax, &extrinsic));
+    if (n < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: negative n", fn);
     if (n == 0) return RTG_OK;
-    if (!q || !out) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_quat_as_euler_f64: NULL buffer");
-    RTG_TRY(launch_quat_as_euler(q, ax[0], ax[1], ax[2], lower[0], degrees != 0, n, out, as_stream(stream)),
+    if (!q || !out) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    RTG_TRY(launch_quat_as_euler(q, ax[0], ax[1], ax[2], extrinsic, degrees != 0, n, out, as_stream(stream)),
             "k_quat_as_euler");
     return RTG_OK;
 }
 
 // ---------------------------------------------------------------- motion velocities
-static int make_taps(const double *w, int32_t radius, GaussTaps *taps, const char *fn)
-{
-    if (!w) return RTG_OK;
-    if (radius < 0 || radius > RTG_MAX_FILTER_RADIUS)
-        return fail(RTG_ERR_UNSUPPORTED, "%s: filter radius %d (max %d)", fn, radius, RTG_MAX_FILTER_RADIUS);
-    taps->radius = radius;
-    for (int i = 0; i < 2 * radius + 1; ++i) taps->w[i] = w[i];
-    return RTG_OK;
-}
-
 int rtg_linear_velocity_f32(const float *p, int64_t nseq, int64_t L, int64_t S, float dt, const double *w,
                             int32_t radius, float *tmp, float *out, rtg_stream_t stream)
 {
@@ -1179,8 +1163,7 @@ int rtg_linear_velocity_f32(const float *p, int64_t nseq, int64_t L, int64_t S, 
     if (L < 2) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_linear_velocity_f32: np.gradient needs >= 2 frames");
     if (!p || !out || (w && !tmp)) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_linear_velocity_f32: NULL buffer");
     GaussTaps taps{};
-    int rc = make_taps(w, radius, &taps, "rtg_linear_velocity_f32");
-    if (rc != RTG_OK) return rc;
+    RTG_CHECK(make_taps(w, radius, &taps, "rtg_linear_velocity_f32"));
     RTG_TRY(launch_linear_velocity(p, nseq, L, S, dt, w ? &taps : nullptr, tmp, out, as_stream(stream)),
             "rtg_linear_velocity_f32 launch");
     return RTG_OK;
@@ -1193,8 +1176,7 @@ int rtg_angular_velocity_f32(const float *r, int64_t nseq, int64_t L, int64_t J,
     if (nseq * L * J == 0) return RTG_OK;
     if (!r || !out || (w && !tmp)) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_angular_velocity_f32: NULL buffer");
     GaussTaps taps{};
-    int rc = make_taps(w, radius, &taps, "rtg_angular_velocity_f32");
-    if (rc != RTG_OK) return rc;
+    RTG_CHECK(make_taps(w, radius, &taps, "rtg_angular_velocity_f32"));
     RTG_TRY(launch_angular_velocity(r, nseq, L, J, dt, w ? &taps : nullptr, tmp, out, as_stream(stream)),
             "rtg_angular_velocity_f32 launch");
     return RTG_OK;
@@ -1213,53 +1195,47 @@ int rtg_box_probe(double *out, int32_t n_out, rtg_stream_t stream)
     const int nblk = prop.multiProcessorCount * 8;   // 8 workgroups of 4 waves per CU: 8 waves per SIMD
     const int nrec = (nblk + 63) / 64;
     const int64_t nf4 = (int64_t)1 << 26;             // 1 GiB per buffer: far beyond the 256 MiB Infinity Cache
-    float *src = nullptr, *dst = nullptr;
-    uint64_t *clk = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = hip_check(hipMalloc(&src, nf4 * 16), "hipMalloc(probe)");
-    if (rc == RTG_OK) rc = hip_check(hipMalloc(&dst, nf4 * 16), "hipMalloc(probe)");
-    if (rc == RTG_OK) rc = hip_check(hipMalloc(&clk, nrec * 2 * sizeof(uint64_t)), "hipMalloc(probe)");
-    if (rc == RTG_OK) rc = hip_check(hipEventCreate(&e0), "hipEventCreate");
-    if (rc == RTG_OK) rc = hip_check(hipEventCreate(&e1), "hipEventCreate");
-    if (rc == RTG_OK) rc = hip_check(hipMemsetAsync(src, 0, nf4 * 16, s), "hipMemsetAsync");
+    DevBuf<float> src, dst;
+    DevBuf<uint64_t> clk;
+    Event e0, e1;
+    RTG_CHECK(src.alloc((size_t)nf4 * 4, "hipMalloc(probe)"));
+    RTG_CHECK(dst.alloc((size_t)nf4 * 4, "hipMalloc(probe)"));
+    RTG_CHECK(clk.alloc((size_t)nrec * 2, "hipMalloc(probe)"));
+    RTG_CHECK(e0.create());
+    RTG_CHECK(e1.create());
+    RTG_TRY(hipMemsetAsync(src.get(), 0, nf4 * 16, s), "hipMemsetAsync");
+    // one timed launch between the two events, in ms
+    auto timed = [&](auto launch, const char *what, float *ms) {
+        RTG_TRY(hipEventRecord(e0.get(), s), "hipEventRecord");
+        RTG_TRY(launch(), what);
+        RTG_TRY(hipEventRecord(e1.get(), s), "hipEventRecord");
+        RTG_TRY(hipEventSynchronize(e1.get()), "hipEventSynchronize");
+        RTG_TRY(hipEventElapsedTime(ms, e0.get(), e1.get()), "hipEventElapsedTime");
+        return (int)RTG_OK;
+    };
     float best_valu = 1e30f, best_copy = 1e30f, ms = 0.0f;
-    for (int rep = 0; rc == RTG_OK && rep < 4; ++rep) {   // rep 0 warms up; the best of the other three counts
-        rc = hip_check(hipEventRecord(e0, s), "hipEventRecord");
-        if (rc == RTG_OK) rc = hip_check(launch_probe_valu(nblk, dst, clk, s), "k_probe_valu");
-        if (rc == RTG_OK) rc = hip_check(hipEventRecord(e1, s), "hipEventRecord");
-        if (rc == RTG_OK) rc = hip_check(hipEventSynchronize(e1), "hipEventSynchronize");
-        if (rc == RTG_OK) rc = hip_check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-        if (rc == RTG_OK && rep > 0 && ms < best_valu) best_valu = ms;
-        if (rc == RTG_OK) rc = hip_check(hipEventRecord(e0, s), "hipEventRecord");
-        if (rc == RTG_OK) rc = hip_check(launch_probe_copy(src, dst, nf4, s), "k_probe_copy");
-        if (rc == RTG_OK) rc = hip_check(hipEventRecord(e1, s), "hipEventRecord");
-        if (rc == RTG_OK) rc = hip_check(hipEventSynchronize(e1), "hipEventSynchronize");
-        if (rc == RTG_OK) rc = hip_check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-        if (rc == RTG_OK && rep > 0 && ms < best_copy) best_copy = ms;
+    for (int rep = 0; rep < 4; ++rep) {   // rep 0 warms up; the best of the other three counts
+        RTG_CHECK(timed([&] { return launch_probe_valu(nblk, dst.get(), clk.get(), s); }, "k_probe_valu", &ms));
+        if (rep > 0 && ms < best_valu) best_valu = ms;
+        RTG_CHECK(timed([&] { return launch_probe_copy(src.get(), dst.get(), nf4, s); }, "k_probe_copy", &ms));
+        if (rep > 0 && ms < best_copy) best_copy = ms;
     }
     uint64_t h[2 * 64] = {};
     const int nr = nrec < 64 ? nrec : 64;
-    if (rc == RTG_OK) rc = hip_check(hipMemcpy(h, clk, nr * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy");
-    if (rc == RTG_OK) {
-        double mhz[64];   // shader cycles per 100 MHz tick of each recording workgroup (the last rep), median
-        int m = 0;
-        for (int i = 0; i < nr; ++i)
-            if (h[2 * i + 1] > 0) mhz[m++] = 100.0 * (double)h[2 * i] / (double)h[2 * i + 1];
-        for (int i = 1; i < m; ++i)
-            for (int j = i; j > 0 && mhz[j - 1] > mhz[j]; --j) std::swap(mhz[j - 1], mhz[j]);
-        out[0] = m ? mhz[m / 2] : 0.0;
-        out[1] = (double)nblk * 256 * probe_valu_iters() * 8 / (best_valu * 1e-3) / 1e12;
-        out[2] = 2.0 * (double)nf4 * 16 / (best_copy * 1e-3) / 1e9;
-        out[3] = best_valu;
-        out[4] = best_copy;
-        out[5] = prop.multiProcessorCount;
-    }
-    (void)hipFree(src);
-    (void)hipFree(dst);
-    (void)hipFree(clk);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    RTG_TRY(hipMemcpy(h, clk.get(), nr * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy");
+    double mhz[64];   // shader cycles per 100 MHz tick of each recording workgroup (the last rep), median
+    int m = 0;
+    for (int i = 0; i < nr; ++i)
+        if (h[2 * i + 1] > 0) mhz[m++] = 100.0 * (double)h[2 * i] / (double)h[2 * i + 1];
+    for (int i = 1; i < m; ++i)
+        for (int j = i; j > 0 && mhz[j - 1] > mhz[j]; --j) std::swap(mhz[j - 1], mhz[j]);
+    out[0] = m ? mhz[m / 2] : 0.0;
+    out[1] = (double)nblk * 256 * probe_valu_iters() * 8 / (best_valu * 1e-3) / 1e12;
+    out[2] = 2.0 * (double)nf4 * 16 / (best_copy * 1e-3) / 1e9;
+    out[3] = best_valu;
+    out[4] = best_copy;
+    out[5] = prop.multiProcessorCount;
+    return RTG_OK;
 }
 
 // ---------------------------------------------------------------- side-kernel residency
@@ -1268,8 +1244,7 @@ int rtg_side_kernel_residency(int kind, int precise_gripper, int layout, int32_t
     if (!blocks_per_cu) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_side_kernel_residency: blocks_per_cu is NULL");
     if (kind < RTG_SOLVER_FULL_BODY_POS || kind > RTG_SOLVER_BODY_ROT)
         return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_side_kernel_residency: bad solver kind %d", kind);
-    if (layout != RTG_LAYOUT_AOS && layout != RTG_LAYOUT_SOA)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_side_kernel_residency: bad layout %d", layout);
+    RTG_CHECK(check_layout("rtg_side_kernel_residency", layout));
     int n = 0;
     RTG_TRY(side_kernel_residency(kind, precise_gripper != 0, layout, &n), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
     *blocks_per_cu = n;
@@ -1280,8 +1255,7 @@ int rtg_side_kernel_residency(int kind, int precise_gripper, int layout, int32_t
 int rtg_synth_full_body_f32(rtg_topology_t t, uint64_t seed, int64_t off, int64_t B, int layout, float *body,
                             float *lh, float *rh, float *body_rot, rtg_stream_t stream)
 {
-    if (layout != RTG_LAYOUT_AOS && layout != RTG_LAYOUT_SOA)
-        return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_synth_full_body_f32: bad layout %d", layout);
+    RTG_CHECK(check_layout("rtg_synth_full_body_f32", layout));
     if (!t || t->J != 59) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_synth_full_body_f32: needs the 59-joint VTRDYN_FULL topology");
     if (B < 0 || off < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "rtg_synth_full_body_f32: negative batch/offset");
     if (B == 0) return RTG_OK;

@@ -30,10 +30,9 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib
 from ._lib import LAYOUT_SOA, check, lib
 from .bridge import as_tensor, back
-from .runtime import _host_f32, _host_i32, dev_f32, layout_code, ptr, stream_handle
+from .runtime import Handle, _host_f32, _host_i32, dev_f32, layout_code, ptr, stream_handle
 from .safe_pickle import Call, Global, Obj, _run_vm
 
 # sim_full_body_teleop.py:109 (23 -> 21) and :111-112 (hand point order)
@@ -232,6 +231,18 @@ def _conj(q: np.ndarray) -> np.ndarray:
     return (q * np.array([-1.0, -1.0, -1.0, 1.0], np.float32)).astype(np.float32)   # quat_inverse, rotation3d.py:214-219
 
 
+class _RotIngestHandle(Handle):
+    """One ``rtg_rot_ingest_t``: a transform's constants on the current device."""
+    _destroy = "rtg_rot_ingest_destroy"
+
+    def __init__(self, J_in: int, src, pre, post):
+        ip, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        h = ctypes.c_void_p()
+        check(lib().rtg_rot_ingest_create(J_in, int(post.shape[0]), None if src is None else src.ctypes.data_as(ip),
+                                          pre.ctypes.data_as(fp), post.ctypes.data_as(fp), ctypes.byref(h)))
+        self._h = h
+
+
 class ZeroPoseTransform:
     """``out[f, j] = quat_mul_norm(quat_mul_norm(q[f, src[j]], pre), post[j])`` as one fused launch
     (``rtg_rot_ingest_t``): ``pre`` (4) one axis rotation, ``post`` (J_out, 4) the conjugated zero-pose rows, ``src``
@@ -308,15 +319,9 @@ class ZeroPoseTransform:
     def _handle(self, dev: torch.device):
         key = dev.index
         if key not in self._handles:
-            src, pre, post = self._consts()
-            ip, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
-            h = ctypes.c_void_p()
             with torch.cuda.device(dev):
-                check(lib().rtg_rot_ingest_create(self.J_in, int(post.shape[0]),
-                                                  None if src is None else src.ctypes.data_as(ip),
-                                                  pre.ctypes.data_as(fp), post.ctypes.data_as(fp), ctypes.byref(h)))
-            self._handles[key] = h
-        return self._handles[key]
+                self._handles[key] = _RotIngestHandle(self.J_in, *self._consts())
+        return self._handles[key].handle
 
     def __call__(self, q, layout="aos") -> torch.Tensor:
         """q (..., J_in, 4), on the CPU or the device -> the transformed rotations on the device: (..., J_out, 4), or
@@ -330,12 +335,6 @@ class ZeroPoseTransform:
                           dtype=torch.float32)
         check(lib().rtg_rot_ingest_f32(self._handle(t.device), ptr(t), B, code, ptr(out), stream_handle()))
         return out
-
-    def __del__(self):
-        for h in getattr(self, "_handles", {}).values():
-            if h is not None and h.value and _lib._lib is not None:
-                _lib._lib.rtg_rot_ingest_destroy(h)
-        self._handles = {}
 
 
 _NAMED: dict = {}

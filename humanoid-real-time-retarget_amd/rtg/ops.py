@@ -444,6 +444,24 @@ def _fit_inputs(model, target_pos, root_rot, root_t, dof, weight):
     return tp, d, rr, rt, w
 
 
+def _fit_state(model, d, dof0, iters, state):
+    """What dof_fit and pose_fit share around their launches: ``iters`` range-checked; the angles' optimiser state
+    ``(m, v, step)`` -- fresh (zeros, 0) for ``state`` None, else the caller's, copied (the launch updates it in
+    place); and ``as_dof0``, which gives an angle-shaped result (or None) the trailing 1 of a ``dof0`` passed as
+    (..., J-1, 1).  Returns (iters, m, v, step, as_dof0)."""
+    iters = int(iters)
+    if not 0 <= iters <= DOF_FIT_MAX_ITERS:
+        raise ValueError(f"iters must be in 0..{DOF_FIT_MAX_ITERS}, got {iters}")
+    if state is None:
+        m, v, step = torch.zeros_like(d), torch.zeros_like(d), 0
+    else:
+        m, v, step = state
+        m, v = (dev_f32(x, (model.num_dofs,), "state").reshape(d.shape).clone() for x in (m, v))
+        step = int(step)
+    tail = dof0 is not None and tuple(_as_tensor(dof0).shape) == tuple(d.shape) + (1,)
+    return iters, m, v, step, (lambda t: t.unsqueeze(-1) if tail and t is not None else t)
+
+
 def _fit_launch(model, clip, tp, w, rr, rt, d, iters=0, lr=0.0, betas=(0.9, 0.999), eps=1e-8, step0=0, m=None, v=None,
                 want_dof=False, want_loss=True, want_grad=False):
     """rtg_dof_fit_f32 on prepared tensors; m, v are updated in place.  Returns (dof_out, loss, grad), None where not
@@ -475,22 +493,11 @@ def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: 
     and the new state -- plus the gradient there (dof's shape) when ``return_grad``.  ``iters=0`` only evaluates.
     Raises RtgError without a GPU: there is no CPU fallback."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof0, weight)
-    iters = int(iters)
-    if not 0 <= iters <= DOF_FIT_MAX_ITERS:
-        raise ValueError(f"iters must be in 0..{DOF_FIT_MAX_ITERS}, got {iters}")
-    if state is None:
-        m, v, step = torch.zeros_like(d), torch.zeros_like(d), 0
-    else:
-        m, v, step = state
-        m, v = (dev_f32(x, (model.num_dofs,), "state").reshape(d.shape).clone() for x in (m, v))
-        step = int(step)
+    iters, m, v, step, as_dof0 = _fit_state(model, d, dof0, iters, state)
     out, loss, grad = _fit_launch(model, clip, tp, w, rr, rt, d.detach(), iters, lr, betas, eps, step, m, v,
                                   want_dof=True, want_grad=bool(return_grad))
-    if dof0 is not None and tuple(_as_tensor(dof0).shape) == tuple(d.shape) + (1,):
-        out = out.unsqueeze(-1)
-        grad = None if grad is None else grad.unsqueeze(-1)
-    res = (out, loss, (m, v, step + iters))
-    return res + (grad,) if return_grad else res
+    res = (as_dof0(out), loss, (m, v, step + iters))
+    return res + (as_dof0(grad),) if return_grad else res
 
 
 def keypoint_loss(model, dof, target_pos, root_rot, root_t, weight=None, clip: bool = False):
@@ -563,31 +570,22 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
     {dL/dt, dL/dq} there when ``return_grad``.  ``iters=0`` only evaluates.  Raises RtgError without a GPU: there is
     no CPU fallback."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot0, root_t0, dof0, weight)
-    iters = int(iters)
-    if not 0 <= iters <= DOF_FIT_MAX_ITERS:
-        raise ValueError(f"iters must be in 0..{DOF_FIT_MAX_ITERS}, got {iters}")
+    iters, m, v, step, as_dof0 = _fit_state(model, d, dof0, iters, None if state is None else (*state[:2], state[3]))
     lead = tuple(tp.shape[:-2])
     if state is None:
-        m, v, step = torch.zeros_like(d), torch.zeros_like(d), 0
         rs = torch.zeros(lead + (14,), device=d.device, dtype=torch.float32)
     else:
-        m, v, rs, step = state
-        m, v = (dev_f32(x, (model.num_dofs,), "state").reshape(d.shape).clone() for x in (m, v))
-        rs = dev_f32(rs, (14,), "root_state").reshape(lead + (14,)).clone()
-        step = int(step)
+        rs = dev_f32(state[2], (14,), "root_state").reshape(lead + (14,)).clone()
     fit_root = (FIT_ROOT_T if fit_root_t else 0) | (FIT_ROOT_ROT if fit_root_rot else 0)
     # (a one-joint model has no angle moments: their arguments only say that a state is given)
     out, rr_out, rt_out, loss, grad, grad_root = _pose_launch(
         model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach(), iters, lr,
         lr if lr_root_t is None else lr_root_t, lr if lr_root_rot is None else lr_root_rot, betas, eps, step,
         m if m.numel() else rs, v if v.numel() else rs, rs, want_iterate=True, want_grad=bool(return_grad))
-    if dof0 is not None and tuple(_as_tensor(dof0).shape) == tuple(d.shape) + (1,):
-        out = out.unsqueeze(-1)
-        grad = None if grad is None else grad.unsqueeze(-1)
     new_state = (m, v, rs, step + iters)
     if return_grad:
-        return PoseFitGrad(out, rr_out, rt_out, loss, new_state, grad, grad_root)
-    return PoseFit(out, rr_out, rt_out, loss, new_state)
+        return PoseFitGrad(as_dof0(out), rr_out, rt_out, loss, new_state, as_dof0(grad), grad_root)
+    return PoseFit(as_dof0(out), rr_out, rt_out, loss, new_state)
 
 
 def pose_loss(model, dof, root_rot, root_t, target_pos, weight=None, clip: bool = False, normalize_root: bool = True):

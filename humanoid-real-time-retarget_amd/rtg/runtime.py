@@ -68,8 +68,26 @@ def _host_i32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
 
 
-class Topology:
+class Handle:
+    """What the classes that own one handle of the C ABI share: ``_h``, the ``handle`` property, and its release
+    through the library's ``_destroy`` symbol when the object goes (unless the library went first, at shutdown)."""
+    _destroy = ""   # e.g. "rtg_topology_destroy"
+    _h = None
+
+    @property
+    def handle(self) -> ctypes.c_void_p:
+        return self._h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib._lib is not None:
+            getattr(_lib._lib, self._destroy)(h)
+            self._h = None
+
+
+class Topology(Handle):
     """A parent-indexed skeleton resident on the device (``rtg_topology_t``)."""
+    _destroy = "rtg_topology_destroy"
 
     def __init__(self, parent_indices, local_translation, tree_quat=None):
         require_gpu()
@@ -89,20 +107,11 @@ class Topology:
         self.parents = p
         self.local_translation = lt
 
-    @property
-    def handle(self) -> ctypes.c_void_p:
-        return self._h
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and _lib._lib is not None:
-            _lib._lib.rtg_topology_destroy(h)
-            self._h = None
-
-
-class DofModel:
+class DofModel(Handle):
     """A joint-angle forward model (``rtg_dof_model_t``, HuForwardModel hu_forward_model.py:13-33):
     a topology, one rotation axis per DOF (0/1/2) and optional DOF limits."""
+    _destroy = "rtg_dof_model_destroy"
 
     def __init__(self, topo: Topology, axis, lower=None, upper=None):
         require_gpu()
@@ -127,16 +136,6 @@ class DofModel:
         self.num_dofs = n
         self.has_limits = lo is not None
 
-    @property
-    def handle(self) -> ctypes.c_void_p:
-        return self._h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and _lib._lib is not None:
-            _lib._lib.rtg_dof_model_destroy(h)
-            self._h = None
-
 
 def retarget_tables(src_parents, tgt_parents, src_joint, tgt_joint) -> dict:
     """rtg_retarget_plan_tables (host only, no GPU needed): the tables of a retarget_to plan -- kept_src, kept_tgt,
@@ -157,9 +156,10 @@ def retarget_tables(src_parents, tgt_parents, src_joint, tgt_joint) -> dict:
     return {k: v[:(Jt if k == "src_of" else K)] for k, v in out.items()}
 
 
-class RetargetPlan:
+class RetargetPlan(Handle):
     """Everything of a ``SkeletonState.retarget_to`` call that does not depend on the frame (``rtg_retarget_plan_t``):
     the two trees, the joint mapping as index pairs, both t-poses, rotation_to_target_skeleton and the scale."""
+    _destroy = "rtg_retarget_plan_destroy"
 
     def __init__(self, src: Topology, tgt: Topology, src_joint, tgt_joint, src_tpose_local_rot, src_tpose_root_t,
                  tgt_tpose_local_rot, tgt_tpose_root_t, rotation_to_target, scale: float):
@@ -187,21 +187,12 @@ class RetargetPlan:
         self.num_source_joints, self.num_target_joints = src.num_joints, tgt.num_joints
         self.device = torch.device("cuda", torch.cuda.current_device())   # owns the constants (rtg.h)
 
-    @property
-    def handle(self) -> ctypes.c_void_p:
-        return self._h
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and _lib._lib is not None:
-            _lib._lib.rtg_retarget_plan_destroy(h)
-            self._h = None
-
-
-class MotionLib:
+class MotionLib(Handle):
     """The clip table of a motion library (``rtg_motion_lib_t``): per clip its first row in the packed arrays, its
     length in frames and its frame rate.  The arrays themselves stay with the caller (``ops.motion_sample``).  The
     table is validated on the host first: a bad one raises RtgError with the reason, GPU or not."""
+    _destroy = "rtg_motion_lib_destroy"
 
     def __init__(self, start, length, fps, total_frames: int):
         s = np.ascontiguousarray(np.asarray(start, dtype=np.int64).reshape(-1))
@@ -219,16 +210,6 @@ class MotionLib:
         self.total_frames = int(total_frames)
         self.start, self.length, self.fps = s, n, f
         self.device = torch.device("cuda", torch.cuda.current_device())   # owns the table (rtg.h)
-
-    @property
-    def handle(self) -> ctypes.c_void_p:
-        return self._h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and _lib._lib is not None:
-            _lib._lib.rtg_motion_lib_destroy(h)
-            self._h = None
 
 
 # Frames the reference raises on (rtg.h rtg_frame_error): the batched solve marks them -- every dof of the row NaN,
@@ -277,8 +258,9 @@ def layout_code(layout) -> int:
     return int(layout)
 
 
-class Solver:
+class Solver(Handle):
     """A retarget solver (``rtg_solver_t``) of one of the four reference kinds."""
+    _destroy = "rtg_solver_destroy"
 
     N_INPUTS = {k: len(v) for k, v in IN_TAILS.items()}
 
@@ -296,10 +278,6 @@ class Solver:
         self.kind = int(kind)
         self.precise_gripper = bool(precise_gripper)
         self.device = torch.device("cuda", torch.cuda.current_device())   # owns the angle table (rtg.h)
-
-    @property
-    def handle(self) -> ctypes.c_void_p:
-        return self._h
 
     def retarget(self, inputs: Sequence[torch.Tensor], want_local_rot=False, want_body_rot=False,
                  out_dof: Optional[torch.Tensor] = None, stream=None, layout="aos"):
@@ -339,9 +317,3 @@ class Solver:
         check(lib().rtg_retarget_f32(self._h, ins[0], ins[1], ins[2], ins[3], B, code, ptr(dof), ptr(lr), ptr(br),
                                      stream_handle(s)))
         return dof, lr, br
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and _lib._lib is not None:
-            _lib._lib.rtg_solver_destroy(h)
-            self._h = None
