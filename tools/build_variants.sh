@@ -3,27 +3,15 @@
 # usage: tools/build_variants.sh "name:-DKNOB=1 -DOTHER=0" ...   (time them with tools/variant_bench.sh)
 # The knobs are those of csrc/rtg_knobs.h.  A variant that was measured and rejected has no knob any more: its branch
 # was removed from the source (DESIGN.md keeps the numbers, git history the code), so build it from that commit.
-# NOSLP_TUS (environment; default as csrc/Makefile) lists the TUs built with -fno-slp-vectorize.
+# A variant is the product plus its defines: csrc/Makefile compiles every unit with the product's own flags and the
+# spec's -D... into variants/obj_<name>/.  NOSLP_TUS / IEEE_DIV_TUS (environment) override the Makefile's lists.
 # A variant built with a wrong-answer knob (RTG_EXP_STUB_SVD / _NO_TABLE / _HOT_INPUTS) reports it in
 # rtg_build_info(); rtg._lib refuses to load it unless RTG_ALLOW_MEASUREMENT_BUILD=1 (variant_bench.sh sets it).
 set -eu
-cd "$(dirname "$0")/../humanoid-real-time-retarget_amd/csrc"
-mkdir -p ../variants
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -I../../include"
-TUS="rtg_solve_fbp_aos rtg_solve_fbp_soa rtg_solve_fbp_small rtg_solve_other rtg_fk rtg_ops"
-SMALL_FLAGS="-mllvm -amdgpu-sched-strategy=max-ilp"   # rtg_solve_fbp_small and rtg_fk (csrc/Makefile)
-NOSLP_TUS="${NOSLP_TUS-rtg_solve_fbp_soa rtg_solve_fbp_aos}"
+csrc="$(dirname "$0")/../humanoid-real-time-retarget_amd/csrc"
 for spec in "$@"; do
   name="${spec%%:*}"; defs="${spec#*:}"
-  objs=""
-  for t in $TUS; do
-    extra=""; { [ "$t" = rtg_solve_fbp_small ] || [ "$t" = rtg_fk ]; } && extra="$SMALL_FLAGS"
-    case " $NOSLP_TUS " in *" $t "*) extra="$extra -fno-slp-vectorize";; esac
-    /opt/rocm/bin/hipcc $FLAGS $extra $defs -c $t.hip -o /tmp/v_$name.$t.o &
-    objs="$objs /tmp/v_$name.$t.o"
-  done
-  /opt/rocm/bin/hipcc $FLAGS $defs -x hip -c rtg_api.cpp -o /tmp/v_$name.api.o &
-  wait
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs /tmp/v_$name.api.o -o ../variants/$name.so
+  make -C "$csrc" -j"${JOBS:-8}" all OBJDIR="../variants/obj_$name" OUT="../variants/$name.so" DEFS="$defs" \
+    ${NOSLP_TUS+NOSLP_TUS="$NOSLP_TUS"} ${IEEE_DIV_TUS+IEEE_DIV_TUS="$IEEE_DIV_TUS"}
   echo "built variants/$name.so ($defs)"
 done
