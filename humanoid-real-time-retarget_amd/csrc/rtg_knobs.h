@@ -92,6 +92,13 @@
 #define RTG_FIT_FAST_DIV_TU RTG_FIT_FAST_DIV   // the same per translation unit: the Makefile's IEEE_DIV_TUS get 0 (rtg_ops, so
                                                // rtg_build_info reports 0 here: k_cal_joint_quat would lose a wave)
 #endif
+#ifndef RTG_FDIV_CORRECTIONS
+#define RTG_FDIV_CORRECTIONS 1   // fdiv_n_bare: residual corrections per quotient.  2 is the compiler's sequence; 1 gives
+                                 // the same bits on the whole window (proved by exhaustion, rtg_math.cuh; round 18)
+#endif
+#if RTG_FDIV_CORRECTIONS != 1 && RTG_FDIV_CORRECTIONS != 2
+#error "RTG_FDIV_CORRECTIONS: 1 or 2 (fewer gives wrong quotients)"
+#endif
 #ifndef RTG_DOF_NT_STORE
 #define RTG_DOF_NT_STORE 1   // A/B knob (same values): the solvers' DOF rows (whole 128-B lines) as non-temporal stores
                              // (headline 101.3 vs 104.5 us SoA, 114.4 vs 117.7 AoS; profiles/r05/nt/)

@@ -59,8 +59,12 @@ RTG_DEV float cr_sqrt(float x)
 // selects the unscaled value both times (it reads true on +-0 too, but 0 * 2^64 = 0 and 0 * 2^-32 = 0 with the
 // sign kept), so its five scaling instructions (compare, multiply, select; multiply, select) drop out and the rest
 // is the same sequence: the same bits as cr_sqrt.  Only for call sites whose comment says why the argument is in
-// that set; a negative or denormal argument needs cr_sqrt.  tools/check_fdiv.hip checks it against __builtin_sqrtf
-// on every such bit pattern.
+// that set; a positive argument below 2^-96 (denormals included) needs cr_sqrt.  A negative argument is a NaN either
+// way (x 2^64 stays negative, v_sqrt_f32 of a negative is the same quiet NaN, and the 2^-32 product keeps it; no
+// residual test moves a NaN), so a site whose argument is negative only where the result is a NaN in the reference
+// too may use it (the exp-map read-out, below: its mask turns that NaN into +0).  tools/check_fdiv.hip checks it
+// against __builtin_sqrtf on every bit pattern of the set, tools/check_fdiv1.hip [R] against cr_sqrt bit for bit,
+// NaN patterns included, on 1 - w w for every f32 w.
 RTG_DEV float cr_sqrt_nt(float x)
 {
 #if RTG_FIT_FAST_DIV_TU
@@ -760,6 +764,10 @@ RTG_DEV uint32_t ang_tab_build_word(uint32_t wd)
 }
 // quat_to_exp_map(q)[k] given only w = q.w and qk = q[k]: for |sin_theta| <= 1e-5 the reference's product is
 // 0 * (0 or 1) = +0 whatever k is, so the component index itself is not needed.
+// sin_theta's argument x = RN(1 - RN(w w)) is never tiny (round 18), so cr_sqrt_nt returns cr_sqrt's bits: for
+// |w| <= 1, RN(w w) is an f32 in [0, 1], so x is 0 (w = +-1) or at least 1 - (1 - 2^-24) = 2^-24; for |w| > 1,
+// RN(w w) >= 1 + 2^-23 and x is negative, which v_sqrt_f32 turns into the same NaN scaled or not; a NaN w is a NaN
+// either way.  tools/check_fdiv1.hip [R] compares the two and __builtin_sqrtf on every f32 w.
 RTG_DEV float exp_dof_tab(float w, float qk, const uint32_t *__restrict__ tab)
 {
     const uint32_t i = __float_as_uint(w) - kAngTabLo;
@@ -771,7 +779,7 @@ RTG_DEV float exp_dof_tab(float w, float qk, const uint32_t *__restrict__ tab)
     const uint32_t wd = ang_tab_word(i);
     const uint32_t word = tab[in ? wd : 0u];
 #endif
-    const float sin_theta = cr_sqrt(1.0f - w * w);
+    const float sin_theta = cr_sqrt_nt(1.0f - w * w);   // never tiny: see exp_dof_tab
     const bool mask = fabsf(sin_theta) > 1e-5f;
     const float P = exp_angle_estimate(w);
     const uint32_t code = in ? (word >> ((i - wd * kAngTabPer) * kAngTabBits)) & ((1u << kAngTabBits) - 1u) : 0u;
@@ -810,7 +818,7 @@ RTG_DEV ExpDof exp_dof_word_part(float w, uint32_t word)
 #if RTG_EXP_NO_TABLE
     word = 0x24924924u;
 #endif
-    const float sin_theta = cr_sqrt(1.0f - w * w);
+    const float sin_theta = cr_sqrt_nt(1.0f - w * w);   // never tiny: see exp_dof_tab
     const bool mask = fabsf(sin_theta) > 1e-5f;
     const float P = exp_angle_estimate(w);
     const uint32_t code = in ? (word >> ((i - wd * kAngTabPer) * kAngTabBits)) & ((1u << kAngTabBits) - 1u) : 0u;
@@ -821,7 +829,7 @@ RTG_DEV float exp_dof_finish(const ExpDof &e, float qk) { return e.mask ? e.angl
 __device__ __attribute__((noinline)) float exp_dof_exact(float w, float qk)
 {
     const float angle = normalize_angle(2.0f * cr_acos(w));
-    return angle * (qk / cr_sqrt(1.0f - w * w));
+    return angle * (qk / cr_sqrt_nt(1.0f - w * w));   // never tiny: see exp_dof_tab
 }
 RTG_DEV float qexp_component_tab(Q q, int k, const uint32_t *__restrict__ tab)
 {
@@ -958,8 +966,9 @@ RTG_DEV float la_sqrt_nt(float x) { return cr_sqrt_nt(x); }   // the argument ca
 //   q = as * y;  q = fma(fma(-bs, q, as), y, q);  q = v_div_fmas(fma(-bs, q, as), y, q);  v_div_fixup(q, b, a)
 // and it rebuilds all of it for every quotient, the reciprocal included, because v_div_scale reads the numerator.
 // Inside the window below nothing is scaled and nothing fixed up, so the sequence is plain f32 arithmetic whose
-// reciprocal part (three VALU, the one transcendental) depends on b alone: fdiv_n computes it once and runs the five
-// quotient instructions per numerator -- the same instructions on the same operands, hence the same bits.
+// reciprocal part (three VALU, the one transcendental) depends on b alone: fdiv_n computes it once and runs the
+// quotient instructions per numerator -- the same instructions on the same operands, hence the same bits (five of
+// them in the compiler's sequence; three since round 18, see fdiv_n_bare).
 //
 // The window: |b| and every |a_i| in [2^-47, 2^47] (kDivLo, kDivHi; la_lartg passes its own test, see there).  By
 // the ISA's definition v_div_scale_f32 returns its operand unscaled and VCC = 0 unless one of: an operand is 0 or
@@ -978,6 +987,18 @@ RTG_DEV bool fdiv_in_window(float x)
     const float ax = fabsf(x);
     return (ax >= kDivLo) & (ax <= kDivHi);
 }
+//
+// One residual correction (round 18, RTG_FDIV_CORRECTIONS = 1).  The compiler's second correction never moves the
+// quotient inside the window: after the first, q already is RN(a / b).  Proved by exhaustion, not by an error bound
+// (the bound is too close: the refined y is within 2^-24 or so of 1 / b, the corrected quotient within about 2^-47
+// of a / b relatively, and a quotient of two 24-bit mantissas can lie that close to a rounding boundary).  In the
+// window every operation of the sequence is ONE rounding of an exact expression in operands that scale with a and
+// b: y with 2^-k for b 2^k (v_rcp_f32 itself does, checked for every mantissa and every k of the window), t and q
+// with 2^(j-k) for a 2^j, the residual a - b t (exact inside the fma; zero or at least 2^-46 |a| / 4 >= 2^-96, so
+// never subnormal) with 2^j, and fma(-b, y, 1) not at all; RN is sign-symmetric.  So the sequence commutes with
+// powers of two and signs, as RN(a / b) does, and agreement on every mantissa pair a, b in [1, 2) -- 2^46 pairs,
+// tools/check_fdiv1.hip `exhaustive`, 0 mismatches, profiles/r18/check_fdiv1.log -- is agreement on the whole window.
+// tests/test_gpu_fdiv_one_correction.py runs the tool's sampled form.  2 rebuilds the compiler's sequence.
 // the bare sequence: a_i / b only where b and a_i are in the window (the caller tests that and redoes the rest)
 template <int N>
 RTG_DEV void fdiv_n_bare(const float (&a)[N], float b, float (&q)[N])
@@ -987,8 +1008,9 @@ RTG_DEV void fdiv_n_bare(const float (&a)[N], float b, float (&q)[N])
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         float t = a[i] * y;
-        t = __builtin_fmaf(__builtin_fmaf(-b, t, a[i]), y, t);
-        q[i] = __builtin_fmaf(__builtin_fmaf(-b, t, a[i]), y, t);
+#pragma unroll
+        for (int k = 0; k < RTG_FDIV_CORRECTIONS; ++k) t = __builtin_fmaf(__builtin_fmaf(-b, t, a[i]), y, t);
+        q[i] = t;
     }
 }
 template <int N>

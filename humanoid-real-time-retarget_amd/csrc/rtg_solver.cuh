@@ -261,11 +261,22 @@ RTG_DEV void store_dof_rows(float *__restrict__ dst, const float *src, int64_t n
     };
     const int nvec = nvals >> 2;
     typedef float f4v __attribute__((ext_vector_type(4)));
+    // (row, column) of a vector's first element, divided out once and carried: a step is 4 nthr elements, i.e. `dr`
+    // rows and `dc` columns (8 and 16 at 64 threads).  i = 4 v and 30 are even, so the column c is even and at most
+    // 28: elements 0 and 1 are in row rr, elements 2 and 3 move to the next row exactly when c = 28, where the LDS
+    // offset (rr + 1) 31 + (c + k - 30) is rr 31 + c + k + 1.
+    const int dr = (4 * nthr) / 30, dc = (4 * nthr) - dr * 30;
+    int rr = (4 * t) / 30, c = 4 * t - rr * 30;
     for (int v = t; v < nvec; v += nthr) {
         const int i = v << 2;
-        const f4v q = {at(i), at(i + 1), at(i + 2), at(i + 3)};
+        const float *p = src + rr * kDofStride + c;
+        const int wrap = c == 28 ? 1 : 0;
+        const f4v q = {p[0], p[1], p[2 + wrap], p[3 + wrap]};
         if (RTG_DOF_NT_STORE) __builtin_nontemporal_store(q, reinterpret_cast<f4v *>(dst + i));   // A/B knob
         else *reinterpret_cast<f4v *>(dst + i) = q;
+        c += dc;
+        rr += dr;
+        if (c >= 30) { c -= 30; ++rr; }
     }
     for (int i = (nvec << 2) + t; i < nvals; i += nthr) dst[i] = at(i);
 }
