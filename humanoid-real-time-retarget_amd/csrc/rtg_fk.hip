@@ -152,7 +152,7 @@ RTG_DEV void fk_group_tile(const TopoView &T, const float *__restrict__ local_ro
     root_preset(I.pos, J, nfr, r);
     wave_sync();
     group_compose<F>(T, I.rot, I.pos, I.sch, nfr, I.utab, [&](int, Q lq, const GEnt &e, int) {
-        if (STATE) lq = qmul_norm_tab(Q{e.qx, e.qy, e.qz, e.qw}, lq, I.utab);   // skeleton3d.py:412-418
+        if (STATE) lq = qmul_norm(Q{e.qx, e.qy, e.qz, e.qw}, lq, fk_tab(I.utab));   // skeleton3d.py:412-418
         return lq;
     });
     group_store<F>(I.rot, I.pos, nrec, g_rot + f0 * J * 4, g_pos + f0 * J * 3);
@@ -215,8 +215,8 @@ RTG_DEV void lrot_group_tile(const TopoView &T, const float *__restrict__ g_rot,
             const Q gj = q_of(rot[rec]);
             Q q = gj;   // root copied (kinematics.py:49)
             if (it.j > 0) {
-                q = qmul_norm_tab(qconj(q_of(rot[it.fr * J + I.par[it.j]])), gj, utab);
-                if (STATE) q = qmul_norm_tab(q_of(I.tqn[it.j]), q, utab);
+                q = qmul_norm(qconj(q_of(rot[it.fr * J + I.par[it.j]])), gj, fk_tab(utab));
+                if (STATE) q = qmul_norm(q_of(I.tqn[it.j]), q, fk_tab(utab));
             }
             st_out(dst + rec, v_of(q));
         }

@@ -52,11 +52,8 @@ RTG_DEV int tile_frames(int64_t B, int64_t f0) { return (int)((B - f0) < F ? (B 
 // the near-unit normalisation table (rtg_math.cuh) in the lane-group tiles' LDS, when any of them uses it
 constexpr bool kUnitTab = RTG_FK_UNIT_TAB || RTG_DOF_UNIT_TAB;
 constexpr size_t kUnitTabEnts = kUnitTab ? 2 * kUnitTabK + 1 : 0;
-RTG_DEV Q qmul_norm_tab(Q a, Q b, const UnitEnt *tab)
-{
-    if (!RTG_FK_UNIT_TAB) return qmul_norm(a, b);
-    return qnormalize_t(qmul(a, b), tab);
-}
+// the `tab` argument of the FK-side normalisations (qmul_norm, qnormalize): the table where RTG_FK_UNIT_TAB, else NoTab
+RTG_DEV auto fk_tab(const UnitEnt *utab) { return TabSel<RTG_FK_UNIT_TAB != 0>::get(utab); }
 
 // item i of a tile's (frame, joint) items, J per frame: i / J as ((i + 1/2) / J) truncated with rJ = item_rcp(J),
 // exact for i < 2^12, J <= 64
@@ -309,7 +306,7 @@ RTG_DEV void group_compose(const TopoView &T, f4v *rot, float *pos, const GEnt *
                 const float *tp = pos + 3 * (base + p);
                 const V t{tp[0], tp[1], tp[2]};
                 const V rv = qrotate(g, V{e.lx, e.ly, e.lz});
-                ng = qmul_norm_tab(g, lq, utab);
+                ng = qmul_norm(g, lq, fk_tab(utab));
                 nt = V{rv.x + t.x, rv.y + t.y, rv.z + t.z};
             }
             rot[base + j] = v_of(ng);

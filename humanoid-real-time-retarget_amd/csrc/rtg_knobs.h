@@ -70,7 +70,8 @@
 #endif
 // ---- used by rtg_math.cuh
 #ifndef RTG_EXP_MULR_NOBRANCH
-#define RTG_EXP_MULR_NOBRANCH 0   // measurement knob: mulr without its subnormal-quotient branch (wrong answers on rare inputs)
+#define RTG_EXP_MULR_NOBRANCH 0   // measurement knob: mulr_k / mulr_n without their subnormal-quotient branch (wrong
+                                  // answers on rare inputs)
 #endif
 #ifndef RTG_EXP_NO_TABLE
 #define RTG_EXP_NO_TABLE 0
@@ -91,6 +92,8 @@
 #ifndef RTG_FIT_FAST_DIV_TU
 #define RTG_FIT_FAST_DIV_TU RTG_FIT_FAST_DIV   // the same per translation unit: the Makefile's IEEE_DIV_TUS get 0 (rtg_ops, so
                                                // rtg_build_info reports 0 here: k_cal_joint_quat would lose a wave)
+                                               // la_lasv2 has one form for both settings since round 20: free in rtg_ops
+                                               // (no register, occupancy or time change, profiles/r20/leaf_math/)
 #endif
 #ifndef RTG_FDIV_CORRECTIONS
 #define RTG_FDIV_CORRECTIONS 1   // fdiv_n_bare: residual corrections per quotient.  2 is the compiler's sequence; 1 gives
@@ -161,7 +164,8 @@
 #endif
 #ifndef RTG_EXP_NO_RARE
 #define RTG_EXP_NO_RARE 0  // measurement knob, a bit mask: the rare-case branches of cr_sqrt (1) / cr_acos (2) /
-#endif                      // cr_sincos (4) / mulr (8) / sqrt_clamp_rcp (16) removed (wrong answers on rare inputs)
+#endif                      // cr_sincos (4) / mulr_k and mulr_n (8: the single-quotient mulr too, which is mulr_k<1>
+                            // since round 20) / sqrt_clamp_rcp (16) removed (wrong answers on rare inputs)
 #ifndef RTG_EXP_STUB_SVD
 #define RTG_EXP_STUB_SVD 0   // measurement knob (tools/build_variants.sh): R = identity-ish, wrong answers
 #endif

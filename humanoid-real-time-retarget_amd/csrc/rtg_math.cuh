@@ -131,12 +131,33 @@ RTG_DEV float acos_fast(float x, bool &ok)
     ok = (f32_round_safe(y, 1u << 12) & (ax < 1.0f)) | one;
     return one ? (neg ? 3.14159274f : 0.0f) : (float)y;
 }
+// ------------------------------------------------ N-way leaf math (round 6; the only form since round 20)
+// Each leaf function with a fast path and a rare exact path is ONE template over N elements: the fast paths of all N
+// run first and the whole group shares ONE rare-case branch, behind which each element that declined takes its exact
+// path.  A rare-case branch ends a basic block, and the scheduler does not move instructions across it: with a branch
+// per element two independent chains (the two arms of a frame) could not interleave, ~17 branches per arm map.  The
+// scalar name is the N = 1 call (arrays of one), so there is no second body to keep equal.
+template <int N>
+RTG_DEV void cr_acos_n(const float (&x)[N], float (&out)[N])
+{
+    bool ok[N], all = true;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        out[i] = acos_fast(x[i], ok[i]);
+        all &= ok[i];
+    }
+    if (!(RTG_EXP_NO_RARE & 2) && __builtin_expect(!all, 0)) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (!ok[i]) out[i] = acos_libm_call(x[i]);
+    }
+}
 RTG_DEV float cr_acos(float x)
 {
-    bool ok;
-    float r = acos_fast(x, ok);
-    if (!(RTG_EXP_NO_RARE & 2) && __builtin_expect(!ok, 0)) r = acos_libm_call(x);
-    return r;
+    const float a[1] = {x};
+    float r[1];
+    cr_acos_n<1>(a, r);
+    return r[0];
 }
 RTG_DEV float cr_sin(float x) { return (float)::sin((double)x); }
 RTG_DEV float cr_cos(float x) { return (float)::cos((double)x); }
@@ -147,15 +168,32 @@ struct SC { float s, c; };
 // the rare-case libm calls of cr_sincos, out of line (registers: see acos_libm_call)
 __device__ __attribute__((noinline)) float sin_libm_call(double x) { return (float)::sin(x); }
 __device__ __attribute__((noinline)) float cos_libm_call(double x) { return (float)::cos(x); }
+template <int N>
+RTG_DEV void cr_sincos_n(const double (&x)[N], SC (&out)[N])
+{
+    bool sok[N], cok[N], all = true;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const crm::SinCos r = crm::crm_sincos(x[i]);
+        out[i] = SC{r.s, r.c};
+        sok[i] = r.s_ok;
+        cok[i] = r.c_ok;
+        all &= r.s_ok & r.c_ok;
+    }
+    if (!(RTG_EXP_NO_RARE & 4) && __builtin_expect(!all, 0)) {   // one rare-case branch for every sine and cosine
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (!sok[i]) out[i].s = sin_libm_call(x[i]);
+            if (!cok[i]) out[i].c = cos_libm_call(x[i]);
+        }
+    }
+}
 RTG_DEV SC cr_sincos(double x)
 {
-    const crm::SinCos r = crm::crm_sincos(x);
-    SC out{r.s, r.c};
-    if (!(RTG_EXP_NO_RARE & 4) && __builtin_expect(!(r.s_ok & r.c_ok), 0)) {   // one rare-case branch for the pair
-        if (!r.s_ok) out.s = sin_libm_call(x);
-        if (!r.c_ok) out.c = cos_libm_call(x);
-    }
-    return out;
+    const double a[1] = {x};
+    SC r[1];
+    cr_sincos_n<1>(a, r);
+    return r[0];
 }
 // k float divisions by one denominator n: RN(a/n) == (float)((double)a * RN(1/(double)n))
 // for all f32 a, n.  (An f32 quotient is never within 2^-50 relative of an f32
@@ -182,18 +220,9 @@ RTG_DEV Rcp rcp64(float n)
 // 2^-50 (relative) of an f32 midpoint and the f64 product is within 2^-52.  A subnormal quotient (absolute
 // grid) takes the IEEE division; that branch is rare and divergent.  tools/check_fastmath.hip: 2^32 random
 // pairs + all special-value pairs, 0 mismatches.
-RTG_DEV float mulr(float a, const Rcp &r)
-{
-    const double p = (double)a * r.r;
-    float q = (float)p;
-#if !RTG_EXP_MULR_NOBRANCH   // measurement knob: no subnormal-quotient branch (wrong on rare exact subnormal midpoints)
-    if (__builtin_expect(__builtin_fabs(p) < 0x1p-126 && p != 0.0, 0)) q = a / r.n;
-#endif
-    return q;
-}
-// K quotients by one denominator behind ONE rare-case branch: each is (float)(a_i * 1/n) as in mulr, and if any
-// product is a nonzero subnormal, every quotient of the group takes the IEEE division -- identical to separate mulr
-// calls (for a normal quotient the IEEE division equals the product, by mulr's argument), one branch instead of K.
+// K quotients by one denominator behind ONE rare-case branch: each is (float)(a_i * 1/n), and if any product is a
+// nonzero subnormal, every quotient of the group takes the IEEE division -- identical to a branch per quotient (for a
+// normal quotient the IEEE division equals the product, by the argument above), one branch instead of K.
 template <int K>
 RTG_DEV void mulr_k(const float (&a)[K], const Rcp &r, float (&q)[K])
 {
@@ -204,33 +233,19 @@ RTG_DEV void mulr_k(const float (&a)[K], const Rcp &r, float (&q)[K])
         q[i] = (float)p;
         sub |= (__builtin_fabs(p) < 0x1p-126) & (p != 0.0);
     }
-#if !RTG_EXP_MULR_NOBRANCH
+#if !RTG_EXP_MULR_NOBRANCH   // measurement knob: no subnormal-quotient branch (wrong on rare exact subnormal midpoints)
     if (!(RTG_EXP_NO_RARE & 8) && __builtin_expect(sub, 0)) {
 #pragma unroll
         for (int i = 0; i < K; ++i) q[i] = a[i] / r.n;
     }
 #endif
 }
-// the subnormal-quotient path of mulr_q, out of line (registers: see acos_libm_call); returned by value
-__device__ __attribute__((noinline)) Q div_q_call(Q v, float n) { return Q{v.x / n, v.y / n, v.z / n, v.w / n}; }
-RTG_DEV Q mulr_q(Q v, const Rcp &r)
+RTG_DEV float mulr(float a, const Rcp &r)
 {
-    const double p[4] = {(double)v.x * r.r, (double)v.y * r.r, (double)v.z * r.r, (double)v.w * r.r};
-    bool sub = false;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) sub |= (__builtin_fabs(p[i]) < 0x1p-126) & (p[i] != 0.0);
-    Q q{(float)p[0], (float)p[1], (float)p[2], (float)p[3]};
-#if !RTG_EXP_MULR_NOBRANCH
-    if (!(RTG_EXP_NO_RARE & 8) && __builtin_expect(sub, 0)) q = div_q_call(v, r.n);   // = mulr_k<4>: every quotient by IEEE division
-#endif
-    return q;
-}
-RTG_DEV V mulr_v(V v, const Rcp &r)
-{
-    const float a[3] = {v.x, v.y, v.z};
-    float q[3];
-    mulr_k<3>(a, r, q);
-    return V{q[0], q[1], q[2]};
+    const float n[1] = {a};
+    float q[1];
+    mulr_k<1>(n, r, q);
+    return q[0];
 }
 RTG_DEV float clamp_lo(float v, float lo) { return v < lo ? lo : v; }          // NaN passes through
 // n = max(RN32(sqrt(s)), lo) and its reciprocal for mulr -- the normalisation step every quat_unit / quat_normalize /
@@ -269,15 +284,84 @@ RTG_DEV NormRcp sqrt_clamp_rcp_exact(float s, float lo)
     const float nc = clamp_lo(cr_sqrt(s), lo);
     return NormRcp{nc, rcp64(nc)};
 }
-RTG_DEV NormRcp sqrt_clamp_rcp(float s, float lo)
+template <int N>
+RTG_DEV void sqrt_clamp_rcp_n(const float (&s)[N], float lo, NormRcp (&out)[N])
 {
     // the fast path runs unconditionally (on s <= 0 / inf / NaN its values are discarded) and ONE rare-case branch
-    // takes the cr_sqrt + rcp64 path when s is not a positive finite number or n needs the clamp
-    bool ok;
-    NormRcp out = sqrt_clamp_rcp_fast(s, lo, ok);
-    if (!(RTG_EXP_NO_RARE & 16) && __builtin_expect(!ok, 0)) out = sqrt_clamp_rcp_exact(s, lo);
-    return out;
+    // takes the cr_sqrt + rcp64 path for each s that is not a positive finite number or whose n needs the clamp
+    bool ok[N], all = true;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        out[i] = sqrt_clamp_rcp_fast(s[i], lo, ok[i]);
+        all &= ok[i];
+    }
+    if (!(RTG_EXP_NO_RARE & 16) && __builtin_expect(!all, 0)) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (!ok[i]) out[i] = sqrt_clamp_rcp_exact(s[i], lo);
+    }
 }
+RTG_DEV NormRcp sqrt_clamp_rcp(float s, float lo)
+{
+    const float a[1] = {s};
+    NormRcp r[1];
+    sqrt_clamp_rcp_n<1>(a, lo, r);
+    return r[0];
+}
+// v_i * 1/n_i for N vectors of C components (V: 3, Q: 4), as mulr_k per vector: the products, and a vector with a
+// nonzero subnormal product takes IEEE divisions for all its components.  mulr_products_n is the unconditional part
+// (it returns whether any vector needs the divisions, `sub` says which); mulr_n adds the ONE rare-case branch.
+RTG_DEV void comps_of(V v, float (&a)[3]) { a[0] = v.x; a[1] = v.y; a[2] = v.z; }
+RTG_DEV void comps_of(Q v, float (&a)[4]) { a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w; }
+RTG_DEV V of_comps(const float (&a)[3]) { return V{a[0], a[1], a[2]}; }
+RTG_DEV Q of_comps(const float (&a)[4]) { return Q{a[0], a[1], a[2], a[3]}; }
+RTG_DEV V div_comps(V v, float n) { return V{v.x / n, v.y / n, v.z / n}; }
+// four divisions out of line (registers: see acos_libm_call); returned by value
+__device__ __attribute__((noinline)) Q div_q_call(Q v, float n) { return Q{v.x / n, v.y / n, v.z / n, v.w / n}; }
+RTG_DEV Q div_comps(Q v, float n) { return div_q_call(v, n); }
+template <typename T, int N>
+RTG_DEV bool mulr_products_n(const T (&v)[N], const NormRcp (&r)[N], T (&out)[N], bool (&sub)[N])
+{
+    constexpr int C = sizeof(T) / sizeof(float);
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        float a[C], q[C];
+        comps_of(v[i], a);
+        sub[i] = false;
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            const double p = (double)a[k] * r[i].r.r;
+            q[k] = (float)p;
+            sub[i] |= (__builtin_fabs(p) < 0x1p-126) & (p != 0.0);
+        }
+        out[i] = of_comps(q);
+        any |= sub[i];
+    }
+    return any;
+}
+template <typename T, int N>
+RTG_DEV void mulr_n(const T (&v)[N], const NormRcp (&r)[N], T (&out)[N])
+{
+    bool sub[N];
+    const bool any = mulr_products_n(v, r, out, sub);
+    if (!RTG_EXP_MULR_NOBRANCH && !(RTG_EXP_NO_RARE & 8) && __builtin_expect(any, 0)) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (sub[i]) out[i] = div_comps(v[i], r[i].r.n);
+    }
+}
+template <typename T>
+RTG_DEV T mulr_1(T v, const Rcp &r)
+{
+    const T a[1] = {v};
+    const NormRcp n[1] = {NormRcp{r.n, r}};
+    T q[1];
+    mulr_n(a, n, q);
+    return q[0];
+}
+RTG_DEV V mulr_v(V v, const Rcp &r) { return mulr_1(v, r); }
+RTG_DEV Q mulr_q(Q v, const Rcp &r) { return mulr_1(v, r); }
 
 RTG_DEV float tsign(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
 RTG_DEV float clamp_lohi(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -384,14 +468,111 @@ RTG_DEV Q qmul(Q a, Q b)   // :14-27, each component a left fold of four product
 RTG_DEV Q qconj(Q a) { return Q{-a.x, -a.y, -a.z, a.w}; }
 RTG_DEV Q qident() { return Q{0.0f, 0.0f, 0.0f, 1.0f}; }
 
-RTG_DEV Q qnormalize(Q q)  // quat_unit(quat_pos(q)) :30-56,92-98
+// ---- near-unit normalisation (round 6)
+// Most quaternions the kinematics normalise are products of unit quaternions, or {e_ax sin, cos} from a correctly
+// rounded pair: |q|^2 lands within a few f32 codes of 1.0f.  sqrt_clamp_rcp's (n, 1/n) for the 2K + 1 codes around
+// 1.0f are a table, filled by the kernel with sqrt_clamp_rcp_exact itself (unit_tab_fill: one code per lane, while
+// its loads are in flight), so a lookup returns exactly that function's values; a |q|^2 outside the table (a
+// non-unit input row, NaN) takes the ordinary path.
+constexpr int kUnitTabK = RTG_UNIT_TAB_K;
+struct UnitEnt {
+    double r;
+    float n, pad;
+};
+RTG_DEV void unit_tab_fill(UnitEnt *tab, int t)   // t: the filling thread's index in a wave (0 .. 63)
 {
-    const float f = 1.0f - 2.0f * (q.w < 0.0f ? 1.0f : 0.0f);
-    q.x = f * q.x; q.y = f * q.y; q.z = f * q.z; q.w = f * q.w;
-    const Rcp r = sqrt_clamp_rcp(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w, 1e-9f).r;
-    return mulr_q(q, r);
+    for (int e = t; e >= 0 && e <= 2 * kUnitTabK; e += 64) {
+        const NormRcp n = sqrt_clamp_rcp_exact(__int_as_float(0x3F800000 - kUnitTabK + e), 1e-9f);
+        tab[e] = UnitEnt{n.r.r, n.n, 0.0f};
+    }
 }
-RTG_DEV Q qmul_norm(Q a, Q b) { return qnormalize(qmul(a, b)); }
+RTG_DEV bool unit_tab_index(float s, uint32_t &idx)
+{
+    idx = (uint32_t)(__float_as_int(s) - (0x3F800000 - kUnitTabK));
+    const bool in = idx <= 2u * kUnitTabK;
+    idx = in ? idx : 0u;
+    return in;
+}
+// "Through the table or not" is the last argument `tab` of every function that normalises: NoTab (the default) is
+// the ordinary path, a const UnitEnt * the table.  TabSel picks between the two at compile time.
+struct NoTab {};
+template <bool ON> struct TabSel {   // a table pointer where ON, NoTab elsewhere
+    static RTG_DEV const UnitEnt *get(const UnitEnt *t) { return t; }
+};
+template <> struct TabSel<false> {
+    static RTG_DEV NoTab get(const UnitEnt *) { return NoTab{}; }
+};
+
+// quat_pos (:92-98) of N quaternions and their |q|^2 (left fold)
+template <int N>
+RTG_DEV void quat_pos_norm2_n(const Q (&q0)[N], Q (&q)[N], float (&s)[N])
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const float f = 1.0f - 2.0f * (q0[i].w < 0.0f ? 1.0f : 0.0f);
+        q[i] = Q{f * q0[i].x, f * q0[i].y, f * q0[i].z, f * q0[i].w};
+        s[i] = ((q[i].x * q[i].x + q[i].y * q[i].y) + q[i].z * q[i].z) + q[i].w * q[i].w;
+    }
+}
+template <int N>
+RTG_DEV void qnormalize_n(const Q (&q0)[N], Q (&out)[N], NoTab = NoTab{})  // quat_unit(quat_pos(q)) :30-56,92-98
+{
+    Q q[N];
+    float s[N];
+    quat_pos_norm2_n<N>(q0, q, s);
+    NormRcp r[N];
+    sqrt_clamp_rcp_n<N>(s, 1e-9f, r);
+    mulr_n(q, r, out);
+}
+RTG_DEV Q qnormalize(Q q, NoTab = NoTab{})
+{
+    const Q a[1] = {q};
+    Q o[1];
+    qnormalize_n<1>(a, o);
+    return o[0];
+}
+// through the table: the same sign flip, sum, products and subnormal test, element by element; the ones off the
+// table (or with a subnormal product) take the plain qnormalize, one rare-case branch per group
+template <int N>
+RTG_DEV void qnormalize_n(const Q (&q0)[N], Q (&out)[N], const UnitEnt *tab)
+{
+    Q q[N];
+    float s[N];
+    quat_pos_norm2_n<N>(q0, q, s);
+    NormRcp r[N];
+    bool in[N], sub[N], all = true;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        uint32_t idx;
+        in[i] = unit_tab_index(s[i], idx);
+        r[i] = NormRcp{tab[idx].n, Rcp{tab[idx].r, tab[idx].n}};
+    }
+    mulr_products_n(q, r, out, sub);
+#pragma unroll
+    for (int i = 0; i < N; ++i) all &= in[i] & !sub[i];
+    if (__builtin_expect(!all, 0)) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (!(in[i] & !sub[i])) out[i] = qnormalize(q0[i]);
+    }
+}
+RTG_DEV Q qnormalize(Q q, const UnitEnt *tab)
+{
+    const Q a[1] = {q};
+    Q o[1];
+    qnormalize_n<1>(a, o, tab);
+    return o[0];
+}
+template <typename Tab = NoTab>
+RTG_DEV Q qmul_norm(Q a, Q b, Tab tab = Tab{}) { return qnormalize(qmul(a, b), tab); }
+template <int N, typename Tab = NoTab>
+RTG_DEV void qmul_norm_n(const Q (&a)[N], const Q (&b)[N], Q (&out)[N], Tab tab = Tab{})
+{
+    Q p[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) p[i] = qmul(a[i], b[i]);
+    qnormalize_n<N>(p, out, tab);
+}
 RTG_DEV float qabs(Q q) { return cr_sqrt(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w); }   // :41-47
 RTG_DEV Q qunit(Q q)                                                                                 // :50-56
 {
@@ -427,218 +608,6 @@ RTG_DEV Q qfrom_angle_axis(float angle, V axis)  // :122-143
 }
 // quat_from_angle_axis about an exact unit axis (ex / ey / ez): the axis normalisation is the identity
 // (sqrt(1) = 1, +0 and 1 times RN(1/1) stay +0 and 1), so it is skipped -- the same bits.
-RTG_DEV Q qfrom_angle_unit_axis(float angle, V axis)
-{
-    const float theta = angle / 2.0f;
-    const SC t = cr_sincos((double)theta);
-    return qnormalize(Q{axis.x * t.s, axis.y * t.s, axis.z * t.s, t.c});
-}
-
-// ------------------------------------------------ N-way forms of the leaf math (round 6)
-// Element by element the same values as the scalar functions above (each element's fast path, and its exact path
-// where that one declines), but the fast paths of all N elements run first and the whole group shares ONE rare-case
-// branch.  A rare-case branch ends a basic block, and the scheduler does not move instructions across it: in the
-// scalar forms two independent chains (the two arms of a frame) could not interleave, ~17 branches per arm map.
-template <int N>
-RTG_DEV void sqrt_clamp_rcp_n(const float (&s)[N], float lo, NormRcp (&out)[N])
-{
-    bool ok[N], all = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        out[i] = sqrt_clamp_rcp_fast(s[i], lo, ok[i]);
-        all &= ok[i];
-    }
-    if (!(RTG_EXP_NO_RARE & 16) && __builtin_expect(!all, 0)) {
-#pragma unroll
-        for (int i = 0; i < N; ++i)
-            if (!ok[i]) out[i] = sqrt_clamp_rcp_exact(s[i], lo);
-    }
-}
-// v_i * 1/n_i for N vectors: mulr_v's products; a vector with a nonzero subnormal product takes IEEE divisions
-// (the same quotients: mulr_k)
-template <int N>
-RTG_DEV void mulr_v_n(const V (&v)[N], const NormRcp (&r)[N], V (&out)[N])
-{
-    bool sub[N], any = false;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const double p[3] = {(double)v[i].x * r[i].r.r, (double)v[i].y * r[i].r.r, (double)v[i].z * r[i].r.r};
-        out[i] = V{(float)p[0], (float)p[1], (float)p[2]};
-        sub[i] = false;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) sub[i] |= (__builtin_fabs(p[k]) < 0x1p-126) & (p[k] != 0.0);
-        any |= sub[i];
-    }
-#if !RTG_EXP_MULR_NOBRANCH
-    if (!(RTG_EXP_NO_RARE & 8) && __builtin_expect(any, 0)) {
-#pragma unroll
-        for (int i = 0; i < N; ++i)
-            if (sub[i]) out[i] = V{v[i].x / r[i].r.n, v[i].y / r[i].r.n, v[i].z / r[i].r.n};
-    }
-#endif
-}
-template <int N>
-RTG_DEV void mulr_q_n(const Q (&v)[N], const NormRcp (&r)[N], Q (&out)[N])
-{
-    bool sub[N], any = false;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const double p[4] = {(double)v[i].x * r[i].r.r, (double)v[i].y * r[i].r.r, (double)v[i].z * r[i].r.r,
-                             (double)v[i].w * r[i].r.r};
-        out[i] = Q{(float)p[0], (float)p[1], (float)p[2], (float)p[3]};
-        sub[i] = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) sub[i] |= (__builtin_fabs(p[k]) < 0x1p-126) & (p[k] != 0.0);
-        any |= sub[i];
-    }
-#if !RTG_EXP_MULR_NOBRANCH
-    if (!(RTG_EXP_NO_RARE & 8) && __builtin_expect(any, 0)) {
-#pragma unroll
-        for (int i = 0; i < N; ++i)
-            if (sub[i]) out[i] = div_q_call(v[i], r[i].r.n);
-    }
-#endif
-}
-template <int N>
-RTG_DEV void cr_acos_n(const float (&x)[N], float (&out)[N])
-{
-    bool ok[N], all = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        out[i] = acos_fast(x[i], ok[i]);
-        all &= ok[i];
-    }
-    if (!(RTG_EXP_NO_RARE & 2) && __builtin_expect(!all, 0)) {
-#pragma unroll
-        for (int i = 0; i < N; ++i)
-            if (!ok[i]) out[i] = acos_libm_call(x[i]);
-    }
-}
-template <int N>
-RTG_DEV void cr_sincos_n(const double (&x)[N], SC (&out)[N])
-{
-    bool sok[N], cok[N], all = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const crm::SinCos r = crm::crm_sincos(x[i]);
-        out[i] = SC{r.s, r.c};
-        sok[i] = r.s_ok;
-        cok[i] = r.c_ok;
-        all &= r.s_ok & r.c_ok;
-    }
-    if (!(RTG_EXP_NO_RARE & 4) && __builtin_expect(!all, 0)) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            if (!sok[i]) out[i].s = sin_libm_call(x[i]);
-            if (!cok[i]) out[i].c = cos_libm_call(x[i]);
-        }
-    }
-}
-template <int N>
-RTG_DEV void vunit_n(const V (&a)[N], V (&u)[N])   // vunit
-{
-    float s[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) s[i] = __builtin_fmaf(a[i].z, a[i].z, __builtin_fmaf(a[i].y, a[i].y, a[i].x * a[i].x));
-    NormRcp r[N];
-    sqrt_clamp_rcp_n<N>(s, 0.0f, r);
-    mulr_v_n<N>(a, r, u);
-}
-template <int N>
-RTG_DEV void qnormalize_n(const Q (&q0)[N], Q (&out)[N])   // qnormalize
-{
-    Q q[N];
-    float s[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float f = 1.0f - 2.0f * (q0[i].w < 0.0f ? 1.0f : 0.0f);
-        q[i] = Q{f * q0[i].x, f * q0[i].y, f * q0[i].z, f * q0[i].w};
-        s[i] = ((q[i].x * q[i].x + q[i].y * q[i].y) + q[i].z * q[i].z) + q[i].w * q[i].w;
-    }
-    NormRcp r[N];
-    sqrt_clamp_rcp_n<N>(s, 1e-9f, r);
-    mulr_q_n<N>(q, r, out);
-}
-// ------------------------------------------------ near-unit normalisation (round 6)
-// Most quaternions the kinematics normalise are products of unit quaternions, or {e_ax sin, cos} from a correctly
-// rounded pair: |q|^2 lands within a few f32 codes of 1.0f.  sqrt_clamp_rcp's (n, 1/n) for the 2K + 1 codes around
-// 1.0f are a table, filled by the kernel with sqrt_clamp_rcp_exact itself (unit_tab_fill: one code per lane, while
-// its loads are in flight), so a lookup returns exactly that function's values; a |q|^2 outside the table (a
-// non-unit input row, NaN) takes the ordinary path.
-constexpr int kUnitTabK = RTG_UNIT_TAB_K;
-struct UnitEnt {
-    double r;
-    float n, pad;
-};
-RTG_DEV void unit_tab_fill(UnitEnt *tab, int t)   // t: the filling thread's index in a wave (0 .. 63)
-{
-    for (int e = t; e >= 0 && e <= 2 * kUnitTabK; e += 64) {
-        const NormRcp n = sqrt_clamp_rcp_exact(__int_as_float(0x3F800000 - kUnitTabK + e), 1e-9f);
-        tab[e] = UnitEnt{n.r.r, n.n, 0.0f};
-    }
-}
-RTG_DEV bool unit_tab_index(float s, uint32_t &idx)
-{
-    idx = (uint32_t)(__float_as_int(s) - (0x3F800000 - kUnitTabK));
-    const bool in = idx <= 2u * kUnitTabK;
-    idx = in ? idx : 0u;
-    return in;
-}
-// qnormalize for N quaternions through the table: the same sign flip, sum, products and subnormal test, element by
-// element; the ones off the table (or with a subnormal product) take qnormalize, one rare-case branch per group
-template <int N>
-RTG_DEV void qnormalize_tab_n(const Q (&q0)[N], const UnitEnt *tab, Q (&out)[N])
-{
-    bool ok[N], all = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float f = 1.0f - 2.0f * (q0[i].w < 0.0f ? 1.0f : 0.0f);
-        const Q q{f * q0[i].x, f * q0[i].y, f * q0[i].z, f * q0[i].w};
-        uint32_t idx;
-        const bool in = unit_tab_index(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w, idx);
-        const double r = tab[idx].r;
-        const double p[4] = {(double)q.x * r, (double)q.y * r, (double)q.z * r, (double)q.w * r};
-        bool sub = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) sub |= (__builtin_fabs(p[k]) < 0x1p-126) & (p[k] != 0.0);
-        out[i] = Q{(float)p[0], (float)p[1], (float)p[2], (float)p[3]};
-        ok[i] = in & !sub;
-        all &= ok[i];
-    }
-    if (__builtin_expect(!all, 0)) {
-#pragma unroll
-        for (int i = 0; i < N; ++i)
-            if (!ok[i]) out[i] = qnormalize(q0[i]);
-    }
-}
-// compile-time choice of the normalisation: NoTab = qnormalize itself, a table pointer = the table
-struct NoTab {};
-template <int N>
-RTG_DEV void qnormalize_n_t(const Q (&q)[N], Q (&out)[N], NoTab) { qnormalize_n<N>(q, out); }
-template <int N>
-RTG_DEV void qnormalize_n_t(const Q (&q)[N], Q (&out)[N], const UnitEnt *tab) { qnormalize_tab_n<N>(q, tab, out); }
-RTG_DEV Q qnormalize_t(Q q, NoTab) { return qnormalize(q); }
-template <typename Tab>
-RTG_DEV Q qfrom_angle_unit_axis_t(float angle, V axis, Tab tab)   // qfrom_angle_unit_axis, normalised per Tab
-{
-    const float theta = angle / 2.0f;
-    const SC t = cr_sincos((double)theta);
-    return qnormalize_t(Q{axis.x * t.s, axis.y * t.s, axis.z * t.s, t.c}, tab);
-}
-template <bool ON> struct TabSel {   // a table pointer where ON, NoTab elsewhere
-    static RTG_DEV const UnitEnt *get(const UnitEnt *t) { return t; }
-};
-template <> struct TabSel<false> {
-    static RTG_DEV NoTab get(const UnitEnt *) { return NoTab{}; }
-};
-RTG_DEV Q qnormalize_t(Q q, const UnitEnt *tab)
-{
-    const Q a[1] = {q};
-    Q o[1];
-    qnormalize_tab_n<1>(a, tab, o);
-    return o[0];
-}
-
 template <int N, typename Tab = NoTab>
 RTG_DEV void qfrom_angle_unit_axis_n(const float (&angle)[N], const V (&axis)[N], Q (&out)[N], Tab tab = Tab{})
 {
@@ -650,7 +619,16 @@ RTG_DEV void qfrom_angle_unit_axis_n(const float (&angle)[N], const V (&axis)[N]
     Q q[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) q[i] = Q{axis[i].x * t[i].s, axis[i].y * t[i].s, axis[i].z * t[i].s, t[i].c};
-    qnormalize_n_t<N>(q, out, tab);
+    qnormalize_n<N>(q, out, tab);
+}
+template <typename Tab = NoTab>
+RTG_DEV Q qfrom_angle_unit_axis(float angle, V axis, Tab tab = Tab{})
+{
+    const float a[1] = {angle};
+    const V ax[1] = {axis};
+    Q q[1];
+    qfrom_angle_unit_axis_n<1>(a, ax, q, tab);
+    return q[0];
 }
 
 template <typename Tab = NoTab>
@@ -681,7 +659,7 @@ RTG_DEV Q qfrom_rotmat(const float m[9], Tab tab = Tab{})  // :146-193 (the four
         x *= tsign(m[6] + m[2]);
         y *= tsign(m[7] + m[5]);
     }
-    return qnormalize_t(Q{x, y, z, w}, tab);
+    return qnormalize(Q{x, y, z, w}, tab);
 }
 
 // quat_to_angle_axis + angle_axis_to_exp_map (:587-627), returns the 3 exp-map components
@@ -854,11 +832,16 @@ RTG_DEV V vdiv(V a, float s)
     return mulr_v(a, r);
 }
 RTG_DEV V vmul(V a, float s) { return V{s * a.x, s * a.y, s * a.z}; }
-// v / torch.linalg.norm(v): vdiv(v, lnorm3(v)) through one sqrt_clamp_rcp (lo = 0 clamps nothing)
-RTG_DEV V vunit(V a)
+// v / torch.linalg.norm(v): vdiv(v, lnorm3(v)) through one sqrt_clamp_rcp (lo = 0 clamps nothing), N vectors
+template <int N>
+RTG_DEV void vunit_n(const V (&a)[N], V (&u)[N])
 {
-    const Rcp r = sqrt_clamp_rcp(__builtin_fmaf(a.z, a.z, __builtin_fmaf(a.y, a.y, a.x * a.x)), 0.0f).r;
-    return mulr_v(a, r);
+    float s[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) s[i] = __builtin_fmaf(a[i].z, a[i].z, __builtin_fmaf(a[i].y, a[i].y, a[i].x * a[i].x));
+    NormRcp r[N];
+    sqrt_clamp_rcp_n<N>(s, 0.0f, r);
+    mulr_n(a, r, u);
 }
 
 RTG_DEV V proj_in_plane(V v, V n)  // :61-75
@@ -867,14 +850,14 @@ RTG_DEV V proj_in_plane(V v, V n)  // :61-75
     return vsub(v, vmul(n, dot3(v, n) / (nn * nn)));
 }
 
-RTG_DEV float radians_between(V v1, V v2, V n);   // :77-100 (after the N-way leaf math below)
-// radians_between with v1 and n exact unit axes (the arm maps' ex / ey / ez): their normalisation is the
-// identity (lnorm3 = sqrt(1) = 1, x * RN(1/1) = x), so only v2 is normalised -- the same bits, 2/3 fewer divides.
-RTG_DEV float radians_between_axes(V v1, V v2, V n)
+// the three unit vectors through one vunit_n (one rare-case branch instead of three)
+RTG_DEV float radians_between(V v1, V v2, V n)  // :77-100
 {
-    v2 = vunit(v2);
-    const float c = clamp_lohi(dot3(v1, v2), -1.0f, 1.0f);
-    return cr_acos(c) * tsign(dot3(n, cross3(v1, v2)));
+    const V in[3] = {v1, v2, n};
+    V u[3];
+    vunit_n<3>(in, u);
+    const float c = clamp_lohi(dot3(u[0], u[1]), -1.0f, 1.0f);
+    return cr_acos(c) * tsign(dot3(u[2], cross3(u[0], u[1])));
 }
 
 // ------------------------------------------------ the rest of the rotation3d / transform3d surface
@@ -1175,7 +1158,8 @@ RTG_DEV void la_lasv2(float f, float g, float h, float &ssmin, float &ssmax, flo
             }
         }
         if (gasmal) {
-#if RTG_FIT_FAST_DIV_TU
+            // one form for both settings of RTG_FIT_FAST_DIV_TU (round 20): with 0, fdiv_n is a plain division loop and
+            // la_sqrt_nt is cr_sqrt, so the grouped order below computes the values the ungrouped order did
             const float d = fa - ha, l = d == fa ? 1.0f : fdiv(d, fa);
             const float numf[2] = {gt, ht};
             float quof[2];
@@ -1203,24 +1187,6 @@ RTG_DEV void la_lasv2(float f, float g, float h, float &ssmin, float &ssmax, flo
             ssmin = quoa[0];
             clt = quoa[1];
             slt = quoa[2];
-#else   // the same operations in the order they had before the groups were formed
-            const float d = fa - ha, l = d == fa ? 1.0f : fdiv(d, fa);
-            const float m = fdiv(gt, ft), mm = m * m;
-            float t = 2.0f - l;
-            const float tt = t * t;
-            const float s = la_sqrt(tt + mm);
-            const float r = l == 0.0f ? fabsf(m) : la_sqrt(l * l + mm);
-            const float a = 0.5f * (s + r);
-            ssmin = fdiv(ha, a);
-            ssmax = fa * a;
-            if (mm == 0.0f) t = l == 0.0f ? la_sign(2.0f, ft) * la_sign(1.0f, gt) : fdiv(gt, la_sign(d, ft)) + fdiv(m, t);
-            else t = (fdiv(m, s + t) + fdiv(m, r + l)) * (1.0f + a);
-            const float l2 = la_sqrt(t * t + 4.0f);
-            crt = fdiv(2.0f, l2);
-            srt = fdiv(t, l2);
-            clt = fdiv(crt + srt * m, a);
-            slt = fdiv(fdiv(ht, ft) * srt, a);
-#endif
         }
     }
     if (swap) { csl = srt; snl = crt; csr = slt; snr = clt; }
@@ -2099,42 +2065,12 @@ RTG_DEV ArmZero elbow_zero(V v0)
     return ArmZero{radians_between(ex, v0p, ez), radians_between(v0p, v0, cross3(ez, v0p))};
 }
 
-// cal_shoulderPR (full_body_pos_retargeter.py:246-278)
-RTG_DEV void shoulder_pr(V v1, ArmZero z0, Q parent, Q &pitch, Q &roll)
-{
-    const V ex{1.f, 0.f, 0.f}, ey{0.f, 1.f, 0.f};
-    const V v1r = qrotate(qconj(parent), v1);
-    const V v1p = proj_in_plane(v1r, ey);
-    const float th1 = radians_between_axes(ex, v1p, ey);
-    pitch = qfrom_angle_unit_axis(th1 - z0.th0, ey);
-    const float ph1 = radians_between(v1p, v1r, cross3(v1p, ey));
-    roll = qfrom_angle_unit_axis(ph1 - z0.ph0, ex);
-}
-
-// cal_elbowP_and_shoulderY (full_body_pos_retargeter.py:220-243)
-RTG_DEV void elbow_py(V v1, ArmZero z0, Q parent, Q &yaw, Q &elbow)
-{
-    const V ex{1.f, 0.f, 0.f}, ey{0.f, 1.f, 0.f}, ez{0.f, 0.f, 1.f};
-    const V v1r = qrotate(qconj(parent), v1);
-    const V v1p = proj_in_plane(v1r, ez);
-    const float th1 = radians_between_axes(ex, v1p, ez);
-    yaw = qfrom_angle_unit_axis(th1 - z0.th0, ez);
-    const float ph1 = radians_between(v1p, v1r, cross3(ez, v1p));
-    elbow = qfrom_angle_unit_axis(ph1 - z0.ph0, ey);
-}
-
-// the three unit vectors through one vunit_n (one rare-case branch instead of three; the same values)
-RTG_DEV float radians_between(V v1, V v2, V n)  // :77-100
-{
-    const V in[3] = {v1, v2, n};
-    V u[3];
-    vunit_n<3>(in, u);
-    const float c = clamp_lohi(dot3(u[0], u[1]), -1.0f, 1.0f);
-    return cr_acos(c) * tsign(dot3(u[2], cross3(u[0], u[1])));
-}
-
-// shoulder_pr (SHOULDER) / elbow_py of NA arms at once, on the N-way leaf math: per arm the same operations on the
-// same operands as the scalar forms above (vunit(v1p) serves both angles, as CSE made it there), so the same bits
+// cal_shoulderPR (SHOULDER; full_body_pos_retargeter.py:246-278: pitch about ey, then roll about ex) /
+// cal_elbowP_and_shoulderY (:220-243: yaw about ez, then the elbow about ey) of NA arms at once.  Per arm:
+//   v1r = v1 in the parent's frame, v1p = its projection into the plane of the first angle (normal pn);
+//   first angle = radians_between(ex, v1p, pn) - th0: ex and pn are exact unit axes, whose normalisation is the
+//     identity (lnorm3 = sqrt(1) = 1, x * RN(1/1) = x), so only v1p is normalised -- the same bits, 2/3 fewer divides;
+//   second angle = radians_between(v1p, v1r, n) - ph0, with the unit v1p of the first angle.
 template <bool SHOULDER, int NA, typename Tab = NoTab>
 RTG_DEV void arm_pair_n(const V (&v1)[NA], const ArmZero (&z0)[NA], const Q (&parent)[NA], Q (&first)[NA],
                         Q (&second)[NA], Tab tab = Tab{})
@@ -2155,7 +2091,7 @@ RTG_DEV void arm_pair_n(const V (&v1)[NA], const ArmZero (&z0)[NA], const Q (&pa
     float c[2 * NA];
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
-        c[2 * a] = clamp_lohi(dot3(ex, u[3 * a]), -1.0f, 1.0f);                  // radians_between_axes(ex, v1p, pn)
+        c[2 * a] = clamp_lohi(dot3(ex, u[3 * a]), -1.0f, 1.0f);                  // radians_between(ex, v1p, pn)
         c[2 * a + 1] = clamp_lohi(dot3(u[3 * a], u[3 * a + 1]), -1.0f, 1.0f);    // radians_between(v1p, v1r, n)
     }
     float ac[2 * NA];
@@ -2176,6 +2112,27 @@ RTG_DEV void arm_pair_n(const V (&v1)[NA], const ArmZero (&z0)[NA], const Q (&pa
         first[a] = q[2 * a];
         second[a] = q[2 * a + 1];
     }
+}
+template <bool SHOULDER, typename Tab>
+RTG_DEV void arm_pair_1(V v1, ArmZero z0, Q parent, Q &first, Q &second, Tab tab)
+{
+    const V v[1] = {v1};
+    const ArmZero z[1] = {z0};
+    const Q par[1] = {parent};
+    Q a[1], b[1];
+    arm_pair_n<SHOULDER, 1>(v, z, par, a, b, tab);
+    first = a[0];
+    second = b[0];
+}
+template <typename Tab = NoTab>
+RTG_DEV void shoulder_pr(V v1, ArmZero z0, Q parent, Q &pitch, Q &roll, Tab tab = Tab{})
+{
+    arm_pair_1<true>(v1, z0, parent, pitch, roll, tab);
+}
+template <typename Tab = NoTab>
+RTG_DEV void elbow_py(V v1, ArmZero z0, Q parent, Q &yaw, Q &elbow, Tab tab = Tab{})
+{
+    arm_pair_1<false>(v1, z0, parent, yaw, elbow, tab);
 }
 
 // torch sum of 5 elements (cascade reduce order, measured) / 5

@@ -57,11 +57,6 @@ struct MsImages {
 RTG_DEV float ms_nan() { return __int_as_float(0x7FC00000); }
 // torch's (1 - b) * a + b * c: each operation rounds on its own
 RTG_DEV float ms_blend(float a, float c, float b) { return ((1.0f - b) * a) + (b * c); }
-RTG_DEV Q ms_norm(Q q, const UnitEnt *tab)
-{
-    if (!RTG_FK_UNIT_TAB) return qnormalize(q);
-    return qnormalize_t(q, tab);
-}
 
 template <int F, bool NORM, bool GLOBAL, bool STATE>
 __global__ __launch_bounds__(64, 4) void k_motion_sample(TopoView T, MotionLibView L, MotionSampleArgs A)
@@ -117,7 +112,7 @@ __global__ __launch_bounds__(64, 4) void k_motion_sample(TopoView T, MotionLibVi
             if (k0 + w >= G::NR) continue;
             const int rec = (k0 + w) * 64 + lane;
             Q q = qslerp(q_of(a[w]), q_of(c[w]), b[w]);
-            if (NORM) q = ms_norm(q, I.utab);
+            if (NORM) q = qnormalize(q, fk_tab(I.utab));
             const f4v v = ok[w] ? v_of(q) : nan4;
             if (rec < nrec) {
                 st_out(dst + rec, v);
@@ -167,7 +162,7 @@ __global__ __launch_bounds__(64, 4) void k_motion_sample(TopoView T, MotionLibVi
     if (GLOBAL) {
         wave_sync();
         group_compose<F>(T, I.rot, I.pos, I.sch, nfr, I.utab, [&](int, Q lq, const GEnt &e, int) {
-            if (STATE) lq = qmul_norm_tab(Q{e.qx, e.qy, e.qz, e.qw}, lq, I.utab);   // skeleton3d.py:412-418
+            if (STATE) lq = qmul_norm(Q{e.qx, e.qy, e.qz, e.qw}, lq, fk_tab(I.utab));   // skeleton3d.py:412-418
             return lq;
         });
         if (any_invalid) {   // wave-uniform: an invalid query's global rows are the quiet NaN too, whatever FK made of them

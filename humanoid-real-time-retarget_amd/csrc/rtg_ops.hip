@@ -628,7 +628,7 @@ __global__ __launch_bounds__(256) void k_velocity_tile(const float *__restrict__
 #pragma unroll
                 for (int k = 0; k < NB; ++k) prod[k] = qmul(ca[k], qconj(cb[k]));
 #if RTG_VEL_UNIT_TAB
-                qnormalize_tab_n<NB>(prod, utab, dn);
+                qnormalize_n<NB>(prod, dn, utab);
 #else
                 qnormalize_n<NB>(prod, dn);
 #endif
@@ -646,13 +646,13 @@ __global__ __launch_bounds__(256) void k_velocity_tile(const float *__restrict__
                 NormRcp nr[NB], rdt[NB];
                 sqrt_clamp_rcp_n<NB>(s3, 1e-9f, nr);
                 V ax[NB], prod3[NB], av[NB];
-                mulr_v_n<NB>(xyz, nr, ax);
+                mulr_n(xyz, nr, ax);
 #pragma unroll
                 for (int k = 0; k < NB; ++k) {
                     prod3[k] = V{ax[k].x * ang[k], ax[k].y * ang[k], ax[k].z * ang[k]};
                     rdt[k] = NormRcp{dt, Rcp{vt.rdt, dt}};
                 }
-                mulr_v_n<NB>(prod3, rdt, av);
+                mulr_n(prod3, rdt, av);
 #pragma unroll
                 for (int k = 0; k < NB; ++k)
                     if (e0 + 256u * k < n) {

@@ -32,12 +32,6 @@
 
 namespace rtg {
 
-RTG_DEV Q qnorm_tab(Q q, const UnitEnt *tab)
-{
-    if (!RTG_FK_UNIT_TAB) return qnormalize(q);
-    return qnormalize_t(q, tab);
-}
-
 // a list schedule's steps on the rotations alone: joint j's row becomes qmul_norm(parent's global row,
 // qmul_norm(tree quaternion, row)) (:416-422); the root's row is its global rotation already and has no entry
 template <int F>
@@ -52,8 +46,8 @@ RTG_DEV void rot_compose(f4v *img, int stride, const GEnt *sch, int steps, int n
         const GEnt e = sch[s * G::L + sub];
         const int j = e.code & 0xFF, p = (e.code >> 8) & 0xFF;
         if (live && j != 0xFF) {
-            const Q lq = qmul_norm_tab(Q{e.qx, e.qy, e.qz, e.qw}, q_of(img[base + j]), utab);
-            img[base + j] = v_of(qmul_norm_tab(q_of(img[base + p]), lq, utab));
+            const Q lq = qmul_norm(Q{e.qx, e.qy, e.qz, e.qw}, q_of(img[base + j]), fk_tab(utab));
+            img[base + j] = v_of(qmul_norm(q_of(img[base + p]), lq, fk_tab(utab)));
         }
         wave_sync();   // this step's rows before the next step's parent reads (other lanes)
     }
@@ -120,7 +114,7 @@ __global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const flo
     const float rK = item_rcp(K);
     for (int i = lane; i < nk; i += 64) {   // stage 2
         const Item it = item_split(i, rK, K);
-        red[i] = v_of(qnorm_tab(q_of(img[it.fr * Js + kept[it.j]]), utab));
+        red[i] = v_of(qnormalize(q_of(img[it.fr * Js + kept[it.j]]), fk_tab(utab)));
     }
     wave_sync();   // the image is dead from here: rows [F K] of it take stages 3-6
     const Q cid = qnormalize(qconj(qident()));   // S_red's tree quaternions are identities (:259, :477-481)
@@ -130,12 +124,12 @@ __global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const flo
         const Q g = q_of(red[fr * K + ks]);
         Q l = g;   // S_red's root copied (:470)
         if (ks > 0) {
-            l = qmul_norm_tab(qconj(q_of(red[fr * K + spar[ks]])), g, utab);
-            l = qmul_norm_tab(cid, l, utab);
+            l = qmul_norm(qconj(q_of(red[fr * K + spar[ks]])), g, fk_tab(utab));
+            l = qmul_norm(cid, l, fk_tab(utab));
         }
-        l = qnorm_tab(l, utab);                          // :735-740
-        if (k == 0) l = qmul_norm_tab(P.R, l, utab);     // :849
-        img[i] = v_of(qnorm_tab(l, utab));               // :850-855
+        l = qnormalize(l, fk_tab(utab));                      // :735-740
+        if (k == 0) l = qmul_norm(P.R, l, fk_tab(utab));      // :849
+        img[i] = v_of(qnormalize(l, fk_tab(utab)));           // :850-855
     }
     const V tr = qrotate(P.R, root);                     // :853
     wave_sync();
@@ -155,9 +149,9 @@ __global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const flo
 
     for (int i = lane; i < nk; i += 64) {   // stage 7, and stage 8's normalisation (the same for every j it serves)
         const int k = item_split(i, rK, K).j;
-        const Q d = qmul_norm_tab(q_of(img[i]), q_of(cg[k]), utab);
-        const Q n = qmul_norm_tab(d, q_of(tg[k]), utab);
-        red[i] = v_of(qnorm_tab(n, utab));
+        const Q d = qmul_norm(q_of(img[i]), q_of(cg[k]), fk_tab(utab));
+        const Q n = qmul_norm(d, q_of(tg[k]), fk_tab(utab));
+        red[i] = v_of(qnormalize(n, fk_tab(utab)));
     }
     wave_sync();
 
@@ -179,10 +173,10 @@ __global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const flo
             const Q o = q_of(red[fr * K + src_of[j]]);
             Q q = o;   // T's root copied (:470)
             if (j > 0) {
-                q = qmul_norm_tab(qconj(q_of(red[fr * K + src_of[tpar[j]]])), o, utab);
-                q = qmul_norm_tab(q_of(ttqn[j]), q, utab);
+                q = qmul_norm(qconj(q_of(red[fr * K + src_of[tpar[j]]])), o, fk_tab(utab));
+                q = qmul_norm(q_of(ttqn[j]), q, fk_tab(utab));
             }
-            st_out(dst + rec, v_of(qnorm_tab(q, utab)));   // :645-650
+            st_out(dst + rec, v_of(qnormalize(q, fk_tab(utab))));   // :645-650
         }
     }
 }

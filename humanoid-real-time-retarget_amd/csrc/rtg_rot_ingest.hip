@@ -23,21 +23,6 @@
 
 namespace rtg {
 
-// qmul_norm_tab for N pairs: one rare-case branch for the group
-template <int N>
-RTG_DEV void qmul_norm_tab_n(const Q (&a)[N], const Q (&b)[N], const UnitEnt *tab, Q (&out)[N])
-{
-    Q p[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) p[i] = qmul(a[i], b[i]);
-    if (!RTG_FK_UNIT_TAB) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) out[i] = qnormalize(p[i]);
-    } else {
-        qnormalize_tab_n<N>(p, tab, out);
-    }
-}
-
 // the tile's items of the first N slots (item u NT + tid of slot u), as one N-way group: one rare-case branch each product
 struct RotItems {
     const f4v *img, *post;
@@ -60,8 +45,8 @@ RTG_DEV void rot_items(const RotItems &P, int tid, Q (&r)[4])
         b[u] = P.pre;
         m[u] = q_of(P.post[it.j]);
     }
-    qmul_norm_tab_n<N>(a, b, P.utab, o);
-    qmul_norm_tab_n<N>(o, m, P.utab, a);
+    qmul_norm_n<N>(a, b, o, fk_tab(P.utab));
+    qmul_norm_n<N>(o, m, a, fk_tab(P.utab));
 #pragma unroll
     for (int u = 0; u < N; ++u) r[u] = a[u];
 }

@@ -152,32 +152,14 @@ RTG_DEV void report_device_error(uint32_t *err, uint32_t code)
 
 // one arm: shoulder pitch/roll then shoulder yaw / elbow pitch (full_body_pos_retargeter.py:75-93);
 // returns quat_mul_four of the four link rotations (the wrist parent chain, :128-136)
-// (round 6: on arm_pair_n, the two angles of each map in one instruction stream with shared rare-case branches; the
-// same values as shoulder_pr / elbow_py)
 template <int L0, typename Tab = NoTab>
 RTG_DEV Q solve_arm(const Emit &E, V upper, V fore, ArmZero zs, ArmZero ze, Q parent, Tab tab = Tab{})
 {
     Q p, r, y, e;
-    {
-        const V v[1] = {upper};
-        const ArmZero z[1] = {zs};
-        const Q par[1] = {parent};
-        Q a[1], b[1];
-        arm_pair_n<true, 1>(v, z, par, a, b, tab);
-        p = a[0];
-        r = b[0];
-    }
+    shoulder_pr(upper, zs, parent, p, r, tab);
     E.link<L0>(p);
     E.link<L0 + 1>(r);
-    {
-        const V v[1] = {fore};
-        const ArmZero z[1] = {ze};
-        const Q par[1] = {qmul(qmul(parent, p), r)};
-        Q a[1], b[1];
-        arm_pair_n<false, 1>(v, z, par, a, b, tab);
-        y = a[0];
-        e = b[0];
-    }
+    elbow_py(fore, ze, qmul(qmul(parent, p), r), y, e, tab);
     E.link<L0 + 2>(y);
     E.link<L0 + 3>(e);
     return qmul(qmul(qmul(p, r), y), e);
@@ -396,7 +378,7 @@ RTG_DEV bool fbp_side_after_arm(const SolverConsts &C, const TipPts &tp, Q R10, 
                                 float *__restrict__ brow, Tab tab = Tab{})
 {
     constexpr int E0 = SIDE ? 25 : 16, D0 = SIDE ? 27 : 18;
-    const bool refused = emit_euler_xyz<E0>(E, qnormalize_t(qmul(qconj(qnormalize_t(qmul(R10, chain), tab)), W), tab));
+    const bool refused = emit_euler_xyz<E0>(E, qmul_norm(qconj(qmul_norm(R10, chain, tab)), W, tab));
     fbp_gripper<PRECISE>(C, hand_x_mean(qconj(W), tp.h0, tp.t), E.row + D0);
     if (brow) fbp_body_rows<SIDE>(brow, R10, W);
     return refused;
@@ -430,7 +412,7 @@ RTG_DEV bool solve_full_body_rot_side(const SolverConsts &C, const View &q, cons
     const Q chain = solve_arm<L0>(E, vsub(bel, b.p3(SH)), vsub(b.p3(WR), bel), SIDE ? C.rsh : C.lsh,
                                   SIDE ? C.rel : C.lel, par, tab);
     const Q w = q.q4(WR);
-    const bool refused = emit_euler_xyz<E0>(E, qnormalize_t(qmul(qconj(qnormalize_t(qmul(par, chain), tab)), w), tab));
+    const bool refused = emit_euler_xyz<E0>(E, qmul_norm(qconj(qmul_norm(par, chain, tab)), w, tab));
     constexpr int tips[5] = {3, 7, 11, 15, 19};   // :145-177 rotates by the wrist quaternion itself
     const bool closed = hand_x_mean(w, H, tips) / C.orig < 0.7f;
     E.row[D0] = closed ? 0.0f : 0.044f;
@@ -442,17 +424,17 @@ RTG_DEV bool solve_full_body_rot_side(const SolverConsts &C, const View &q, cons
 template <int SIDE, typename View, typename Tab = NoTab>
 RTG_DEV bool solve_body_rot_side(const SolverConsts &C, const View &g, const Emit &E, Tab tab = Tab{})
 {
-    auto local = [&](int j, int p) { return qnormalize_t(qmul(qconj(g.q4(p)), g.q4(j)), tab); };
+    auto local = [&](int j, int p) { return qmul_norm(qconj(g.q4(p)), g.q4(j), tab); };
     constexpr int SH = SIDE ? 14 : 18, EL = SIDE ? 15 : 19, D0 = SIDE ? 27 : 18;
     Q s3[3], e3[3];
     bool refused = quat_in_xyz_axis(local(SH, C.par[SIDE ? 1 : 0]), 1, 0, 2, false, s3);   // 'YXZ'
     refused |= quat_in_xyz_axis(local(EL, C.par[SIDE ? 3 : 2]), 2, 1, 0, false, e3);       // 'ZYX'
     if (SIDE) {
-        E.link<21>(s3[0]); E.link<22>(s3[1]); E.link<23>(qnormalize_t(qmul(e3[0], s3[2]), tab));
+        E.link<21>(s3[0]); E.link<22>(s3[1]); E.link<23>(qmul_norm(e3[0], s3[2], tab));
         E.link<24>(e3[1]); E.link<25>(e3[2]);
         E.identity<26>(); E.identity<27>();
     } else {
-        E.link<12>(s3[0]); E.link<13>(s3[1]); E.link<14>(qnormalize_t(qmul(e3[0], s3[2]), tab));
+        E.link<12>(s3[0]); E.link<13>(s3[1]); E.link<14>(qmul_norm(e3[0], s3[2], tab));
         E.link<15>(e3[1]); E.link<16>(e3[2]);
         E.identity<17>(); E.identity<18>();
     }
@@ -939,7 +921,7 @@ __global__ __launch_bounds__(320) void k_fbp_latency5(SolverConsts C, const floa
 //   * the scipy Euler split of each wrist: its three atan2 on lanes 0-2, then one elementary quaternion per lane;
 //   * the exp-map DOF read-out: one link per lane.
 // Every value is computed by the same device functions on the same operands as in the batched kernels (the pitch
-// angle as radians_between of the exact unit axes, which is radians_between_axes bit for bit), so the bits are the
+// angle as radians_between of the exact unit axes, which arm_pair_n's unnormalised-axes form equals bit for bit), so the bits are the
 // batched kernels' (test_frame_server_matches_batched, test_solver_batch_invariance).  Partial results cross
 // lanes by v_readlane.
 // ----------------------------------------------------------------------------
@@ -997,7 +979,7 @@ RTG_DEV void arm_pair_lanes(V v1, ArmZero z0, Q parent, Q &first, Q &second, con
         const float ang = radians_between(a, b, n);
         hook(2);
         const V ax = l0 ? pn : (SHOULDER ? ex : ey);
-        q = qfrom_angle_unit_axis_t(ang - (l0 ? z0.th0 : z0.ph0), ax, tab);
+        q = qfrom_angle_unit_axis(ang - (l0 ? z0.th0 : z0.ph0), ax, tab);
         hook(3);
     }
     first = gbc<G, 0>(q);
@@ -1209,7 +1191,7 @@ RTG_DEV uint32_t fbp_frame1_tile(const SolverConsts &C, const float *rows, float
                 else fbp_body_rows<0>(body_rot, R10, W, const_rows);
             }
         }
-        const Q loc = qnormalize_t(qmul(qconj(qnormalize_t(qmul(R10, chain), tab)), W), tab);
+        const Q loc = qmul_norm(qconj(qmul_norm(R10, chain, tab)), W, tab);
         const bool refused = emit_euler_xyz_lanes_rt(E, side ? 25 : 16, loc);
         st |= refused ? (side ? kStRightEuler : kStLeftEuler) : 0u;
         TS(7);
