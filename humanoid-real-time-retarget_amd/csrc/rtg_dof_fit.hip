@@ -21,9 +21,23 @@
 // normalisation's adjoint (g - (g.G_0) G_0) / |q| and takes the 3 + 4 Adam steps, renormalising q after its step.
 // The fit_root mask is a launch argument (wave-uniform branches in that one lane's work).
 //
+// k_dof_fit_orient_group (rtg_dof_fit_orient_f32) is the root tile with orientation targets for up to
+// RTG_FIT_MAX_ROT_LINKS chosen links (ORI): L_f gains sum_k rot_weight[k] 4 (1 - c_k^2), c_k = <G_j, Rh_fk> for
+// j = rot_joint[k], G_j the global rotation the forward sweep holds and Rh_fk the target row over max(|row|, 1e-9) (no
+// sign flip; normalised once, on its way into LDS).  4 (1 - c^2) = (2 sin(theta / 2))^2 of the angle theta between
+// the two rotations: even in either quaternion, theta^2 to second order, and stationary at theta = pi as well as at 0
+// (a link exactly half a turn off gets no pull from this term).  Its adjoint dL/dG_j = -8 rot_weight[k] c_k Rh_fk is
+// the joint's own upstream rotation adjoint: child_pull's first argument at that joint's reverse step (the root's in
+// fit_root_reverse), formed from G_j before the row takes the joint's contribution to its parent.  Everything behind
+// it -- the normalisation's tangent projection, angle_grad, the Adam steps -- is the position fit's.  rot_joint comes
+// in the launch arguments (checked on the host), so a joint's {slot, rot_weight} entry is filled from them.  The loss
+// adds the links after the positions, in k order, by the lane that writes the frame's loss.
+//
 // LDS images of a tile: FitImages below (every image starts 16-byte aligned).
 // 33-link Hu, F = 16 (10 steps): 29.3 KiB; a 64-joint chain, F = 8, 64 steps: 43.9 KiB (the largest: gsteps <= J).
 // With the root image and the two more step sizes per Adam step: 31.1 KiB (still 5 tiles per CU) and 45.1 KiB.
+// ORI adds 8 J + 16 F K bytes, sized by the launch's own K: Hu keeps 5 tiles per CU up to K = 2 and has 4 from there
+// (K = 8: 34,160 B of the 40,960 a tile may have there); the 64-joint chain with K = 8: 47,680 B.
 //
 // Arithmetic: as in rtg_fk_grad.hip no operation order is owed to a reference (explicit fmaf, the device sincosf,
 // -ffp-contract=fast); the forward here is the float32 restatement of rtg_dof_fk_f32's, not its bit-exact f64 sincos.
@@ -53,6 +67,11 @@ RTG_DEV double pow_int(double b, int t)
     return r;
 }
 
+struct OriEnt {
+    int slot;
+    float w;
+};
+
 struct FitImages {
     f4v *G;          // [F J] forward: global rotations; reverse: a finished joint's contribution to its parent
     float *P;        // [F J 3] positions, then in place the residual adjoints 2 w_j (P_j - T_j), then the complete ones
@@ -69,8 +88,11 @@ struct FitImages {
     float *Rt;       // root: [F 3] the root translations, likewise
     float *Rs;       // root: [F 14] root_state's rows {m_t, m_q, v_t, v_q}; in the evaluation sweep after the last step
                      // (the moments are out by then) [F 7]: grad_root's rows {dL/dt, dL/dq}
+    f4v *Rh;         // ORI: [F K] the unit target rotations of the oriented links
+    OriEnt *otab;    // ORI: [J] per joint {slot in 0..K-1 or -1: not oriented, rot_weight}
     size_t floats;
-    __host__ __device__ FitImages(float *base, int J, int F, int steps, bool root)
+    // K < 0: no orientation images
+    __host__ __device__ FitImages(float *base, int J, int F, int steps, bool root, int K = -1)
     {
         LdsCarve c(base);
         G = c.take<f4v>((size_t)F * J);
@@ -87,6 +109,8 @@ struct FitImages {
         Rq = c.take<f4v>(root ? F : 0);
         Rt = c.take<float>(root ? 3 * F : 0);
         Rs = c.take<float>(root ? 14 * F : 0);
+        Rh = c.take<f4v>(K > 0 ? (size_t)F * K : 0);
+        otab = c.take<OriEnt>(K >= 0 ? J : 0);
         floats = c.floats;
     }
 };
@@ -160,6 +184,33 @@ RTG_DEV float fit_residual(const FitImages &I, int J, bool live, int fr, int sub
     return acc;
 }
 
+// ORI: joint j's own upstream rotation adjoint, -8 w c Rh with c = <G_j, Rh>, from the forward's G_j (the caller
+// forms it before the row is overwritten); +0 for a joint that is not oriented
+template <bool ORI>
+RTG_DEV f4v orient_adjoint(const FitImages &I, int K, int fr, int row, int j)
+{
+    if (!ORI) return f4v{0.0f, 0.0f, 0.0f, 0.0f};
+    const OriEnt o = I.otab[j];
+    if (o.slot < 0) return f4v{0.0f, 0.0f, 0.0f, 0.0f};
+    const f4v R = I.Rh[fr * K + o.slot];
+    const float s = -8.0f * o.w * fdot4(q_of(I.G[row]), q_of(R));
+    return f4v{s * R.x, s * R.y, s * R.z, s * R.w};
+}
+
+// ORI: the links' part of frame fr's loss from the forward's G rows, added to l in k order
+RTG_DEV float orient_loss(const FitImages &I, const DofFitOriArgs &O, int J, int fr, float l)
+{
+#pragma unroll
+    for (int k = 0; k < RTG_FIT_MAX_ROT_LINKS; ++k) {
+        if (k < O.K) {
+            const int j = O.joint[k];
+            const float c = fdot4(q_of(I.G[fr * J + j]), q_of(I.Rh[fr * O.K + k]));
+            l = __builtin_fmaf(I.otab[j].w, 4.0f * __builtin_fmaf(-c, c, 1.0f), l);
+        }
+    }
+    return l;
+}
+
 struct AdamStep {
     float b1, omb1, b2, omb2, eps;
     float step, rbc2s;   // lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)
@@ -177,14 +228,15 @@ RTG_DEV float adam_step(const AdamStep &S, float step, float g, float &m, float 
 // The root's reverse step (one lane per frame): its children's rows pulled as k_fk_bwd_group's j == 0 does, giving
 // dL/dt (the root's own residual included) and dL/dG_0; a fitted rotation's gradient goes through G_0 = q / |q|: it is
 // tangent, (g - (g.G_0) G_0) / |q| (under the norm's clamp the divisor is a constant), a given one's is dL/dG_0 itself
-// (the unnormalised model, as rtg_dof_fk_backward_f32 reports it).  EVAL: grad_root's row into the Rs image, else the
+// (the unnormalised model, as rtg_dof_fk_backward_f32 reports it).  ORI: an oriented root's own adjoint leads the pull
+// (G_0 as the model uses it: the row the forward sweep preset, which nothing has overwritten).  EVAL: grad_root's row into the Rs image, else the
 // Adam steps of the fitted blocks, q renormalised after its step.
-template <bool EVAL>
-RTG_DEV void fit_root_reverse(const FitImages &I, int J, int fr, int first_child, int fit_root, const AdamStep &S)
+template <bool EVAL, bool ORI>
+RTG_DEV void fit_root_reverse(const FitImages &I, int J, int K, int fr, int first_child, int fit_root, const AdamStep &S)
 {
     const int base = fr * J;
     V pb;
-    f4v g = child_pull(f4v{0.0f, 0.0f, 0.0f, 0.0f}, I.G, I.P, base, 0, first_child, I.nsib, pb);
+    f4v g = child_pull(orient_adjoint<ORI>(I, K, fr, base, 0), I.G, I.P, base, 0, first_child, I.nsib, pb);
     const f4v q = I.Rq[fr];
     if (fit_root & RTG_FIT_ROOT_ROT) {
         const float n = __builtin_sqrtf(fdot4(q_of(q), q_of(q)));
@@ -218,9 +270,10 @@ RTG_DEV void fit_root_reverse(const FitImages &I, int J, int fr, int first_child
 }
 
 // the reverse sweep; EVAL: the gradient rows into the M image, else the Adam step of each angle where its gradient
-// appears; ROOT: the sweep ends with the root's step (fit_root_reverse)
-template <bool CLIP, bool EVAL, int F, bool ROOT>
-RTG_DEV void fit_reverse(const FitImages &I, int J, int gsteps, bool live, int fr, int sub, const AdamStep &S,
+// appears; ROOT: the sweep ends with the root's step (fit_root_reverse); ORI: an oriented joint's own rotation adjoint
+// leads its pull (orient_adjoint)
+template <bool CLIP, bool EVAL, int F, bool ROOT, bool ORI>
+RTG_DEV void fit_reverse(const FitImages &I, int J, int K, int gsteps, bool live, int fr, int sub, const AdamStep &S,
                          int fit_root)
 {
     using G = Grp<F>;
@@ -232,8 +285,8 @@ RTG_DEV void fit_reverse(const FitImages &I, int J, int gsteps, bool live, int f
         const int j = e.code & 0xFF, p = (e.code >> 8) & 0xFF;
         if (live && j != 0xFF && j != 0) {
             V pb;
-            const f4v a = child_pull(f4v{0.0f, 0.0f, 0.0f, 0.0f}, I.G, I.P, base, j, (e.code >> 16) & 0xFF, I.nsib,
-                                     pb);
+            const f4v a = child_pull(orient_adjoint<ORI>(I, K, fr, base + j, j), I.G, I.P, base, j,
+                                     (e.code >> 16) & 0xFF, I.nsib, pb);
             const Q Gp = q_of(I.G[base + p]), Gj = q_of(I.G[base + j]);
             const f4v t = I.tab[j];
             const int i = fr * nd + j - 1;
@@ -252,25 +305,29 @@ RTG_DEV void fit_reverse(const FitImages &I, int J, int gsteps, bool live, int f
                 I.A[i] = __builtin_fmaf(-S.step, m / __builtin_fmaf(__builtin_sqrtf(v), S.rbc2s, S.eps), ang);
             }
         }
-        if (ROOT && live && j == 0) fit_root_reverse<EVAL>(I, J, fr, (e.code >> 16) & 0xFF, fit_root, S);
+        if (ROOT && live && j == 0) fit_root_reverse<EVAL, ORI>(I, J, K, fr, (e.code >> 16) & 0xFF, fit_root, S);
         wave_sync();   // this step's rows before the next step's parents pull them (other lanes)
     }
 }
 
 using RootStateRows = LaneRows<float, 4>;   // a tile's root_state rows: 14 F <= 256 floats
+using OriRows = LaneRows<f4v, 2>;           // a tile's target rotations: F K <= 128 records
 
 // one tile of the fit; ROOT: the root's rows come from the root image and its adjoints are taken (R: the root's
-// arguments, not looked at otherwise)
-template <bool CLIP, int F, bool ROOT>
-RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs &A, const DofFitRootArgs &R)
+// arguments, not looked at otherwise); ORI: with orientation targets (O: theirs, likewise)
+template <bool CLIP, int F, bool ROOT, bool ORI>
+RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs &A, const DofFitRootArgs &R,
+                          const DofFitOriArgs &O)
 {
+    static_assert(ROOT || !ORI, "the oriented tile carries the root image");
     extern __shared__ __attribute__((aligned(16))) float ft_lds[];
     using G = Grp<F>;
     const int J = T.J, lane = (int)threadIdx.x, nd = J - 1;
     const int64_t f0 = (int64_t)blockIdx.x * F;
     const int nfr = tile_frames<F>(A.B, f0);
     const int npos = 3 * nfr * J, nang = nfr * nd;
-    const FitImages I(ft_lds, J, F, T.gsteps, ROOT);
+    const int K = ORI ? O.K : 0;
+    const FitImages I(ft_lds, J, F, T.gsteps, ROOT, ORI ? K : -1);
     float *lossp = I.lossp, *adam = I.adam;
     const int fit_root = ROOT ? R.fit_root : 0;
 
@@ -285,6 +342,8 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
         v0.load(A.v + f0 * nd, nang);
     }
     if (rstate) rs.load(R.state + f0 * 14, 14 * nfr);
+    OriRows tr = {};
+    if (ORI && K > 0) tr.load(O.target_rot + f0 * K * 4, nfr * K);
     const float *trow = A.target_pos + f0 * J * 3;
     PosRows<F> tp;
     tp.load(trow, npos);
@@ -296,6 +355,18 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
     m0.store(I.M, nang);
     v0.store(I.V, nang);
     tp.to_lds(I.T, trow, npos);
+    if (ORI) {   // the unit targets, and each joint's entry from the launch's link list
+#pragma unroll
+        for (int k = 0; k < 2; ++k) tr.v[k] = root_unit(tr.v[k]);
+        tr.store(I.Rh, nfr * K);
+        for (int j = lane; j < J; j += 64) {
+            int slot = -1;
+#pragma unroll
+            for (int k = 0; k < RTG_FIT_MAX_ROT_LINKS; ++k)
+                if (k < K && O.joint[k] == j) slot = k;
+            I.otab[j] = OriEnt{slot, slot >= 0 && O.rot_weight ? ld_const(O.rot_weight + slot) : 1.0f};
+        }
+    }
     if (ROOT) {   // the root image; fit_forward presets the root's rows from it
         if (lane < nfr) I.Rq[lane] = rr;
         if (lane < 3 * nfr) I.Rt[lane] = rt;
@@ -339,7 +410,7 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
         }
         fit_forward<CLIP, F, ROOT>(I, J, T.gsteps, live, fr, sub, fit_root);
         (void)fit_residual<F, ROOT>(I, J, live, fr, sub);
-        fit_reverse<CLIP, false, F, ROOT>(I, J, T.gsteps, live, fr, sub, S, fit_root);
+        fit_reverse<CLIP, false, F, ROOT, ORI>(I, J, K, T.gsteps, live, fr, sub, S, fit_root);
     }
 
     // the iterate and its state out (coalesced), then loss and gradient there by one more sweep
@@ -364,11 +435,12 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
             float l = lossp[lane * G::L];
 #pragma unroll
             for (int u = 1; u < G::L; ++u) l += lossp[lane * G::L + u];
+            if (ORI) l = orient_loss(I, O, J, lane, l);   // G still holds the forward's rotations
             A.loss[f0 + lane] = l;
         }
     }
     if (A.grad || (ROOT && R.grad)) {
-        fit_reverse<CLIP, true, F, ROOT>(I, J, T.gsteps, live, fr, sub, S, fit_root);
+        fit_reverse<CLIP, true, F, ROOT, ORI>(I, J, K, T.gsteps, live, fr, sub, S, fit_root);
         if (A.grad) ScalarRows<F>::copy_out(I.M, A.grad + f0 * nd, nang);
         if (ROOT && R.grad) RootStateRows::copy_out(I.Rs, R.grad + f0 * 7, 7 * nfr);
     }
@@ -377,13 +449,20 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
 template <bool CLIP, int F>
 __global__ __launch_bounds__(64) void k_dof_fit_group(TopoView T, DofView D, DofFitArgs A)
 {
-    dof_fit_tile<CLIP, F, false>(T, D, A, DofFitRootArgs{});
+    dof_fit_tile<CLIP, F, false, false>(T, D, A, DofFitRootArgs{}, DofFitOriArgs{});
 }
 
 template <bool CLIP, int F>
 __global__ __launch_bounds__(64) void k_dof_fit_root_group(TopoView T, DofView D, DofFitArgs A, DofFitRootArgs R)
 {
-    dof_fit_tile<CLIP, F, true>(T, D, A, R);
+    dof_fit_tile<CLIP, F, true, false>(T, D, A, R, DofFitOriArgs{});
+}
+
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_orient_group(TopoView T, DofView D, DofFitArgs A, DofFitRootArgs R,
+                                                             DofFitOriArgs O)
+{
+    dof_fit_tile<CLIP, F, true, true>(T, D, A, R, O);
 }
 
 template <bool ROOT>
@@ -419,6 +498,25 @@ hipError_t launch_dof_fit_root(const TopoView &T, const DofView &D, bool clip, c
                                const DofFitRootArgs &R, hipStream_t s)
 {
     return launch_fit<true>(T, D, clip, A, R, s);
+}
+
+hipError_t launch_dof_fit_orient(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
+                                 const DofFitRootArgs &R, const DofFitOriArgs &O, hipStream_t s)
+{
+    if (!T.gsched || O.K < 0 || O.K > RTG_FIT_MAX_ROT_LINKS) return hipErrorInvalidValue;
+    for (int k = 0; k < O.K; ++k)   // the kernel indexes rows with them
+        if (O.joint[k] < 0 || O.joint[k] >= T.J) return hipErrorInvalidValue;
+    const int F = T.gF;
+    const size_t lds = sizeof(float) * FitImages(nullptr, T.J, F, T.gsteps, true, O.K).floats;
+    if (lds > kFitMaxLdsBytes) return hipErrorInvalidValue;
+    hipError_t attr = hipSuccess;
+    group_dispatch(F, [&](auto f, auto cl) {
+        attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_orient_group<cl(), f()>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
+        if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_orient_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A, R, O);
+    }, clip);
+    if (attr != hipSuccess) return attr;
+    return hipGetLastError();
 }
 
 }  // namespace rtg

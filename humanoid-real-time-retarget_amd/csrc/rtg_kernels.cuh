@@ -113,6 +113,16 @@ struct DofFitRootArgs {
 };
 hipError_t launch_dof_fit_root(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
                                const DofFitRootArgs &R, hipStream_t s);
+// rtg_dof_fit_orient_f32: the root launch with orientation targets for K <= RTG_FIT_MAX_ROT_LINKS links.  joint: the
+// links' joint indices (host-checked: in range, none twice), carried in the launch arguments; target_rot (B,K,4),
+// rot_weight (K) or nullptr: device memory
+struct DofFitOriArgs {
+    const float *target_rot, *rot_weight;
+    int32_t K;
+    int32_t joint[RTG_FIT_MAX_ROT_LINKS];
+};
+hipError_t launch_dof_fit_orient(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
+                                 const DofFitRootArgs &R, const DofFitOriArgs &O, hipStream_t s);
 // SkeletonState.retarget_to (poselib skeleton3d.py:742-889) as one launch, rtg_retarget_to.hip.
 // The host tables of a mapping of K (source joint, target joint) pairs: S_red / T_red are the trees with only the
 // mapped joints kept, each hung from its nearest kept ancestor (drop_nodes_by_names, :226-259).

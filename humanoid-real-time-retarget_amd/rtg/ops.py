@@ -444,6 +444,48 @@ def _fit_inputs(model, target_pos, root_rot, root_t, dof, weight):
     return tp, d, rr, rt, w
 
 
+FIT_MAX_ROT_LINKS = 8   # rtg.h RTG_FIT_MAX_ROT_LINKS
+
+Orient = collections.namedtuple("Orient", "joints K target_rot rot_weight")   # joints: the host int32 array of the call
+
+
+def _orient_inputs(model, lead, rot_joints, target_rot, rot_weight):
+    """The orientation targets of a fit, checked before the C ABI sees a pointer: rot_joints K <= 8 distinct joint
+    indices in 0..J-1 (host integers: they travel in the launch's arguments); target_rot (..., K, 4) [x, y, z, w] over
+    the batch shape ``lead``, as a contiguous float32 device tensor with 16-byte aligned rows (copied where it is not);
+    rot_weight (K,) or None.  None when none of the three is given."""
+    if rot_joints is None and target_rot is None and rot_weight is None:
+        return None
+    if rot_joints is None or target_rot is None:
+        raise ValueError("orientation targets need both rot_joints and target_rot")
+    import numpy as np
+    if isinstance(rot_joints, torch.Tensor):
+        rot_joints = rot_joints.detach().cpu().numpy()
+    jn = np.asarray(rot_joints)
+    if jn.ndim != 1 or (jn.size and not np.issubdtype(jn.dtype, np.integer)):
+        raise ValueError(f"rot_joints must be a 1-D sequence of joint indices, got {rot_joints!r}")
+    joints = [int(j) for j in jn]
+    K, J = len(joints), model.num_dofs + 1
+    if K > FIT_MAX_ROT_LINKS:
+        raise ValueError(f"at most {FIT_MAX_ROT_LINKS} oriented links, got {K}")
+    if any(not 0 <= j < J for j in joints) or len(set(joints)) != K:
+        raise ValueError(f"rot_joints must be distinct joint indices in 0..{J - 1}, got {joints}")
+    tr = _as_tensor(target_rot)
+    if tr.dtype not in (torch.float16, torch.bfloat16, torch.float32, torch.float64):
+        raise ValueError(f"target_rot must be floating point, got {tr.dtype}")
+    tr = dev_f32(tr.detach(), (K, 4), "target_rot")
+    if tuple(tr.shape[:-2]) != tuple(lead):
+        raise ValueError(f"target_rot {tuple(tr.shape)} does not match the batch shape {tuple(lead)} of target_pos")
+    if tr.data_ptr() % 16:
+        tr = tr.clone()
+    rw = None
+    if rot_weight is not None:
+        rw = dev_f32(rot_weight, (K,), "rot_weight")
+        if rw.dim() != 1:
+            raise ValueError(f"rot_weight must be ({K},), got {tuple(rw.shape)}")
+    return Orient((ctypes.c_int32 * max(K, 1))(*joints), K, tr, rw)
+
+
 def _fit_state(model, d, dof0, iters, state):
     """What dof_fit and pose_fit share around their launches: ``iters`` range-checked; the angles' optimiser state
     ``(m, v, step)`` -- fresh (zeros, 0) for ``state`` None, else the caller's, copied (the launch updates it in
@@ -478,7 +520,8 @@ def _fit_launch(model, clip, tp, w, rr, rt, d, iters=0, lr=0.0, betas=(0.9, 0.99
 
 
 def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: int = 32, lr: float = 0.02,
-            betas=(0.9, 0.999), eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False):
+            betas=(0.9, 0.999), eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False,
+            rot_joints=None, target_rot=None, rot_weight=None):
     """Fit the joint angles of a DofModel to target keypoints: ``iters`` steps of torch.optim.Adam (no weight decay, no
     amsgrad) on L_f = sum_j weight[j] |P_j(a_f) - target_pos[f, j]|^2, P the positions of dof_forward_kinematics --
     forward model, loss, gradient and optimiser in ONE launch (rtg_dof_fit_f32).
@@ -491,21 +534,37 @@ def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: 
 
     Returns ``(dof, loss, state)`` -- the angles after the last step (dof0's shape), the per-frame loss there (...),
     and the new state -- plus the gradient there (dof's shape) when ``return_grad``.  ``iters=0`` only evaluates.
+    ``rot_joints``, ``target_rot``, ``rot_weight``: pose_fit's orientation targets, with the root given
+    (rtg_dof_fit_orient_f32 with fit_root = 0; an oriented root then only adds to the loss).
     Raises RtgError without a GPU: there is no CPU fallback."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof0, weight)
     iters, m, v, step, as_dof0 = _fit_state(model, d, dof0, iters, state)
-    out, loss, grad = _fit_launch(model, clip, tp, w, rr, rt, d.detach(), iters, lr, betas, eps, step, m, v,
-                                  want_dof=True, want_grad=bool(return_grad))
+    orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
+    if orient is None:
+        out, loss, grad = _fit_launch(model, clip, tp, w, rr, rt, d.detach(), iters, lr, betas, eps, step, m, v,
+                                      want_dof=True, want_grad=bool(return_grad))
+    else:   # the root is given: its state is neither read nor written, the buffer only pairs with m and v
+        rs = torch.zeros(tuple(tp.shape[:-2]) + (14,), device=d.device, dtype=torch.float32)
+        out, _, _, loss, grad, _ = _pose_launch(model, clip, 0, tp, w, rr, rt, d.detach(), iters, lr, 0.0, 0.0, betas, eps,
+                                                step, m if m.numel() else rs, v if v.numel() else rs, rs,
+                                                want_iterate=True, want_grad=bool(return_grad), orient=orient)
     res = (as_dof0(out), loss, (m, v, step + iters))
     return res + (as_dof0(grad),) if return_grad else res
 
 
-def keypoint_loss(model, dof, target_pos, root_rot, root_t, weight=None, clip: bool = False):
+def keypoint_loss(model, dof, target_pos, root_rot, root_t, weight=None, clip: bool = False, rot_joints=None,
+                  target_rot=None, rot_weight=None):
     """The per-frame keypoint loss L_f = sum_j weight[j] |P_j(dof_f) - target_pos[f, j]|^2 of dof_fit, (...), as the
     evaluate-only launch of rtg_dof_fit_f32.  Differentiable in ``dof`` (only): the launch computes the gradient
     along with the loss, and backward scales its rows by the upstream cotangent -- for callers who keep their own
-    optimiser.  Under no_grad, or when dof does not require grad, it is the plain launch without the gradient."""
+    optimiser.  Under no_grad, or when dof does not require grad, it is the plain launch without the gradient.
+    ``rot_joints``, ``target_rot``, ``rot_weight``: dof_fit's orientation targets."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof, weight)
+    orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
+    if orient is not None:
+        if torch.is_grad_enabled() and d.requires_grad:
+            return _OrientPoseLoss.apply(model, bool(clip), 0, d, rr.detach(), rt.detach(), tp, w, orient)
+        return _pose_launch(model, clip, 0, tp, w, rr, rt, d.detach(), orient=orient)[3]
     if torch.is_grad_enabled() and d.requires_grad:
         return _KeypointLoss.apply(model, bool(clip), d, tp, rr, rt, w)
     return _fit_launch(model, clip, tp, w, rr, rt, d.detach())[1]
@@ -533,26 +592,31 @@ PoseFitGrad = collections.namedtuple("PoseFitGrad", "dof root_rot root_t loss st
 
 def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_root_t=0.0, lr_root_rot=0.0,
                  betas=(0.9, 0.999), eps=1e-8, step0=0, m=None, v=None, root_state=None, want_iterate=False,
-                 want_loss=True, want_grad=False):
-    """rtg_dof_fit_root_f32 on prepared tensors; m, v, root_state are updated in place.  Returns (dof_out, root_rot_out,
-    root_t_out, loss, grad, grad_root), None where not asked for."""
+                 want_loss=True, want_grad=False, orient=None):
+    """rtg_dof_fit_root_f32 -- with ``orient`` (an Orient) rtg_dof_fit_orient_f32 -- on prepared tensors; m, v,
+    root_state are updated in place.  Returns (dof_out, root_rot_out, root_t_out, loss, grad, grad_root), None where
+    not asked for."""
     lead = tuple(tp.shape[:-2])
     B = int(torch.Size(lead).numel())
     new = lambda like, *tail: torch.empty(lead + tail, device=like.device, dtype=torch.float32)
     out, rr_out, rt_out = (torch.empty_like(d), torch.empty_like(rr), torch.empty_like(rt)) if want_iterate else (None,) * 3
     loss = new(d) if want_loss else None
     grad, grad_root = (torch.empty_like(d), new(d, 7)) if want_grad else (None, None)
-    check(lib().rtg_dof_fit_root_f32(model.handle, ptr(tp), ptr(w), ptr(rr), ptr(rt), ptr(d), B, int(bool(clip)),
-                                     int(fit_root), int(iters), float(lr), float(lr_root_t), float(lr_root_rot),
-                                     float(betas[0]), float(betas[1]), float(eps), int(step0), ptr(m), ptr(v),
-                                     ptr(root_state), ptr(out), ptr(rr_out), ptr(rt_out), ptr(loss), ptr(grad),
-                                     ptr(grad_root), stream_handle()))
+    tail = (ptr(rr), ptr(rt), ptr(d), B, int(bool(clip)), int(fit_root), int(iters), float(lr), float(lr_root_t),
+            float(lr_root_rot), float(betas[0]), float(betas[1]), float(eps), int(step0), ptr(m), ptr(v), ptr(root_state),
+            ptr(out), ptr(rr_out), ptr(rt_out), ptr(loss), ptr(grad), ptr(grad_root), stream_handle())
+    if orient is None:
+        check(lib().rtg_dof_fit_root_f32(model.handle, ptr(tp), ptr(w), *tail))
+    else:
+        check(lib().rtg_dof_fit_orient_f32(model.handle, ptr(tp), ptr(w), orient.joints, ptr(orient.target_rot),
+                                           ptr(orient.rot_weight), orient.K, *tail))
     return out, rr_out, rt_out, loss, grad, grad_root
 
 
 def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iters: int = 32, lr: float = 0.02,
              lr_root_t=None, lr_root_rot=None, fit_root_t: bool = True, fit_root_rot: bool = True, betas=(0.9, 0.999),
-             eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False):
+             eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False, rot_joints=None,
+             target_rot=None, rot_weight=None):
     """dof_fit with the floating base among the parameters: the joint angles and -- where ``fit_root_t`` /
     ``fit_root_rot`` -- the root translation and rotation of every frame, fitted to target keypoints by ``iters`` steps
     of torch.optim.Adam with three parameter groups (``lr`` for the angles, ``lr_root_t``, ``lr_root_rot``; None: ``lr``)
@@ -564,6 +628,13 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
     (..., J-1, 1)], default zeros; weight (J,) or None.  ``state`` is ``(m, v, root_state, step)`` from an earlier call
     (None: a fresh optimiser), root_state (..., 14) = {m_t, m_q, v_t, v_q}; it is returned updated, and calls chain:
     two calls of n steps give the bits of one call of 2n.
+
+    Orientation targets (rtg_dof_fit_orient_f32, still one launch): ``rot_joints`` K <= 8 distinct joint indices,
+    ``target_rot`` (..., K, 4) [x, y, z, w] their global rotations (any norm, either sign), ``rot_weight`` (K,) or
+    None for ones.  The loss gains sum_k rot_weight[k] 4 (1 - <G_k, target_k / |target_k|>^2) -- the squared chord
+    (2 sin(theta/2))^2 of the angle between the link's rotation and its target, theta^2 for small angles -- which is what
+    poses leaf joints (wrists, ankles, the head) and a link's twist; positions alone give those DOFs a gradient of
+    exactly 0.  The term is stationary at theta = pi.  With none of the three given this is the position-only launch.
 
     Returns the named tuple ``(dof, root_rot, root_t, loss, state)`` -- the iterate after the last step (root_rot
     (..., 4), unit where fitted), the per-frame loss there -- plus ``grad`` (dof's shape) and ``grad_root`` (..., 7) =
@@ -577,29 +648,36 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
     else:
         rs = dev_f32(state[2], (14,), "root_state").reshape(lead + (14,)).clone()
     fit_root = (FIT_ROOT_T if fit_root_t else 0) | (FIT_ROOT_ROT if fit_root_rot else 0)
+    orient = _orient_inputs(model, lead, rot_joints, target_rot, rot_weight)
     # (a one-joint model has no angle moments: their arguments only say that a state is given)
     out, rr_out, rt_out, loss, grad, grad_root = _pose_launch(
         model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach(), iters, lr,
         lr if lr_root_t is None else lr_root_t, lr if lr_root_rot is None else lr_root_rot, betas, eps, step,
-        m if m.numel() else rs, v if v.numel() else rs, rs, want_iterate=True, want_grad=bool(return_grad))
+        m if m.numel() else rs, v if v.numel() else rs, rs, want_iterate=True, want_grad=bool(return_grad),
+        orient=orient)
     new_state = (m, v, rs, step + iters)
     if return_grad:
         return PoseFitGrad(as_dof0(out), rr_out, rt_out, loss, new_state, as_dof0(grad), grad_root)
     return PoseFit(as_dof0(out), rr_out, rt_out, loss, new_state)
 
 
-def pose_loss(model, dof, root_rot, root_t, target_pos, weight=None, clip: bool = False, normalize_root: bool = True):
+def pose_loss(model, dof, root_rot, root_t, target_pos, weight=None, clip: bool = False, normalize_root: bool = True,
+              rot_joints=None, target_rot=None, rot_weight=None):
     """The per-frame keypoint loss of pose_fit, (...), as the evaluate-only launch of rtg_dof_fit_root_f32,
     differentiable in ``dof``, ``root_rot`` and ``root_t``: the launch computes the three gradients along with the
     loss and backward scales their rows by the upstream cotangent -- for callers who keep their own optimiser.
     ``normalize_root``: the root rotation enters as q / |q| and its gradient is tangent (pose_fit's model of a fitted
     rotation); False: as given, like keypoint_loss.  Under no_grad, or when no input requires grad, it is the plain
-    launch without the gradients."""
+    launch without the gradients.  ``rot_joints``, ``target_rot``, ``rot_weight``: pose_fit's orientation targets (the
+    loss is not differentiable in them)."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof, weight)
     fit_root = FIT_ROOT_ROT if normalize_root else 0   # no step is taken: the mask only selects the model
+    orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
     if torch.is_grad_enabled() and (d.requires_grad or rr.requires_grad or rt.requires_grad):
+        if orient is not None:
+            return _OrientPoseLoss.apply(model, bool(clip), fit_root, d, rr, rt, tp, w, orient)
         return _PoseLoss.apply(model, bool(clip), fit_root, d, rr, rt, tp, w)
-    return _pose_launch(model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach())[3]
+    return _pose_launch(model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach(), orient=orient)[3]
 
 
 class _PoseLoss(torch.autograd.Function):
@@ -615,6 +693,23 @@ class _PoseLoss(torch.autograd.Function):
         grad, grad_root = ctx.saved_tensors
         c = grad_loss.unsqueeze(-1)
         return None, None, None, grad * c, grad_root[..., 3:] * c, grad_root[..., :3] * c, None, None
+
+
+class _OrientPoseLoss(torch.autograd.Function):
+    """_PoseLoss with orientation targets: the evaluate-only launch of rtg_dof_fit_orient_f32."""
+    @staticmethod
+    def forward(ctx, model, clip, fit_root, d, rr, rt, tp, w, orient):
+        _, _, _, loss, grad, grad_root = _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, want_grad=True,
+                                                      orient=orient)
+        ctx.save_for_backward(grad, grad_root)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        grad, grad_root = ctx.saved_tensors
+        c = grad_loss.unsqueeze(-1)
+        return None, None, None, grad * c, grad_root[..., 3:] * c, grad_root[..., :3] * c, None, None, None
 
 
 def rescale_motion(topo: Topology, motion, dir=None):

@@ -28,8 +28,8 @@
 extern "C" {
 #endif
 
-#define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*); rtg_dof_fit_f32 and
-                                  rtg_dof_fit_root_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
+#define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*); rtg_dof_fit_f32,
+                                  rtg_dof_fit_root_f32 and rtg_dof_fit_orient_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
                                6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
                                5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
                                4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
@@ -225,6 +225,45 @@ int rtg_dof_fit_root_f32(rtg_dof_model_t model, const float *target_pos, const f
                          float lr, float lr_root_t, float lr_root_rot, float beta1, float beta2, float eps,
                          int32_t step0, float *m, float *v, float *root_state, float *dof_out, float *root_rot_out,
                          float *root_t_out, float *loss, float *grad, float *grad_root, rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * rtg_dof_fit_root_f32 with orientation targets for K chosen links (a new symbol under ABI 7).  Positions alone cannot
+ * pose a leaf joint (its rotation moves no keypoint) nor the twist of a link about the line through its keypoints;
+ * here link rot_joint[k] is also pulled towards the global rotation target_rot[f,k].  Per frame f
+ *     L_f = sum_j weight[j] |P_j - target_pos[f,j]|^2 + sum_k rot_weight[k] 4 (1 - c_k^2),
+ *     c_k = <G_j, Rh_fk>,  j = rot_joint[k],  Rh_fk = target_rot[f,k] / max(|target_rot[f,k]|, 1e-9) (no sign flip),
+ * G_j the global rotation of link j as the forward model holds it (unit below the root; the root's G_0 is
+ * q / max(|q|, 1e-9) where RTG_FIT_ROOT_ROT is set, else q as given).  4 (1 - c^2) = (2 sin(theta/2))^2 for the
+ * angle theta between the two rotations: it does not see the sign of either quaternion and is theta^2 to second
+ * order, so rot_weight reads "per rad^2" next to weight's "per m^2".  It is stationary at theta = pi as well as at
+ * 0: a link exactly half a turn from its target gets no pull from this term.  Its gradient enters the reverse sweep
+ * as dL/dG_j = -8 rot_weight[k] c_k Rh_fk; everything else -- Adam, the three step sizes, the root's normalisation,
+ * step0, the clip, the outputs -- is rtg_dof_fit_root_f32's.  An oriented root (rot_joint[k] == 0) that is given, not
+ * fitted, adds to the loss and to grad_root's dL/dq (of the unnormalised model) and moves nothing.
+ *   rot_joint (K): joint indices, a HOST pointer, read before the call returns (the launch carries the K <= 8 values
+ *   in its arguments, so the call neither allocates nor synchronises, and they are checked here: in 0..J-1, none
+ *   twice); target_rot (B,K,4) [x, y, z, w], device memory, 16-byte aligned; rot_weight (K) device memory, or
+ *   NULL = all 1; 0 <= K <= RTG_FIT_MAX_ROT_LINKS.  With K == 0 the three pointers are not looked at.
+ * Guarantees: K == 0 gives rtg_dof_fit_root_f32's outputs bit for bit (so fit_root == 0 with K == 0 gives
+ * rtg_dof_fit_f32's).  A DOF gets a gradient of exactly +-0, and from a zero state keeps its bits, when its strict
+ * subtree carries no position weight and its subtree, its own link included, holds no oriented link (a link with
+ * rot_weight 0 still counts as oriented).  A frame depends on its own rows alone (not on the batch, the tile or
+ * another frame's NaN / inf), runs are bit-identical, and n launches of one step that carry (m, v, root_state, step0)
+ * equal one launch of n steps.  A zero target row has Rh = 0: it adds the constant 4 rot_weight[k] and no gradient; a
+ * NaN row makes that frame's loss and gradients NaN -- in both cases exactly where the float32 restatement of the
+ * formula above does, and in no other frame.
+ * Errors: rtg_dof_fit_root_f32's, and K < 0, K > 0 with rot_joint or target_rot NULL, target_rot not 16-byte
+ * aligned, a joint index outside 0..J-1 or listed twice -> RTG_ERR_INVALID_ARGUMENT; K > RTG_FIT_MAX_ROT_LINKS ->
+ * RTG_ERR_UNSUPPORTED; all before any device work.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------- */
+#define RTG_FIT_MAX_ROT_LINKS 8   /* the links' target rows share the tile's LDS */
+int rtg_dof_fit_orient_f32(rtg_dof_model_t model, const float *target_pos, const float *weight,
+                           const int32_t *rot_joint, const float *target_rot, const float *rot_weight, int32_t K,
+                           const float *root_rot, const float *root_t, const float *dof_in, int64_t B, int clip,
+                           int32_t fit_root, int32_t iters, float lr, float lr_root_t, float lr_root_rot, float beta1,
+                           float beta2, float eps, int32_t step0, float *m, float *v, float *root_state,
+                           float *dof_out, float *root_rot_out, float *root_t_out, float *loss, float *grad,
+                           float *grad_root, rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * SkeletonState.retarget_to (poselib skeleton3d.py:742-889): the generic skeleton-to-skeleton retarget, rotations

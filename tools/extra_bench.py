@@ -23,6 +23,12 @@
               build's, and that of another build named by RTG_PARENT_LIB -- and the composed iteration with the root
               among torch's parameters, interleaved rounds
   pose_fit_traffic -- a few launches of rtg_dof_fit_root_f32 and nothing else, for a counter run of its own
+  orient_fit -- the oriented leg of the fit family: the pose fit with orientation targets (rtg_dof_fit_orient_f32,
+              fit_root = 3, same shapes and start as `pose_fit`) per iteration with K = 0, 5 (both hands, both feet, the
+              head) and 8 links, against rtg_dof_fit_root_f32 of this build, of the build RTG_PARENT_LIB names (when
+              set), and the composed iteration (ops.dof_forward_kinematics, the torch loss with the rotation term,
+              backward() with both cotangents, fused torch Adam with three groups), interleaved rounds
+  orient_fit_traffic -- a few launches of rtg_dof_fit_orient_f32 (K = 8) and nothing else, for a counter run of its own
   motion_sample -- the fused motion sampler (rtg_motion_sample_f32, C ABI, preallocated outputs; Hu v5, 64 clips x 4096
               frames, N=262144 queries; uniform / random / frame-instant queries, with global outputs + velocities
               and local only) against the composed chain (index rule in torch, index_select, quat_slerp,
@@ -462,7 +468,7 @@ def rot_ingest(B=262144, rounds=4):
     return res
 
 
-def _fit_setup(B):
+def _fit_setup(B, want_rot=False):
     from rtg.runtime import DofModel
     import importlib
     hu = importlib.import_module("retarget.robot_config.Hu")
@@ -473,8 +479,11 @@ def _fit_setup(B):
     rr = torch.nn.functional.normalize(torch.randn((B, 4), device="cuda", generator=gen), dim=-1)
     rt = torch.randn((B, 3), device="cuda", generator=gen) * 0.3
     truth = lo_d + (hi_d - lo_d) * torch.rand((B, 32), device="cuda", generator=gen)
-    tgt = ops.dof_forward_kinematics(M, truth, rr, rt, clip=True)[1].contiguous()   # reachable targets
+    g_rot, tgt = ops.dof_forward_kinematics(M, truth, rr, rt, clip=True)   # reachable targets
+    tgt = tgt.contiguous()
     start = (0.5 * (lo_d + hi_d)).expand(B, 32).contiguous()
+    if want_rot:
+        return M, tgt, rr, rt, start, g_rot
     return M, tgt, rr, rt, start
 
 
@@ -558,9 +567,10 @@ def _other_build_fit(path, tgt, rr, rt, start, B, iters, out, loss):
     return lambda: other.rtg_dof_fit_f32(*args)
 
 
-def _pose_fit_setup(B):
-    """_fit_setup's reachable targets; the start has the root 0.2 m and 0.3 rad off."""
-    M, tgt, rr, rt, start = _fit_setup(B)
+def _pose_fit_setup(B, want_rot=False):
+    """_fit_setup's reachable targets; the start has the root 0.2 m and 0.3 rad off.  want_rot: the targets' global
+    rotations (B, 33, 4) too."""
+    M, tgt, rr, rt, start, g_rot = _fit_setup(B, want_rot=True)
     gen = torch.Generator(device="cuda").manual_seed(18)
     unit = lambda n: torch.nn.functional.normalize(torch.randn((B, n), device="cuda", generator=gen), dim=-1)
     off = torch.cat([unit(3) * float(np.sin(0.15)), torch.full((B, 1), float(np.cos(0.15)), device="cuda")], dim=-1)
@@ -569,6 +579,8 @@ def _pose_fit_setup(B):
     rr0 = torch.stack([w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2, w1 * y2 + y1 * w2 + z1 * x2 - x1 * z2,
                        w1 * z2 + z1 * w2 + x1 * y2 - y1 * x2, w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2], dim=-1).contiguous()
     rt0 = (rt + 0.2 * unit(3)).contiguous()
+    if want_rot:
+        return M, tgt, rr0, rt0, start, g_rot
     return M, tgt, rr0, rt0, start
 
 
@@ -644,6 +656,110 @@ def pose_fit_traffic(B=262144, iters=32):
     return {"B": B, "copy_bytes_each_way": 4 << 26,
             "launches": "3 x 256 MiB copy, 4 x iters=%d without a state (dof, root, loss out), then 4 x with (m, v, "
                         "root_state); grids equal" % iters}
+
+
+ORIENT_LINKS = {5: (20, 29, 6, 12, 32),              # both wrist yaw links, both toe links, the neck link
+                8: (20, 29, 6, 12, 32, 13, 17, 26)}   # and the torso and both elbow pitch links
+
+
+def _orient_fit_call(M, tgt, joints, trot, rr0, rt0, start, B, iters, mask, outs, state=(None, None, None), lib=None,
+                     handle=None):
+    import ctypes
+    from rtg.runtime import ptr, stream_handle
+    f = (lib or _lib.lib()).rtg_dof_fit_orient_f32
+    K = len(joints)
+    jarr = (ctypes.c_int32 * max(K, 1))(*joints)
+    args = (handle or M.handle, ptr(tgt), None, jarr, ptr(trot) if K else None, None, K, ptr(rr0), ptr(rt0), ptr(start), B, 1,
+            mask, iters, 0.02, 0.02, 0.02, 0.9, 0.999, 1e-8, 0, *(ptr(s) for s in state), *(ptr(o) for o in outs),
+            stream_handle())
+    _lib.check(f(*args))
+    return lambda: f(*args)
+
+
+def _other_build_pose_fit(path, tgt, rr0, rt0, start, B, iters, outs):
+    """rtg_dof_fit_root_f32 (fit_root = 3) of another build of the library (its own handles), for a same-session
+    comparison."""
+    import ctypes
+    import importlib
+    from rtg.runtime import ptr, stream_handle
+    hu = importlib.import_module("retarget.robot_config.Hu")
+    other = ctypes.CDLL(os.path.abspath(path))
+    for name in ("rtg_topology_create", "rtg_dof_model_create", "rtg_dof_fit_root_f32"):
+        getattr(other, name).restype, getattr(other, name).argtypes = _lib.SIGNATURES[name]
+    i32, f32 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+    host = lambda a, dt: np.ascontiguousarray(np.asarray(a), dt)
+    par, lt, tq = host(assets.parents("hu"), np.int32), host(assets.local_translation("hu"), np.float32), \
+        host(assets.tree_quat("hu"), np.float32)
+    ax, lo, hi = host(hu.Hu_DOF_AXIS, np.int32), host(hu.Hu_DOF_LOWER.numpy(), np.float32), \
+        host(hu.Hu_DOF_UPPER.numpy(), np.float32)
+    th, mh = ctypes.c_void_p(), ctypes.c_void_p()
+    assert other.rtg_topology_create(par.ctypes.data_as(i32), lt.ctypes.data_as(f32), tq.ctypes.data_as(f32), len(par),
+                                     ctypes.byref(th)) == 0
+    assert other.rtg_dof_model_create(th, ax.ctypes.data_as(i32), lo.ctypes.data_as(f32), hi.ctypes.data_as(f32),
+                                      ctypes.byref(mh)) == 0
+    args = (mh, ptr(tgt), None, ptr(rr0), ptr(rt0), ptr(start), B, 1, 3, iters, 0.02, 0.02, 0.02, 0.9, 0.999, 1e-8, 0,
+            None, None, None, *(ptr(o) for o in outs), stream_handle())
+    assert other.rtg_dof_fit_root_f32(*args) == 0
+    return lambda: other.rtg_dof_fit_root_f32(*args)
+
+
+def orient_fit(B=262144, rounds=4, iters=32):
+    """The pose fit with orientation targets (rtg_dof_fit_orient_f32, fit_root = 3, C ABI, preallocated outputs, 33-link
+    Hu, clip on, no state) per iteration with K = 0, 5 and 8 links, against rtg_dof_fit_root_f32 of this build, of the
+    build RTG_PARENT_LIB names (when set), and the composed iteration with K = 5; interleaved rounds."""
+    M, tgt, rr0, rt0, start, g_rot = _pose_fit_setup(B, want_rot=True)
+    J = 33
+    new = lambda *s: torch.empty(s, device="cuda")
+    outs = (new(B, 32), new(B, 4), new(B, 3), new(B), None, None)
+    trot = {K: g_rot[:, list(j)].contiguous() for K, j in ORIENT_LINKS.items()}
+    calls = {"root_us_per_iteration": _pose_fit_call(M, tgt, rr0, rt0, start, B, iters, 3, outs),
+             "orient_k0_us_per_iteration": _orient_fit_call(M, tgt, (), None, rr0, rt0, start, B, iters, 3, outs)}
+    for K, j in ORIENT_LINKS.items():
+        calls[f"orient_k{K}_us_per_iteration"] = _orient_fit_call(M, tgt, j, trot[K], rr0, rt0, start, B, iters, 3, outs)
+    parent = os.environ.get("RTG_PARENT_LIB")
+    if parent:
+        calls["parent_root_us_per_iteration"] = _other_build_pose_fit(parent, tgt, rr0, rt0, start, B, iters, outs)
+    a, q, t = (x.clone().requires_grad_(True) for x in (start, rr0, rt0))
+    opt = torch.optim.Adam([dict(params=[a]), dict(params=[t]), dict(params=[q])], lr=0.02, fused=True)
+    links, Rh = list(ORIENT_LINKS[5]), torch.nn.functional.normalize(trot[5], dim=-1, eps=1e-9)
+
+    def composed():
+        opt.zero_grad(set_to_none=True)
+        gr, gp = ops.dof_forward_kinematics(M, a, torch.nn.functional.normalize(q, dim=-1, eps=1e-9), t, clip=True)
+        c = (gr[:, links] * Rh).sum(-1)
+        ((gp - tgt).square().sum() + (4.0 * (1.0 - c * c)).sum()).backward()
+        opt.step()
+        with torch.no_grad():
+            q.copy_(torch.nn.functional.normalize(q, dim=-1, eps=1e-9))
+
+    res = {k: [] for k in calls}
+    res["composed_k5_us_per_iteration"] = []
+    for _ in range(rounds):   # interleaved: all see the same box state
+        for k, call in calls.items():
+            res[k].append(time_events(call, reps=5, warm=1) * 1e3 / iters)
+        res["composed_k5_us_per_iteration"].append(time_events(composed, reps=10, warm=2) * 1e3)
+    rd, wr = J * 12 + (J - 1) * 4 + 28, (J - 1) * 4 + 4 + 28
+    return {"B": B, "J": J, "iters": iters, **res, "parent_lib": parent, "links": {str(k): list(v) for k, v in ORIENT_LINKS.items()},
+            "algorithmic_bytes_per_frame": {"read": rd, "read_per_link": 16, "written": wr}}
+
+
+def orient_fit_traffic(B=262144, iters=32, K=8):
+    """A few launches of rtg_dof_fit_orient_f32 (fit_root = 3, K = 8, no state) and nothing else, for a counter run of
+    its own (FETCH_SIZE or WRITE_SIZE, one per run) against the algorithmic bytes `orient_fit` prints."""
+    M, tgt, rr0, rt0, start, g_rot = _pose_fit_setup(B, want_rot=True)
+    new = lambda *s: torch.empty(s, device="cuda")
+    outs = (new(B, 32), new(B, 4), new(B, 3), new(B), None, None)
+    trot = g_rot[:, list(ORIENT_LINKS[K])].contiguous()
+    src, dst = torch.randn(1 << 26, device="cuda"), torch.empty(1 << 26, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(3):   # known bytes: the counters' unit
+        dst.copy_(src)
+    call = _orient_fit_call(M, tgt, ORIENT_LINKS[K], trot, rr0, rt0, start, B, iters, 3, outs)
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    return {"B": B, "K": K, "copy_bytes_each_way": 4 << 26,
+            "launches": "3 x 256 MiB copy, 4 x iters=%d, K=%d without a state (dof, root, loss out)" % (iters, K)}
 
 
 def motion_sample(N=262144, rounds=4, clips=64, frames=4096):
