@@ -22,7 +22,7 @@
 #ifndef RTG_SIDES_SOA_WAVES
 #define RTG_SIDES_SOA_WAVES 5   // k_solve_sides FULL_BODY_POS, SoA inputs: min waves per SIMD asked of the compiler (1: it
                                 // picks, 4 at 101 VGPRs; 5: 96 VGPRs, 16 B/lane of spills, and the 31,024-B LDS lets
-                                // five blocks share a CU).  The other instantiations (AoS, other kinds) always get 1.
+                                // five blocks share a CU; round 21's one side program: 90 VGPRs, 16 B/lane).  The other instantiations (AoS, other kinds) always get 1.
                                 // bench.py (steps on two streams) 3.90-3.95 vs 3.73-3.74 G frames/s with 1 and 3.70-3.75
                                 // for the parent; a lone launch 92.8-94.6 vs 93.3-94.5 vs 93.0-94.4 us: 2048 blocks fill
                                 // 1280 slots 1.6 times, so only overlapping launches gain (profiles/r08/ab_*.log)
@@ -115,11 +115,6 @@
 #ifndef RTG_UNIT_TAB_K
 #define RTG_UNIT_TAB_K 16   // the near-unit normalisation table: the 2K + 1 f32 codes around 1.0f (32: no faster,
                             // profiles/r06/unit_tab/ab_k32*)
-#endif
-#ifndef RTG_SIDES_SHARED_FIT
-#define RTG_SIDES_SHARED_FIT 1   // k_solve_sides FULL_BODY_POS: both waves' first fits run one inlined copy of the SVD
-                                 // (134.6 -> 112.3 KB; SoA median 99.2 -> 97.9 us; AoS within noise and +1.4 % VALU, so
-                                 // 1 = SoA only, 2 = AoS too; profiles/r06/shared_code/)
 #endif
 #ifndef RTG_EULER_LIBM
 #define RTG_EULER_LIBM 1   // scipy_as_euler: atan2 correctly rounded and hypot as the host libm computes it (rtg_math.cuh);

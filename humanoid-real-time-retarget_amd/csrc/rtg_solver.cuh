@@ -91,7 +91,21 @@ struct Emit {
     }
     // this wave's table-word loads into LDS have landed (vmcnt 0; expcnt / lgkmcnt not waited on)
     static RTG_DEV void wait_words() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+    // The emitter on which link<LINK> / finalize slot j write link LINK + dl and slot j + ds: the DOF row, local_rot
+    // row, stash and table words carry the shift, so one program serves link groups with the same DOF axes
+    // (side_links_alike) from a run-time base -- and link() still starts the early table-word load.
+    RTG_DEV Emit shifted(int dl, int ds) const
+    {
+        return Emit{row + dl, lr ? lr + 4 * dl : nullptr, ang, st + ds * sst, sst, wd ? wd + ds * 64 : nullptr};
+    }
 };
+// links a .. a + n - 1 and b .. b + n - 1 turn about the same Hu_DOF_AXIS components
+constexpr bool side_links_alike(int a, int b, int n)
+{
+    for (int j = 0; j < n; ++j)
+        if (hu_dof_axis(a + j - 1) != hu_dof_axis(b + j - 1)) return false;
+    return true;
+}
 
 // k0: the first fixed DOF written (k_solve_sides keeps a hand-over slot in the row's first dwords and zeroes them itself)
 RTG_DEV void emit_fixed_links(const Emit &E, bool write_lr = true, int k0 = 0)
@@ -269,7 +283,8 @@ RTG_DEV void store_dof_rows(float *__restrict__ dst, const float *src, int64_t n
 // full_body_retargeter.py:60-177, body_retargeter.py:48-81), so waves 2k and 2k+1 of a block take the left
 // and the right side of the same 64 frames.  The side is wave-uniform: its constants stay scalar, the branch
 // never diverges, and each wave runs about half the frame program -- twice the waves in flight, about half the
-// per-frame latency, the same arithmetic per value.
+// per-frame latency, the same arithmetic per value.  FULL_BODY_POS (the headline) has one copy of the side's code,
+// its constants and link base selected by the scalar side; the other kinds instantiate their side body per side.
 // ----------------------------------------------------------------------------
 constexpr int kSideTiles = RTG_SIDES_TILES;        // 64-frame tiles per block (two waves each)
 constexpr int kSideThreads = 128 * kSideTiles;
@@ -318,31 +333,6 @@ RTG_DEV TipPts load_tips(const View &H)
     return TipPts{H.p3(0), {H.p3(4), H.p3(8), H.p3(12), H.p3(16), H.p3(19)}};
 }
 
-// Both arms' chains at once (round 6): solve_arm for the left and the right arm on the N-way leaf math, so the two
-// independent chains interleave in one instruction stream (the same values: arm_pair_n).  Returns the chains.
-template <typename Tab = NoTab>
-RTG_DEV void fbp_arms2(const SolverConsts &C, const ArmPts &apL, const ArmPts &apR, Q R10, const Emit &E, Q &chL,
-                       Q &chR, Tab tab = Tab{})
-{
-    const V up[2] = {vsub(apL.el, apL.sh), vsub(apR.el, apR.sh)};
-    const V fo[2] = {vsub(apL.wr, apL.el), vsub(apR.wr, apR.el)};
-    const ArmZero zs[2] = {C.lsh, C.rsh}, ze[2] = {C.lel, C.rel};
-    const Q par[2] = {R10, R10};
-    Q p[2], r[2], y[2], e[2];
-    arm_pair_n<true, 2>(up, zs, par, p, r, tab);
-    E.link<12>(p[0]);
-    E.link<13>(r[0]);
-    E.link<21>(p[1]);
-    E.link<22>(r[1]);
-    const Q par2[2] = {qmul(qmul(R10, p[0]), r[0]), qmul(qmul(R10, p[1]), r[1])};
-    arm_pair_n<false, 2>(fo, ze, par2, y, e, tab);
-    E.link<14>(y[0]);
-    E.link<15>(e[0]);
-    E.link<23>(y[1]);
-    E.link<24>(e[1]);
-    chL = qmul(qmul(qmul(p[0], r[0]), y[0]), e[0]);
-    chR = qmul(qmul(qmul(p[1], r[1]), y[1]), e[1]);
-}
 // the gripper DOFs of one side from its x-spread a (full_body_pos_retargeter.py:199-215)
 template <bool PRECISE>
 RTG_DEV void fbp_gripper(const SolverConsts &C, float a, float *row_d0)
@@ -370,18 +360,6 @@ RTG_DEV void fbp_body_rows(float *__restrict__ brow, Q R10, Q W, bool const_rows
             st4(brow + 4 * 10, R10);
         }
     }
-}
-// the Euler split of the wrist (:128-136), the gripper (:142-158 / :165-175) and the body_rot rows; true where
-// scipy refuses the wrist's local quaternion
-template <bool PRECISE, int SIDE, typename Tab = NoTab>
-RTG_DEV bool fbp_side_after_arm(const SolverConsts &C, const TipPts &tp, Q R10, Q chain, Q W, const Emit &E,
-                                float *__restrict__ brow, Tab tab = Tab{})
-{
-    constexpr int E0 = SIDE ? 25 : 16, D0 = SIDE ? 27 : 18;
-    const bool refused = emit_euler_xyz<E0>(E, qmul_norm(qconj(qmul_norm(R10, chain, tab)), W, tab));
-    fbp_gripper<PRECISE>(C, hand_x_mean(qconj(W), tp.h0, tp.t), E.row + D0);
-    if (brow) fbp_body_rows<SIDE>(brow, R10, W);
-    return refused;
 }
 
 // HuUpperBodyFromMocapRetarget (retarget_solver.py:40-99), one side: one arm given the torso fit; wrists untouched
@@ -467,10 +445,10 @@ RTG_DEV void lds_wait(int *flag, uint32_t *err)
     if ((threadIdx.x & 63) == 0) report_device_error(err, RTG_DEVERR_HANDOVER_TIMEOUT);
 }
 
-// The hand-over slot of a frame (FULL_BODY_POS: R10 left -> right wave, then the left chain right -> left; UPPER_BODY:
-// R10 left -> right) is the first four dwords of the frame's own DOF row: DOFs 0-3 are fixed zeros, which the slot's
-// last reader writes once it has read (the same lane: its LDS operations execute in order), so the row is whole
-// before the tile is stored.  The row pitch is odd: four b32 accesses, conflict-free, not one b128.
+// The hand-over slot of a frame (FULL_BODY_POS and UPPER_BODY: R10 left -> right wave) is the first four dwords of
+// the frame's own DOF row: DOFs 0-3 are fixed zeros, which the slot's reader writes once it has read (the same lane:
+// its LDS operations execute in order), so the row is whole before the tile is stored; the left wave writes nothing
+// there after its signal.  The row pitch is odd: four b32 accesses, conflict-free, not one b128.
 constexpr int kSlotDwords = 4;
 RTG_DEV void slot_put(float *row, Q q) { row[0] = q.x; row[1] = q.y; row[2] = q.z; row[3] = q.w; }
 RTG_DEV Q slot_get(const float *row) { return Q{row[0], row[1], row[2], row[3]}; }
@@ -533,14 +511,15 @@ __global__ __launch_bounds__(kSideThreads, (side_min_waves<KIND, SOA>())) void k
     auto TS = [](int) {};
 #endif
     uint32_t st = 0;   // this wave's status bits for its frame (the side kernel keeps per-step flags: lane masks)
-    bool fit1_nan = false, fit2_nan = false, euler_refused = false;
+    bool torso_nan = false, wrist_nan = false, euler_refused = false;
     if constexpr (KIND == RTG_SOLVER_FULL_BODY_POS) {
-        // Balanced FULL_BODY_POS: left wave = torso fit, then the left wrist fit, then the left Euler split /
-        // gripper; right wave = the right wrist fit, then BOTH arm chains (each needs only R10), then the right
-        // Euler split / gripper -- 1.5 SVD-equivalents per wave.  Two per-tile LDS flags hand R10 (left -> right)
-        // and the left chain (right -> left) over, so each wave waits only for what it reads; a third counts the
-        // waves out, and the second one to finish stores the tile's DOF rows while the first exits.
-        __shared__ int sflag[kSideTiles][4];   // per tile: [0] R10 ready, [1] left chain ready, [2] waves done, [3] unused (pitch)
+        // FULL_BODY_POS: after the torso fit each wave runs its own side's whole program -- wrist fit, arm chain (it
+        // needs only R10), Euler split, gripper, read-out -- and that program is written once: the side is a
+        // wave-uniform scalar that selects the zero-pose constants, the input rows and where the results go (the
+        // selects below).  The left wave fits the torso first and hands R10 over through the row's slot and one per-tile LDS
+        // flag; the right wave fits its wrist meanwhile and waits for the flag only then.  A second flag word counts
+        // the waves out, and the second one to finish stores the tile's DOF rows while the first exits.
+        __shared__ int sflag[kSideTiles][4];   // per tile: [0] R10 ready, [2] waves done, [1] / [3] unused (pitch)
         if (threadIdx.x < 4 * kSideTiles) (&sflag[0][0])[threadIdx.x] = 0;
         // the near-unit normalisation table (rtg_math.cuh), per site: 1 the fits' quaternions, 2 the arm maps'
         // angle-axis quaternions, 4 the Euler split's products (RTG_SIDES_UNIT_TAB for SoA, _AOS for AoS)
@@ -554,121 +533,85 @@ __global__ __launch_bounds__(kSideThreads, (side_min_waves<KIND, SOA>())) void k
         const auto tabE = TabSel<(kTab & 4) != 0>::get(sut);
         __syncthreads();
         int *const fl = sflag[w >> 1];
-        auto hook1 = [&](int k) { if (k < 2) TS(1 + k); };    // 1: first fit's A formed (its points loaded), 2: its SVD + R done
-        auto hook2 = [&](int k) { if (k < 2) TS(10 + k); };   // 10 / 11: the same for the left wave's second fit
+        auto hookT = [&](int k) { if (k < 2) TS(1 + k); };   // the torso fit -- 1: A formed (its points loaded), 2: SVD + R done
+        // the wrist fit: the right wave's first fit (1 / 2), the left wave's second (10 / 11)
+        auto hookW = [&](int k) { if (k < 2) TS((side ? 1 : 10) + k); };
         TS(0);
         const auto b = view(in0, 63);
+        // The side's selects, all scalar.  The right side's links, DOF columns and stash slots are the left side's, 9
+        // links and 7 slots on, with the same Hu_DOF_AXIS pattern: the program below names the left side's links and
+        // runs on an emitter that carries the shift.  E itself keeps the row's slot and the fixed links.
+        static_assert(Emit::slot<21>() - Emit::slot<12>() == 7 && side_links_alike(12, 21, 7), "the sides' links differ");
+        const Emit ES = E.shifted(side ? 9 : 0, side ? 7 : 0);
+        V Z[5];   // the wrist fit's zero vectors
+#pragma unroll
+        for (int t = 0; t < 5; ++t) Z[t] = side ? C.Zr[t] : C.Zl[t];
+        const ArmZero zsh = side ? C.rsh : C.lsh, zel = side ? C.rel : C.lel;
+        const auto H = view(side ? in2 : in1, 60);   // the side's hand points
+        const int jsh = side ? 14 : 18;              // its shoulder row of the body points; elbow and wrist follow
         Q R10 = qident(), W = qident();
-        ArmPts apL{}, apR{};
         // AoS (RTG_AOS_PRELOAD_TIPS): the gripper's hand points load with the wrist fit's, while the hand row's lines
-        // are in the L2 -- loaded after the arm chains they come back from the MALL or HBM (AoS fetch 1.57x the rows)
+        // are in the L2 -- loaded after the arm chain they come back from the MALL or HBM (AoS fetch 1.57x the rows)
         constexpr bool kPreTips = RTG_AOS_PRELOAD_TIPS && !SOA;
         TipPts tpre{};
-        // RTG_SIDES_SHARED_FIT: each wave's first fit (left: torso, right: right wrist) forms its A, then both run ONE
-        // inlined copy of the SVD's code (the same operations on the same A as cal_joint_quat)
-        constexpr bool kSharedFit = RTG_SIDES_SHARED_FIT >= (SOA ? 1 : 2);
         // RTG_TORSO_X0: a zero pose whose torso vectors have x = 0 (C.torso_x0) takes the zero-column fit; a wave with
         // a lane off its path gets false back and runs the general fit (wave-uniform either way)
         constexpr bool kTorsoX0 = RTG_TORSO_X0 && !RTG_EXP_STUB_SVD;
-        if (live) {
-            if constexpr (kSharedFit) {
-                float A[9];
-                Q q = qident();
-                bool general = true;
-                if (!side) {
-                    const V b10 = b.p3(10);
-                    const V Mt[3] = {vsub(b.p3(17), b10), vsub(b.p3(13), b10), vsub(b.p3(11), b10)};
-                    if constexpr (kTorsoX0) {
-                        if (C.torso_x0) general = !torso_quat_x0(C.Zt, Mt, q, hook1, tabF);
-                    }
-                    if (general) fit1_nan = form_joint_A<3>(C.Zt, Mt, A);
-                } else {
-                    apL = load_arm<0>(b);
-                    apR = load_arm<1>(b);
-                    const auto H = view(in2, 60);
-                    if (kPreTips) tpre = load_tips(H);
-                    const V h0 = H.p3(0);
-                    const V M[5] = {vsub(H.p3(2), h0), vsub(H.p3(6), h0), vsub(H.p3(10), h0), vsub(H.p3(14), h0),
-                                    vsub(H.p3(17), h0)};
-                    fit1_nan = form_joint_A<5>(C.Zr, M, A);
-                }
-                if (general) q = joint_quat_of_A(A, hook1, tabF);
-                if (!side) {
-                    R10 = q;
-                    slot_put(E.row, R10);
-                } else {
-                    W = q;
-                }
-            } else {
-                bool nan = false;
-                if (!side) {
-                    bool general = true;
-                    if constexpr (kTorsoX0) {
-                        if (C.torso_x0) {
-                            const V b10 = b.p3(10);
-                            const V Mt[3] = {vsub(b.p3(17), b10), vsub(b.p3(13), b10), vsub(b.p3(11), b10)};
-                            general = !torso_quat_x0(C.Zt, Mt, R10, hook1, tabF);
-                        }
-                    }
-                    if (general) R10 = fbp_torso(C, b, nan, hook1, tabF);
-                    slot_put(E.row, R10);
-                    fit1_nan = nan;
-                } else {
-                    apL = load_arm<0>(b);
-                    apR = load_arm<1>(b);
-                    if (kPreTips) tpre = load_tips(view(in2, 60));
-                    W = fbp_wrist_fit<1>(C, view(in2, 60), nan, hook1, tabF);
-                    fit1_nan = nan;
-                }
-            }
-        }
-        TS(3);
+        // the wave's own arm points, loaded at kernel start with the first fit's rows (measured -4 %: DESIGN.md §5)
+        ArmPts ap{};
+        if (live) ap = ArmPts{b.p3(jsh), b.p3(jsh + 1), b.p3(jsh + 2)};
         if (!side) {
+            if (live) {
+                const V b10 = b.p3(10);
+                const V Mt[3] = {vsub(b.p3(17), b10), vsub(b.p3(13), b10), vsub(b.p3(11), b10)};
+                bool general = true;
+                if constexpr (kTorsoX0) {
+                    if (C.torso_x0) general = !torso_quat_x0(C.Zt, Mt, R10, hookT, tabF);
+                }
+                // the fallback: the kernel's second copy of the SVD's code, cold for the shipped zero pose
+                if (general) R10 = cal_joint_quat<3>(C.Zt, Mt, torso_nan, hookT, tabF);
+                slot_put(E.row, R10);
+            }
+            TS(3);
             // R10 of this tile is in the rows' slots.  RTG_EXP_SKIP_SIGNAL (measurement knob): block 0's first tile never
             // raises it, so its right wave times out -- the error-word report is tested on that build
             if (!(RTG_EXP_SKIP_SIGNAL && blockIdx.x == 0 && w == 0)) lds_signal(&fl[0]);
-        } else {
-            lds_wait(&fl[0], C.err);
+            TS(4);
+            if (live) emit_fixed_links(E, true, kSlotDwords);   // the slot's dwords are the right wave's from the signal on
         }
-        TS(4);
-        Q chain = qident();
-        if (side) {
-            // both arm chains in one instruction stream (fbp_arms2), then the hand-over
-            if (live) {
-                R10 = slot_get(E.row);   // read R10 before the same lane overwrites the slot with the chain
-                Q cl;
-                fbp_arms2(C, apL, apR, R10, E, cl, chain, tabA);
-                slot_put(E.row, cl);
-            }
-            if (wds) Emit::wait_words();   // the left chain's table words (slots 0-3) have landed in LDS
-            lds_signal(&fl[1]);   // the left chain and its exp-map slots 0-3 are in LDS
-        } else if (live) {
-            emit_fixed_links(E, true, kSlotDwords);   // the slot's dwords stay the right wave's until the chain is read
-            bool nan = false;
-            if (kPreTips) tpre = load_tips(view(in1, 60));
-            W = fbp_wrist_fit<0>(C, view(in1, 60), nan, hook2, tabF);
-            fit2_nan = nan;
-        }
-        TS(5);
-        if (!side) lds_wait(&fl[1], C.err);
-        TS(6);
         if (live) {
-            float *brow = body_rot ? body_rot + f * 236 : nullptr;
-            const TipPts tp = kPreTips ? tpre : load_tips(view(side ? in2 : in1, 60));
-            if (side) {
-                euler_refused = fbp_side_after_arm<PRECISE, 1>(C, tp, R10, chain, W, E, brow, tabE);
-            } else {
-                const Q c = slot_get(E.row);   // the left chain; this lane was the slot's last reader: now its zeros
+            if (kPreTips) tpre = load_tips(H);
+            const V h0 = H.p3(0);
+            const V M[5] = {vsub(H.p3(2), h0), vsub(H.p3(6), h0), vsub(H.p3(10), h0), vsub(H.p3(14), h0), vsub(H.p3(17), h0)};
+            W = cal_joint_quat<5>(Z, M, wrist_nan, hookW, tabF);
+        }
+        if (side) {
+            TS(3);
+            lds_wait(&fl[0], C.err);
+            TS(4);
+            if (live) {
+                R10 = slot_get(E.row);   // this lane is the slot's only reader: now its zeros
                 slot_clear(E.row);
-                euler_refused = fbp_side_after_arm<PRECISE, 0>(C, tp, R10, c, W, E, brow, tabE);
+            }
+        }
+        if (live) {
+            // the side's arm chain from R10, then its Euler split (:128-136), gripper (:142-158 / :165-175), body_rot rows
+            const Q chain = solve_arm<12>(ES, vsub(ap.el, ap.sh), vsub(ap.wr, ap.el), zsh, zel, R10, tabA);
+            TS(5);
+            TS(6);
+            const TipPts tp = kPreTips ? tpre : load_tips(H);
+            euler_refused = emit_euler_xyz<16>(ES, qmul_norm(qconj(qmul_norm(R10, chain, tabE)), W, tabE));
+            fbp_gripper<PRECISE>(C, hand_x_mean(qconj(W), tp.h0, tp.t), ES.row + 18);
+            if (body_rot) {
+                float *brow = body_rot + f * 236;
+                if (side) fbp_body_rows<1>(brow, R10, W);
+                else fbp_body_rows<0>(brow, R10, W);
             }
         }
         TS(7);
-        // exp-map read-out: the left wave reads slots 0-6 (the left chain's 0-3, written by the right wave before
-        // the flag, and its own wrist's 4-6), the right wave 7-13 (all its own)
-        if (live) E.finalize(side ? 7 : 0, 7);
-        st = side ? ((fit1_nan ? kStRightSvd : 0u) | (euler_refused ? kStRightEuler : 0u))
-                  : ((fit1_nan ? kStTorsoSvd : 0u) | (fit2_nan ? kStLeftSvd : 0u) | (euler_refused ? kStLeftEuler : 0u));
+        if (live) ES.finalize(0, 7);   // the side's exp-map read-out: its own seven slots
+        st = side ? ((wrist_nan ? kStRightSvd : 0u) | (euler_refused ? kStRightEuler : 0u))
+                  : ((torso_nan ? kStTorsoSvd : 0u) | (wrist_nan ? kStLeftSvd : 0u) | (euler_refused ? kStLeftEuler : 0u));
         sstat[side][r] = (uint8_t)st;
         TS(8);
         // The tile's two waves meet at an LDS counter instead of the block barrier: the first to arrive exits (its

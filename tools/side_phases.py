@@ -4,10 +4,13 @@ Needs a build with -DRTG_EXP_TIMESTAMPS=1 (tools/build_variants.sh "ts:-DRTG_EXP
 RTG_LIB=humanoid-real-time-retarget_amd/variants/ts.so): lane 0 of each wave of every 8th block records the 100 MHz
 wall clock at the phase boundaries (rtg_solver.cuh, TS slots).  Prints, per wave side and per residency round, the
 median time of each phase (us) and the spread of block start / end times.
-Slots: 0 start, 1 first fit's points loaded + A formed, 2 its SVD + R done, 3 phase-1 done, 4 after the R10 hand-over
-(right wave: flag seen; left wave: flag raised), 5 phase-2 done (left: wrist fit; right: both arm chains), 6 after
-the left-chain hand-over, 7 Euler split + gripper done, 8 exp-map read-out done, 9 past the tile counter, 12 DOF tile
-stored; 10 / 11 the left wave's second fit (A, SVD).  The tile's two waves meet at an LDS counter: the first to
+Slots: 0 start, 1 first fit's points loaded + A formed, 2 its SVD + R done (left wave: the torso fit; right wave: its
+wrist fit), 3 phase-1 done, 4 after the R10 hand-over (right wave: flag seen; left wave: flag raised), 5 and 6 own arm
+chain done (since round 21 each wave runs its own side's chain and there is no second hand-over: the two coincide, so
+`phase2` is the left wave's wrist fit + arm chain or the right wave's arm chain, and `handover2` is 0; the numbering is
+kept so logs from before -- 5 phase-2 done with both chains on the right wave, 6 after the left-chain hand-over --
+still parse), 7 Euler split + gripper done, 8 exp-map read-out done, 9 past the tile counter, 12 DOF tile stored;
+10 / 11 the left wave's second fit, its wrist's (A, SVD).  The tile's two waves meet at an LDS counter: the first to
 arrive records 9 and 12 at once and exits (its "store" phase is 0), the second stores the tile's rows.  A slot a
 wave never recorded stays 0 and is masked out of the medians.
 Needs RTG_ALLOW_MEASUREMENT_BUILD=1 (RTG_EXP_TIMESTAMPS writes the clock into body_rot: a wrong-answer knob).
