@@ -802,7 +802,18 @@ RTG_DEV ExpDof exp_dof_word_part(float w, uint32_t word)
     const uint32_t code = in ? (word >> ((i - wd * kAngTabPer) * kAngTabBits)) & ((1u << kAngTabBits) - 1u) : 0u;
     return ExpDof{__uint_as_float(__float_as_uint(P) + code - kAngTabBias), sin_theta, mask, mask && code == 0u};
 }
-RTG_DEV float exp_dof_finish(const ExpDof &e, float qk) { return e.mask ? e.angle * (qk / e.sin_theta) : 0.0f; }
+// Round 22: the quotient runs bare (fdiv1, region [N]): where mask holds sin_theta
+// lies in (1e-5, 1], inside the window, and the numerator's test joins the batch's rare-case word (exp_dof_redo), whose
+// exact path divides as the compiler does.  Where mask fails the quotient is not read.
+RTG_DEV float fdiv1(float a, float b);   // with the Kabsch fits' divisions below
+RTG_DEV float exp_dof_finish(const ExpDof &e, float qk) { return e.mask ? e.angle * fdiv1(qk, e.sin_theta) : 0.0f; }
+// whether the read-out is to be redone on the exact path: the table says so, or qk is outside [2^-76, 2^47] (zeros,
+// -0 among them, NaN and inf included)
+RTG_DEV bool exp_dof_redo(const ExpDof &e, float qk)
+{
+    const float a = fabsf(qk);
+    return e.exact | (e.mask & !((a >= 0x1p-76f) & (a <= 0x1p47f)));
+}
 // the exact path of one read-out whose mask holds (w outside the table or a code-0 entry), out of line
 __device__ __attribute__((noinline)) float exp_dof_exact(float w, float qk)
 {
@@ -1014,6 +1025,55 @@ RTG_DEV void fdiv_n(const float (&a)[N], float b, float (&q)[N])
 #endif
 }
 RTG_DEV float la_sign(float a, float b) { return __builtin_copysignf(fabsf(a), b); }   // Fortran SIGN
+// ---- ONE IEEE f32 quotient through the bare sequence (round 22): fdiv1(a, b) is fdiv_n_bare<1>, RN(a / b) wherever
+// every step of it is one rounding in the normal range -- the scale argument above, which needs nothing of
+// v_div_scale's conditions except that they describe the compiler's sequence and not this one (both are RN(a / b)
+// there); they hold anyway in each region.  The caller owns the guard, and pays for it per GROUP of quotients:
+//   [W] the symmetric window: |a|, |b| in [2^-47, 2^47] (fdiv_n's).
+//   [N] narrow denominator, wide numerator: |b| in [2^-47, 2^47], |a| in [2^-76, 2^47] (kNumLo, kDivHi).  Below
+//       the window the numerator meets three edges: |a| >= 2^-103 (v_div_scale's last condition) and
+//       exponent(a) - exponent(b) > -126, i.e. a / b normal (its fifth), both implied by |a| >= 2^-78 under
+//       |b| <= 2^47; and the residual a - b t, a multiple of ulp(b) ulp(t) >= 2^-48 |a|, normal: |a| >= 2^-78 again.
+//       kNumLo = 2^-76 keeps two binades of margin.  y, fma(-b, y, 1) are as in [W]; t and q are at least 2^-124.
+//   [C] a constant denominator c in [1, 8): [N] with the wider numerator range [2^-76, 2^94], since the exponent
+//       difference stays under 96 and the quotient under 2^95 (fdiv1_const: the refined reciprocal is a constant too).
+// A numerator of +0 gives +0 through the bare sequence (t = 0, the residual 0), which is RN(0 / b) for b > 0; -0
+// would come out +0, so a zero numerator is admitted only where it is an absolute value or b's sign is its own.
+// NaN in, NaN out (either operand), as a / b; +-inf must fail the guard (inf y - inf).  tools/check_fdiv1.hip
+// `single` checks each region's edges on the device against a / b.
+constexpr float kNumLo = 0x1p-76f;
+RTG_DEV float fdiv1(float a, float b)
+{
+    const float num[1] = {a};
+    float q[1];
+    fdiv_n_bare<1>(num, b, q);
+    return q[0];
+}
+RTG_DEV bool fdiv1_in_n(float a, float b)   // region [N] (which contains [W])
+{
+    const float aa = fabsf(a);
+    return fdiv_in_window(b) & (aa >= kNumLo) & (aa <= kDivHi);
+}
+constexpr float kConstNumHi = 0x1p94f;
+RTG_DEV bool fdiv1_in_c(float a)            // region [C]'s numerators
+{
+    const float aa = fabsf(a);
+    return (aa >= kNumLo) & (aa <= kConstNumHi);
+}
+// a / c for the constant c in [1, 8) with y = the refined reciprocal of c (RN(1 / c) where that is its own
+// refinement), on region [C]'s numerators
+RTG_DEV float fdiv1_const(float a, float c, float y)
+{
+    const float t = a * y;
+    return __builtin_fmaf(__builtin_fmaf(-c, t, a), y, t);
+}
+// a / b as the build divides it behind a group's guard: the bare sequence (the guard holds) or the compiler's
+template <bool BARE>
+RTG_DEV float fdiv_g(float a, float b)
+{
+    if constexpr (BARE) return fdiv1(a, b);
+    else return a / b;
+}
 RTG_DEV float la_lapy2(float x, float y)                                                 // SLAPY2
 {
     const float xa = fabsf(x), ya = fabsf(y);
@@ -1021,9 +1081,18 @@ RTG_DEV float la_lapy2(float x, float y)                                        
     const float r = fdiv(z, w);
     return z == 0.0f ? w : w * la_sqrt_nt(1.0f + r * r);   // 1 + r^2 >= 1 (or NaN): not tiny
 }
+// SLAPY2 for w = max(|x|, |y|) in [2^-47, 2^47] and z = min(|x|, |y|) anything from +0 up: z >= 2^-76 is region [N];
+// below it z / w < 2^-29 and the bare sequence returns at most 2 z / w (t = RN(z y), a residual of at most 2 z), so
+// 1 + r^2 rounds to 1 either way and the value is w, as SLAPY2's.  z = 0 is selected away as before.
+RTG_DEV float la_lapy2_bare(float xa, float ya)   // xa = |x|, ya = |y|
+{
+    const float w = fmaxf(xa, ya), z = fminf(xa, ya);
+    const float r = fdiv1(z, w);
+    return z == 0.0f ? w : w * la_sqrt_nt(1.0f + r * r);
+}
 // SLARFG(n, alpha, x): n = 3 (x = x0, x1) or n = 2 (x = x0); returns tau, updates alpha (= beta) and x
 template <int NX>
-RTG_DEV float la_larfg(float &alpha, float &x0, float &x1)
+RTG_DEV float la_larfg_ieee(float &alpha, float &x0, float &x1)
 {
     const float safmin = 1.17549435e-38f / 5.96046448e-08f, rsafmn = 1.0f / safmin;
     float xn = NX == 1 ? fabsf(x0) : la_lapy2(x0, x1);
@@ -1048,6 +1117,39 @@ RTG_DEV float la_larfg(float &alpha, float &x0, float &x1)
     for (int j = 0; j < knt; ++j) beta *= safmin;
     alpha = beta;
     return tau;
+}
+template <int NX>
+RTG_DEV bool la_larfg_ok(float alpha, float x0, float x1)   // the reflector's test (la_larfg)
+{
+    const float xa0 = fabsf(x0), w = NX == 1 ? xa0 : fmaxf(xa0, fabsf(x1));
+    return (w >= 0x1p-46f) & (w <= 0x1p45f) & (fabsf(alpha) <= 0x1p45f);
+}
+// S1 false: the caller knows the tests would refuse (the general three-point fit, cal_joint_quat) and keeps a / b
+template <int NX, bool S1 = true>
+RTG_DEV float la_larfg(float &alpha, float &x0, float &x1)
+{
+#if RTG_FIT_FAST_DIV_TU
+    if constexpr (!S1) return la_larfg_ieee<NX>(alpha, x0, x1);
+    // One test per reflector (round 22), in place of SLARFG's own two (xn == 0, |beta| < safmin: it implies neither
+    // holds): w = max |x_i| in [2^-46, 2^45] and |alpha| <= 2^45.  Then xn = SLAPY2(x) lies in [w, sqrt(2) w], inside
+    // the window, so la_lapy2_bare holds for it and for SLAPY2(alpha, xn), whose larger operand is at least xn;
+    // |beta| lies in [2^-46, sqrt(3) 2^45] and, beta and alpha having opposite signs, |beta - alpha| = |beta| + |alpha|
+    // in [2^-46, 2^47): both quotients below are in region [W].  NaN or inf in alpha fails the second comparison,
+    // inf in x the first; a NaN in x is dropped by SLAPY2's max / min exactly as in the reference form.  A lane the
+    // test refuses takes SLARFG as it was, behind the same one branch.
+    if (__builtin_expect(!la_larfg_ok<NX>(alpha, x0, x1), 0)) return la_larfg_ieee<NX>(alpha, x0, x1);
+    const float xa0 = fabsf(x0);
+    const float xn = NX == 1 ? xa0 : la_lapy2_bare(xa0, fabsf(x1));
+    const float beta = -__builtin_copysignf(la_lapy2_bare(fabsf(alpha), xn), alpha);
+    const float tau = fdiv1(beta - alpha, beta);
+    const float sc = fdiv1(1.0f, alpha - beta);
+    x0 *= sc;
+    if (NX == 2) x1 *= sc;
+    alpha = beta;
+    return tau;
+#else
+    return la_larfg_ieee<NX>(alpha, x0, x1);
+#endif
 }
 RTG_DEV void la_lartg(float f, float g, float &c, float &s, float &r)   // SLARTG (LAPACK >= 3.10)
 {
@@ -1104,6 +1206,13 @@ RTG_DEV void la_lartg(float f, float g, float &c, float &s, float &r)   // SLART
         }
     }
 }
+// BARE (round 22): the caller (la_bdsqr3's per-pass test) holds |f|, |g|, |h| in kStLo .. kStHi = [2^-46, 2^46], and
+// every quotient below runs bare with no test of its own.  By denominator: fhmx, and ga where ga >= fhmx, are state
+// values, in the window; so are the numerators fhmn, ga and fhmx (region [W]; fhmx / ga >= 2^-92 is never 0).
+// fhmx - fhmn is +0 (a difference of absolute values, fhmx >= fhmn) or at least ulp(fhmn) >= 2^-69 (region [N]).  The
+// two sums of roots are plain numbers: as = 1 + fhmn / fhmx in [1, 2], at <= 1, au < 1 in the first form, so the sum
+// lies in [1, sqrt 5 + sqrt 2]; p = as au <= 2 and q <= 1 in the second, so it lies in [2, sqrt 5 + sqrt 2].
+template <bool BARE = false>
 RTG_DEV float la_las2_min(float f, float g, float h)   // SLAS2, SSMIN only (the shift)
 {
     const float fa = fabsf(f), ga = fabsf(g), ha = fabsf(h);
@@ -1112,22 +1221,24 @@ RTG_DEV float la_las2_min(float f, float g, float h)   // SLAS2, SSMIN only (the
     if (ga < fhmx) {
         const float num[3] = {fhmn, fhmx - fhmn, ga};
         float quo[3];
-        fdiv_n<3>(num, fhmx, quo);
+        if constexpr (BARE) fdiv_n_bare<3>(num, fhmx, quo);
+        else fdiv_n<3>(num, fhmx, quo);
         const float as = 1.0f + quo[0], at = quo[1];
         float au = quo[2];
         au = au * au;
         // as >= 1 (the quotient is >= 0), so as^2 + au >= 1: not tiny.  at^2 + au can be (at = 0, au tiny): cr_sqrt
-        const float c = fdiv(2.0f, la_sqrt_nt(as * as + au) + la_sqrt(at * at + au));
+        const float c = fdiv_g<BARE>(2.0f, la_sqrt_nt(as * as + au) + la_sqrt(at * at + au));
         return fhmn * c;
     }
-    const float au = fdiv(fhmx, ga);
+    const float au = fdiv_g<BARE>(fhmx, ga);
     if (au == 0.0f) return fdiv(fhmn * fhmx, ga);
     const float num[2] = {fhmn, fhmx - fhmn};
     float quo[2];
-    fdiv_n<2>(num, fhmx, quo);
+    if constexpr (BARE) fdiv_n_bare<2>(num, fhmx, quo);
+    else fdiv_n<2>(num, fhmx, quo);
     const float as = 1.0f + quo[0], at = quo[1], p = as * au, q = at * au;
     // 1 + p^2 and 1 + q^2 are >= 1 (or NaN): not tiny
-    const float c = fdiv(1.0f, la_sqrt_nt(1.0f + p * p) + la_sqrt_nt(1.0f + q * q));
+    const float c = fdiv_g<BARE>(1.0f, la_sqrt_nt(1.0f + p * p) + la_sqrt_nt(1.0f + q * q));
     const float mn = (fhmn * c) * au;
     return mn + mn;
 }
@@ -1297,19 +1408,112 @@ RTG_DEV void la_bdsqr3_sort(float &d1, float &d2, float &d3, Svd3 &z)
 // chase (IDIR = 2) is the top-to-bottom chase (IDIR = 1) of the reversed bidiagonal (d3, d2, d1; e2, e1) -- the
 // same scalar recurrences, with the rotations applied to the mirrored row / column pairs and negated sines
 // (SBDSQR :130/:150 store -SN) -- so both directions run one code path and a wave never executes both.
-RTG_DEV void la_bdsqr3(float &d1, float &d2, float &d3, float e1, float e2, Svd3 &z)
+//
+// The single quotients of SBDSQR's bookkeeping run bare behind ONE test of the bidiagonal per group (round 22): the
+// entry's three, and each pass's (the mu chain, smin / smax, SLAS2's, shift / sll).  The test: all of |d1..3|, |e1|,
+// |e2| in [kStLo, kStHi] = [2^-46, 2^46], a min chain next to the max chain smax already is.  What follows from it,
+// per quotient (regions as named at fdiv1):
+//   mu / (mu + |e|), first link: mu = |d1| and the sum, at most 2^47, are in the window [W].  Second link: the sum is
+//     in [2^-46, 2^47]; mu = |d2| q1 can be far below the state.  mu >= kNumLo is region [N].  Below that the exact
+//     quotient is under 2^-76 / 2^-46 = 2^-30 and the bare one at most twice it (t = RN(mu y), a residual of at most
+//     2 mu): at the ENTRY the value matters (thresh), so the entry tests its final sminoa >= kNumLo, which bounds both
+//     links' numerators and the constant division's from below; in a PASS the second link feeds only smin, and
+//   smin / smax is read by one comparison, against 1 / 30: smin >= kNumLo is region [N] (smax is a state value);
+//     under it both the exact and the bare quotient are below 2^-29, and so is any quotient formed from a second
+//     link that was itself below 2^-30 -- the comparison reads the same.  No test beyond the state's.
+//   SLAS2: see la_las2_min.
+//   shift / sll: sll = |D1| is a state value and 0 <= shift <= 2^46 (shift = +0 gives +0).  The quotient is read by
+//     q q < eps alone.  q q >= eps needs shift >= 2^-12 sll >= 2^-58: region [N]; below kNumLo the exact q is under
+//     2^-30, the bare one under 2^-29, and the shift is zeroed.  (The sweep's own shift / D1 is left as it was.)
+// inf fails the max test.  A NaN passes the chains (max / min keep the other operand) and makes NaN of every
+// quotient it enters in either form.  A lane whose state fails takes the group in the compiler's a / b form.
+constexpr float kStLo = 0x1p-46f, kStHi = 0x1p46f;
+constexpr float kSqrt3 = 1.73205078f, kRcpSqrt3 = 0x1.279a74p-1f;   // sqrt(real(3)); RN(1 / kSqrt3), its own refinement
+// SBDSQR's sminoa before its division by sqrt(3)
+template <bool BARE>
+RTG_DEV float la_bdsqr3_sminoa(float d1, float d2, float d3, float e1, float e2)
 {
-    const float eps = 5.96046448e-08f, tol = 10.0f * eps, unfl = 1.17549435e-38f;
     float sminoa = fabsf(d1);
     if (sminoa != 0.0f) {
-        float mu = fabsf(d2) * fdiv(sminoa, sminoa + fabsf(e1));
+        float mu = fabsf(d2) * fdiv_g<BARE>(sminoa, sminoa + fabsf(e1));
         sminoa = fminf(sminoa, mu);
         if (sminoa != 0.0f) {
-            mu = fabsf(d3) * fdiv(mu, mu + fabsf(e2));
+            mu = fabsf(d3) * fdiv_g<BARE>(mu, mu + fabsf(e2));
             sminoa = fminf(sminoa, mu);
         }
     }
-    sminoa = fdiv(sminoa, 1.73205078f);   // / sqrt(real(3))
+    return sminoa;
+}
+// One pass over the block (1, 3) in chase order: SBDSQR's convergence tests, and for a lane that sweeps (zero = 0)
+// the shift.  zero = 1, 2: E1, E2 is negligible; the caller zeroes it and the lane is done with
+// this pass.  Returned by value: nothing here is stored through a pointer, so every value stays in a register.
+struct BdsqrPass { int zero; float shift; };
+template <bool BARE>
+RTG_DEV BdsqrPass la_bdsqr3_shift(float D1, float D2, float D3, float E1, float E2, float smax)
+{
+    const float eps = 5.96046448e-08f, tol = 10.0f * eps;
+    BdsqrPass p{0, 0.0f};
+    if (fabsf(E2) <= fabsf(tol) * fabsf(D3)) p.zero = 2;
+    else {
+        float mu = fabsf(D1), smin = mu;
+        if (fabsf(E1) <= tol * mu) p.zero = 1;
+        else {
+            mu = fabsf(D2) * fdiv_g<BARE>(mu, mu + fabsf(E1));
+            smin = fminf(smin, mu);
+            if (fabsf(E2) <= tol * mu) p.zero = 2;
+            else {
+                mu = fabsf(D3) * fdiv_g<BARE>(mu, mu + fabsf(E2));
+                smin = fminf(smin, mu);
+                if (!((3.0f * tol) * fdiv_g<BARE>(smin, smax) <= fmaxf(eps, 0.01f * tol))) {
+                    const float sll = fabsf(D1), sh = la_las2_min<BARE>(D2, E2, D3);
+                    const float q = fdiv_g<BARE>(sh, sll);   // sll > 0 where BARE: a state value; else unread
+                    p.shift = ((BARE || sll > 0.0f) && q * q < eps) ? 0.0f : sh;
+                }
+            }
+        }
+    }
+    return p;
+}
+// the state's test; smax: the max of the five magnitudes
+RTG_DEV bool la_bdsqr3_state_ok(float D1, float D2, float D3, float E1, float E2, float smax)
+{
+    const float smn = fminf(fminf(fabsf(D3), fminf(fabsf(D2), fabsf(E2))), fminf(fabsf(D1), fabsf(E1)));
+    return (smn >= kStLo) & (smax <= kStHi);
+}
+RTG_DEV float la_bdsqr3_smax(float D1, float D2, float D3, float E1, float E2)
+{
+    // max over a set (a NaN only ever yields to the other operand): the same value in either order
+    return fmaxf(fmaxf(fabsf(D3), fmaxf(fabsf(D2), fabsf(E2))), fmaxf(fabsf(D1), fabsf(E1)));
+}
+// the pass behind the state's test
+template <bool S1 = true>
+RTG_DEV BdsqrPass la_bdsqr3_pass(float D1, float D2, float D3, float E1, float E2, float smax)
+{
+#if RTG_FIT_FAST_DIV_TU
+    if (S1 && __builtin_expect(la_bdsqr3_state_ok(D1, D2, D3, E1, E2, smax), 1)) return la_bdsqr3_shift<true>(D1, D2, D3, E1, E2, smax);
+#endif
+    return la_bdsqr3_shift<false>(D1, D2, D3, E1, E2, smax);
+}
+// SBDSQR's sminoa / sqrt(real(3)) behind the state's test and the one on its own numerator
+template <bool S1 = true>
+RTG_DEV float la_bdsqr3_entry(float d1, float d2, float d3, float e1, float e2)
+{
+#if RTG_FIT_FAST_DIV_TU
+    if constexpr (!S1) return fdiv(la_bdsqr3_sminoa<false>(d1, d2, d3, e1, e2), kSqrt3);
+    const float s = la_bdsqr3_sminoa<true>(d1, d2, d3, e1, e2);
+    const bool ok = la_bdsqr3_state_ok(d1, d2, d3, e1, e2, la_bdsqr3_smax(d1, d2, d3, e1, e2)) & (s >= kNumLo);
+    float q = fdiv1_const(s, kSqrt3, kRcpSqrt3);
+    if (__builtin_expect(!ok, 0)) q = fdiv(la_bdsqr3_sminoa<false>(d1, d2, d3, e1, e2), kSqrt3);
+    return q;
+#else
+    return fdiv(la_bdsqr3_sminoa<false>(d1, d2, d3, e1, e2), kSqrt3);
+#endif
+}
+template <bool S1 = true>
+RTG_DEV void la_bdsqr3(float &d1, float &d2, float &d3, float e1, float e2, Svd3 &z)
+{
+    const float eps = 5.96046448e-08f, tol = 10.0f * eps, unfl = 1.17549435e-38f;
+    const float sminoa = la_bdsqr3_entry<S1>(d1, d2, d3, e1, e2);
     const float thresh = fmaxf(tol * sminoa, 6.0f * (3.0f * (3.0f * unfl)));
     int m = 3, iter = -1, iterdivn = 0;
     // mir: IDIR = 2.  SBDSQR picks the direction when (ll, m) = (1, 3) is new, from |d1| >= |d3|; nothing changes d
@@ -1343,33 +1547,13 @@ RTG_DEV void la_bdsqr3(float &d1, float &d2, float &d3, float e1, float e2, Svd3
         else if (fabsf(e2t) <= thresh) m = 2;
         else if (fabsf(e1t) <= thresh) { blk = true; p1 = true; run = false; }   // split at E(1): block (2, 3)
         else {
-            // max over a set (a NaN only ever yields to the other operand): the same value in either order
-            const float smax = fmaxf(fmaxf(fabsf(D3), fmaxf(fabsf(D2), fabsf(E2))), fmaxf(fabsf(D1), fabsf(E1)));
-            bool zeroed = false;
-            float smin;
-            if (fabsf(E2) <= fabsf(tol) * fabsf(D3)) { E2 = 0.0f; zeroed = true; }
-            else {
-                float mu = fabsf(D1);
-                smin = mu;
-                if (fabsf(E1) <= tol * mu) { E1 = 0.0f; zeroed = true; }
-                else {
-                    mu = fabsf(D2) * fdiv(mu, mu + fabsf(E1));
-                    smin = fminf(smin, mu);
-                    if (fabsf(E2) <= tol * mu) { E2 = 0.0f; zeroed = true; }
-                    else {
-                        mu = fabsf(D3) * fdiv(mu, mu + fabsf(E2));
-                        smin = fminf(smin, mu);
-                    }
-                }
-            }
-            if (!zeroed) {   // a zeroed lane is done with this pass (its e is already in place)
-                sweep = true;
-                if (!((3.0f * tol) * fdiv(smin, smax) <= fmaxf(eps, 0.01f * tol))) {
-                    const float sll = fabsf(D1);
-                    shift = la_las2_min(D2, E2, D3);
-                    if (sll > 0.0f) { const float q = fdiv(shift, sll); if (q * q < eps) shift = 0.0f; }
-                }
-            }
+            const float smax = la_bdsqr3_smax(D1, D2, D3, E1, E2);
+            // a lane with a zeroed e is done with this pass (sweep stays false)
+            const BdsqrPass ps = la_bdsqr3_pass<S1>(D1, D2, D3, E1, E2, smax);
+            E1 = ps.zero == 1 ? 0.0f : E1;
+            E2 = ps.zero == 2 ? 0.0f : E2;
+            sweep = ps.zero == 0;
+            shift = ps.shift;
         }
         if (sweep) {
             iter += 2;
@@ -1454,10 +1638,11 @@ struct NoHook {
 };
 // SGEBD2 after H_0: G_0 from the right (v = (1, a6)), then i = 1: H_1 from the left (v = (1, a5)) on column 2;
 // G_1 = I (one-element reflector), i = 2: H_2 = I
+template <bool S1 = true>
 RTG_DEV void la_gebd2_rest(float a[9], float &tp0, float &tq1, float &e1, float &d2, float &e2, float &d3)
 {
     float dum = 0.0f;
-    tp0 = la_larfg<1>(a[3], a[6], dum);
+    tp0 = la_larfg<1, S1>(a[3], a[6], dum);
     e1 = a[3];
     if (tp0 != 0.0f) {
         const float tv1 = -(tp0 * 1.0f), tv2 = -(tp0 * a[6]);
@@ -1469,7 +1654,7 @@ RTG_DEV void la_gebd2_rest(float a[9], float &tp0, float &tq1, float &e1, float 
         }
     }
     // i = 1: H_1 from the left (v = (1, a5)) on column 2; G_1 = I (one-element reflector)
-    tq1 = la_larfg<1>(a[4], a[5], dum);
+    tq1 = la_larfg<1, S1>(a[4], a[5], dum);
     d2 = a[4];
     if (tq1 != 0.0f) {
         const float w = a[7] + a[8] * a[5];
@@ -1515,7 +1700,7 @@ RTG_DEV void la_ormbr3(const float a[9], float tq0, float tq1, float tp0, Svd3 &
     }
 }
 // SGESDD(JOBZ='A') of a 3x3 (column-major a, overwritten): U and VT (column-major) in z
-template <typename Hook = NoHook>
+template <bool S1 = true, typename Hook = NoHook>
 RTG_DEV void la_gesdd3(float a[9], Svd3 &z, const Hook &hook = Hook{})
 {
     const float smlnum = 9.09494702e-13f, bignum = 1.0f / smlnum;   // sqrt(slamch('S')) / slamch('P') = 2^-40
@@ -1528,7 +1713,7 @@ RTG_DEV void la_gesdd3(float a[9], Svd3 &z, const Hook &hook = Hook{})
         for (int i = 0; i < 9; ++i) a[i] *= mul;
     }
     // SGEBD2, i = 0: H_0 from the left (v = (1, a1, a2)), G_0 from the right (v = (1, a6))
-    const float tq0 = la_larfg<2>(a[0], a[1], a[2]);
+    const float tq0 = la_larfg<2, S1>(a[0], a[1], a[2]);
     const float d1 = a[0];
     if (tq0 != 0.0f) {
 #pragma unroll
@@ -1541,13 +1726,13 @@ RTG_DEV void la_gesdd3(float a[9], Svd3 &z, const Hook &hook = Hook{})
         }
     }
     float tp0, tq1, e1, d2, e2, d3;
-    la_gebd2_rest(a, tp0, tq1, e1, d2, e2, d3);
+    la_gebd2_rest<S1>(a, tp0, tq1, e1, d2, e2, d3);
     hook(10);
     // SBDSDC('U','I') -> SLASDQ -> SBDSQR with U = VT = I
 #pragma unroll
     for (int i = 0; i < 9; ++i) { z.u[i] = (i % 4 == 0) ? 1.0f : 0.0f; z.vt[i] = z.u[i]; }
     float s1 = d1, s2 = d2, s3 = d3;
-    la_bdsqr3(s1, s2, s3, e1, e2, z);
+    la_bdsqr3<S1>(s1, s2, s3, e1, e2, z);
     hook(11);
     la_ormbr3(a, tq0, tq1, tp0, z);
 }
@@ -1643,7 +1828,7 @@ RTG_DEV void kabsch_of_svd(Svd3 &z, float R[9])
                 R[i * 3 + k] = (z.u[i] * z.vt[3 * k] + z.u[i + 3] * z.vt[1 + 3 * k]) + z.u[i + 6] * z.vt[2 + 3 * k];
     }
 }
-template <typename Hook = NoHook>
+template <bool S1 = true, typename Hook = NoHook>
 RTG_DEV void kabsch_rot(const float A[9], float R[9], const Hook &hook = Hook{})
 {
 #if RTG_EXP_STUB_SVD
@@ -1657,7 +1842,7 @@ RTG_DEV void kabsch_rot(const float A[9], float R[9], const Hook &hook = Hook{})
 #pragma unroll
         for (int k = 0; k < 3; ++k) a[i + 3 * k] = A[i * 3 + k];
     Svd3 z;
-    la_gesdd3(a, z, hook);
+    la_gesdd3<S1>(a, z, hook);
     kabsch_of_svd(z, R);
 }
 
@@ -1690,12 +1875,12 @@ RTG_DEV bool form_joint_A(const V (&Z)[N], const V (&M)[N], float (&A)[9])
     return nan;
 }
 // the rotation of a formed A: Kabsch then quat_from_rotation_matrix
-template <typename Hook = NoHook, typename Tab = NoTab>
+template <bool S1 = true, typename Hook = NoHook, typename Tab = NoTab>
 RTG_DEV Q joint_quat_of_A(const float (&A)[9], const Hook &hook = Hook{}, Tab tab = Tab{})
 {
     hook(0);
     float R[9];
-    kabsch_rot(A, R, hook);
+    kabsch_rot<S1>(A, R, hook);
     hook(1);
     return qfrom_rotmat(R, tab);
 }
@@ -1740,7 +1925,11 @@ RTG_DEV Q cal_joint_quat(const V (&Z)[N], const V (&M)[N], bool &svd_nan, const 
 {
     float A[9];
     svd_nan = form_joint_A<N>(Z, M, A);
-    return joint_quat_of_A(A, hook, tab);
+    // Round 22's single-quotient tests are for fits of more than three points.  In the units that have them the
+    // three-point fit is the torso's general path, whose matrix has an exactly zero column for the shipped zero poses
+    // (x = 0): d1 = 0, so every test would refuse and the fit would pay for them (measured: the upper-body solver
+    // 2 % slower with the tests).  It keeps a / b.
+    return joint_quat_of_A<N != 3>(A, hook, tab);
 }
 template <int N, typename Hook = NoHook>
 RTG_DEV Q cal_joint_quat(const V (&Z)[N], const V (&M)[N], const Hook &hook = Hook{})
@@ -2135,10 +2324,18 @@ RTG_DEV void elbow_py(V v1, ArmZero z0, Q parent, Q &yaw, Q &elbow, Tab tab = Ta
     arm_pair_1<false>(v1, z0, parent, yaw, elbow, tab);
 }
 
+// s / 5 (round 22): region [C] behind the numerator's test; RN(1 / 5) is its own refinement.  The sum is signed and
+// can be -0, which the test refuses with every other value under kNumLo
+RTG_DEV float fdiv_by5(float s)
+{
+    float q = fdiv1_const(s, 5.0f, 0x1.99999ap-3f);
+    if (__builtin_expect(!fdiv1_in_c(s), 0)) q = s / 5.0f;
+    return q;
+}
 // torch sum of 5 elements (cascade reduce order, measured) / 5
 RTG_DEV float mean5(float v0, float v1, float v2, float v3, float v4)
 {
-    return ((((v0 + v4) + v1) + v2) + v3) / 5.0f;
+    return fdiv_by5(((((v0 + v4) + v1) + v2) + v3));
 }
 
 // Hu_v5.Hu_DOF_AXIS (retarget/robot_config/Hu_v5.py:12-18), dof k <-> link k+1

@@ -77,7 +77,7 @@ struct Emit {
             if (j >= s0 && j < s0 + n) {
                 const float2 v = st[j * sst];
                 const ExpDof e = wd ? exp_dof_word_part(v.x, wd[j * 64 + (threadIdx.x & 63)]) : exp_dof_table_part(v.x, ang);
-                exact |= (uint32_t)e.exact << j;
+                exact |= (uint32_t)exp_dof_redo(e, v.y) << j;
                 row[j < 7 ? 11 + j : 13 + j] = exp_dof_finish(e, v.y);
             }
         if (__builtin_expect(exact != 0u, 0)) {
@@ -1010,7 +1010,7 @@ RTG_DEV void finalize_lanes(const Emit &E, int s0, int n)
         const float2 v = E.st[j * E.sst];
         const ExpDof e = exp_dof_table_part(v.x, E.ang);
         float val = exp_dof_finish(e, v.y);
-        if (__builtin_expect(e.exact, 0)) val = normalize_angle(2.0f * cr_acos(v.x)) * (v.y / e.sin_theta);
+        if (__builtin_expect(exp_dof_redo(e, v.y), 0)) val = normalize_angle(2.0f * cr_acos(v.x)) * (v.y / e.sin_theta);
         E.row[j < 7 ? 11 + j : 13 + j] = val;
     }
 }

@@ -5,6 +5,8 @@
 //   check_fdiv1 exhaustive [chunks]   the proof: every mantissa pair a, b in [1, 2) (2^46 pairs; `chunks` of 2^36 pairs,
 //                                      default all 1024), the reciprocal's scale invariance, and the read-out's root
 //   check_fdiv1 sampled               the quick form tests/test_gpu_fdiv_one_correction.py runs
+//   check_fdiv1 single                round 22's single quotients (tests/test_gpu_single_quotients.py): fdiv1 on its
+//                                      regions [N] and [C], and each converted site against its a / b form
 //
 // Why the mantissa pairs are the whole window (the argument next to fdiv_n_bare): for |a|, |b| in [2^-47, 2^47] the
 // sequence is  y = rcp(b); y = fma(fma(-b, y, 1), y, y); t = a y; q = fma(fma(-b, t, a), y, t)  in plain f32
@@ -23,6 +25,14 @@
 //  [2.k] sampled: every mantissa of b (2^23 each): in [1, 2) with hashed numerators; in the window's lowest binade;
 //       in its highest; in [1, 2) under the fixed numerator a = 0x3FB504F3 (and its neighbours as a1, a2)
 //  [3.k] sampled: round 13's nine families outside the window, 2^22 groups each: every group takes the fallback
+//  [N.k] single: fdiv1 behind fdiv1_in_n against a / b, every mantissa of b in the region's lowest binade, in [1, 2),
+//       in its highest binade, and in the binade below / above the region (k = 0 .. 4), each under 15 numerators: both
+//       numerator edges, one binade outside them, +-0, denormal, +-inf, NaN, and a hashed one inside
+//  [C.k] single: fdiv1_const behind fdiv1_in_c against a / c, every f32 a, c = sqrt(3) (la_bdsqr3_entry) and 5 (mean5).
+//       The gripper's a / C.orig is not converted (profiles/r22/single_quotients/sites.md): there is no third constant
+//  [G] [P] [T] [X] single: la_larfg<1>, <2>, la_bdsqr3_pass, la_bdsqr3_entry and the exp-map read-out against their
+//       a / b forms on 2^24 hashed operand sets each, scaled to sit inside, on and outside each test's edges
+//  In `single` a guard's verdict is compared with one worked out here from the bit patterns: "in-region" counts both.
 // Built with the library's arithmetic flags (csrc/Makefile check_fdiv1).
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -219,6 +229,184 @@ __global__ __launch_bounds__(256) void k_out(void)
     }
 }
 
+
+// ---- single: round 22's single quotients
+constexpr int kNFams = 5, kNCls = 15, kSites = 5;
+__device__ unsigned long long g_n_bad[kNFams], g_n_in[kNFams], g_n_want[kNFams], g_n_verdict[kNFams];
+__device__ unsigned long long g_c_bad[2], g_c_in[2], g_c_want[2], g_c_verdict[2], g_c_done[2];
+__device__ unsigned long long g_s_bad[kSites], g_s_in[kSites], g_s_verdict[kSites], g_s_done[kSites];
+__device__ __forceinline__ uint32_t absbits(float x) { return __float_as_uint(x) & 0x7FFFFFFFu; }
+constexpr uint32_t kBitsNumLo = (127u - 76u) << 23, kBitsDivLo = (127u - 47u) << 23, kBitsDivHi = (127u + 47u) << 23;
+constexpr uint32_t kBitsConstHi = (127u + 94u) << 23;
+// i = family * 2^23 + mantissa of b; families: b's binade 2^-47 (lowest), [1, 2), 2^46 (highest), 2^-48, 2^47 (outside)
+__global__ __launch_bounds__(256) void k_single_n(void)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t fam = i >> 23, mant = i & 0x7FFFFFu;
+    const uint32_t eb = fam == 0 ? 127u - 47u : fam == 1 ? 127u : fam == 2 ? 127u + 46u : fam == 3 ? 127u - 48u : 127u + 47u;
+    const uint64_t h0 = mix(0xD1Full + i);
+    const uint32_t ub = ((uint32_t)(h0 >> 63) << 31) | (eb << 23) | ((fam == 4 && mant == 0u) ? 1u : mant);
+    const float b = __uint_as_float(ub);
+    const bool b_in = fam < 3;
+    uint32_t nbad = 0, nin = 0, nwant = 0, nverdict = 0, ubad = 0;
+    for (int c = 0; c < kNCls; ++c) {
+        const uint64_t h = mix(h0 + 977ull * (uint64_t)(c + 1));
+        const uint32_t m = (uint32_t)h & 0x7FFFFFu, sg = (uint32_t)(h >> 40) << 31;
+        uint32_t ua;
+        bool a_in;
+        switch (c) {
+        case 0: ua = kBitsNumLo | m; a_in = true; break;                      // the lowest binade inside
+        case 1: ua = kBitsNumLo; a_in = true; break;                          // the lower edge
+        case 2: ua = kBitsNumLo - 1u; a_in = false; break;                    // its predecessor
+        case 3: ua = (kBitsNumLo - (1u << 23)) | m; a_in = false; break;      // one binade outside
+        case 4: ua = (kBitsDivHi - (1u << 23)) | m; a_in = true; break;       // the highest binade inside
+        case 5: ua = kBitsDivHi; a_in = true; break;                          // the upper edge
+        case 6: ua = kBitsDivHi + 1u; a_in = false; break;                    // its successor
+        case 7: ua = kBitsDivHi | (m | 1u); a_in = false; break;              // one binade outside
+        case 8: ua = 0u; a_in = false; break;
+        case 9: ua = 0x80000000u; a_in = false; break;
+        case 10: ua = m | 1u; a_in = false; break;                            // denormal
+        case 11: ua = 0x7F800000u; a_in = false; break;
+        case 12: ua = 0xFF800000u; a_in = false; break;
+        case 13: ua = 0x7FC00000u | (m >> 1); a_in = false; break;
+        default: ua = ((127u - 76u + (uint32_t)(h >> 24) % 123u) << 23) | m; a_in = true; break;   // 2^-76 .. 2^46
+        }
+        if (c <= 7 || c == 10 || c == 13 || c == 14) ua |= sg;
+        const float a = __uint_as_float(ua);
+        const bool in = fdiv1_in_n(a, b), want = a_in && b_in;
+        const float q = in ? fdiv1(a, b) : a / b;
+        nin += in;
+        nwant += want;
+        nverdict += in != want;
+        if (!same(q, a / b)) { ++nbad; ubad = ua; }
+    }
+    ran(C_RAND, kNCls);
+    atomicAdd(&g_n_in[fam], (unsigned long long)nin);
+    atomicAdd(&g_n_want[fam], (unsigned long long)nwant);
+    if (nverdict) atomicAdd(&g_n_verdict[fam], (unsigned long long)nverdict);
+    if (nbad) {
+        atomicAdd(&g_n_bad[fam], (unsigned long long)nbad);
+        first_bad(atomicAdd(&g_bad[C_RAND], (unsigned long long)nbad), ubad, 0u, 0u, ub);
+    }
+}
+// every f32 numerator under constant k: 0 sqrt(3) as la_bdsqr3_entry divides, 1 five as mean5 does
+__global__ __launch_bounds__(256) void k_single_c(uint32_t base, int k)
+{
+    const uint32_t u = base + blockIdx.x * blockDim.x + threadIdx.x;
+    const float a = __uint_as_float(u);
+    const bool in = fdiv1_in_c(a), want = absbits(a) >= kBitsNumLo && absbits(a) <= kBitsConstHi;
+    float q, ref;
+    if (k == 0) { q = in ? fdiv1_const(a, kSqrt3, kRcpSqrt3) : a / kSqrt3; ref = a / kSqrt3; }
+    else { q = fdiv_by5(a); ref = a / 5.0f; }
+    const unsigned long long nin = __popcll(__ballot(in)), nwant = __popcll(__ballot(want));
+    const unsigned long long nver = __popcll(__ballot(in != want)), nbad = __popcll(__ballot(!same(q, ref)));
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&g_c_done[k], 64ull);
+        atomicAdd(&g_c_in[k], nin);
+        atomicAdd(&g_c_want[k], nwant);
+        if (nver) atomicAdd(&g_c_verdict[k], nver);
+        if (nbad) atomicAdd(&g_c_bad[k], nbad);
+    }
+    if (!same(q, ref)) first_bad(atomicAdd(&g_bad[C_MANT], 1ull), u, 0u, 0u, (uint32_t)k);
+}
+// a hashed value whose exponent is e0 + (0 .. spread - 1), hashed sign and mantissa
+__device__ __forceinline__ float hval(uint64_t h, int e0, int spread)
+{
+    const int e = e0 + (int)((h >> 32) % (uint64_t)spread);
+    const uint32_t eb = (uint32_t)(e < -126 ? -126 : e > 127 ? 127 : e) + 127u;
+    return __uint_as_float(((uint32_t)(h >> 63) << 31) | (eb << 23) | ((uint32_t)h & 0x7FFFFFu));
+}
+// specials now and then: which = 0 none, else +-0, denormal, +-inf, NaN, 2^+-100
+__device__ __forceinline__ float special(float x, uint32_t which, uint32_t m)
+{
+    switch (which) {
+    case 1: return 0.0f;
+    case 2: return -0.0f;
+    case 3: return __uint_as_float((__float_as_uint(x) & 0x80000000u) | (m & 0x7FFFFFu) | 1u);
+    case 4: return __uint_as_float(0x7F800000u);
+    case 5: return __uint_as_float(0xFF800000u);
+    case 6: return __uint_as_float(0x7FC00000u);
+    case 7: return __builtin_copysignf(0x1p100f, x);
+    case 8: return __builtin_copysignf(0x1p-100f, x);
+    default: return x;
+    }
+}
+// the base exponents the hashed operand sets are scaled to: around -76, -47 / -46, 0 and 45 .. 47
+__device__ __forceinline__ int base_exp(uint32_t r)
+{
+    const int tab[16] = {-79, -77, -76, -75, -49, -48, -47, -46, -45, -20, 0, 20, 43, 44, 45, 46};
+    return tab[r & 15u];
+}
+// site 0, 1: la_larfg<1>, <2>; 2: la_bdsqr3_pass; 3: la_bdsqr3_entry; 4: the exp-map read-out
+__global__ __launch_bounds__(256) void k_single_sites(int site)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t h = mix(0x5173ull * (uint64_t)(site + 1) + i), h2 = mix(h ^ 0xABCDull), h3 = mix(h2 + 1ull);
+    const uint64_t h4 = mix(h3 + 2ull), h5 = mix(h4 + 3ull), h6 = mix(h5 + 4ull);
+    const int e0 = base_exp((uint32_t)(h6 >> 8));
+    // one operand in 16 sets is special in one place; spread: 0 .. 2 binades, or wide (tiny mu, tiny e, near rank 1)
+    const uint32_t sp = ((h6 >> 16) & 15u) == 0u ? 1u + (uint32_t)((h6 >> 20) % 8u) : 0u, where = (uint32_t)(h6 >> 24) % 5u;
+    const int spread = ((h6 >> 28) & 3u) == 0u ? 40 : 3;
+    float v[5] = {hval(h, e0, 3), hval(h2, e0, spread), hval(h3, e0, 3), hval(h4, e0, spread), hval(h5, e0, spread)};
+    v[where] = special(v[where], sp, (uint32_t)h6);
+    // one set in 32: all five denormal (a state the bare sequence cannot divide: v_rcp_f32 of a denormal sum), so a
+    // fallback that left part of its group bare would show
+    if (((h6 >> 40) & 31u) == 0u) {
+        const uint64_t hd[5] = {h, h2, h3, h4, h5};
+#pragma unroll
+        for (int k = 0; k < 5; ++k) v[k] = __uint_as_float(((uint32_t)(hd[k] >> 63) << 31) | ((uint32_t)hd[k] & 0x7FFFFFu) | 0x1000u);
+    }
+    bool in = false, want = false, bad = false;
+    if (site <= 1) {
+        float al = v[0], x0 = v[1], x1 = site ? v[3] : 0.0f, ar = al, y0 = x0, y1 = x1;
+        in = site ? la_larfg_ok<2>(al, x0, x1) : la_larfg_ok<1>(al, x0, x1);
+        // NaN in x is dropped by the max as in the site; the verdict here takes the larger bit pattern of the non-NaN
+        const uint32_t b0 = absbits(x0) > 0x7F800000u ? 0u : absbits(x0), b1 = absbits(x1) > 0x7F800000u ? 0u : absbits(x1);
+        const uint32_t w = site ? (b0 > b1 ? b0 : b1) : absbits(x0);
+        want = w >= ((127u - 46u) << 23) && w <= ((127u + 45u) << 23) && absbits(al) <= ((127u + 45u) << 23);
+        if (site == 0 && absbits(x0) > 0x7F800000u) want = false;
+        const float t = site ? la_larfg<2>(al, x0, x1) : la_larfg<1>(al, x0, x1);
+        const float tr = site ? la_larfg_ieee<2>(ar, y0, y1) : la_larfg_ieee<1>(ar, y0, y1);
+        bad = !same(t, tr) || !same(al, ar) || !same(x0, y0) || !same(x1, y1);
+    } else if (site == 2 || site == 3) {
+        const float smax = la_bdsqr3_smax(v[0], v[1], v[2], v[3], v[4]);
+        in = la_bdsqr3_state_ok(v[0], v[1], v[2], v[3], v[4], smax);
+        uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+        for (int k = 0; k < 5; ++k) {
+            const uint32_t u = absbits(v[k]);
+            if (u > 0x7F800000u) continue;   // a NaN passes the chains (see la_bdsqr3)
+            mn = u < mn ? u : mn;
+            mx = u > mx ? u : mx;
+        }
+        want = mn >= ((127u - 46u) << 23) && mx <= ((127u + 46u) << 23) && mx != 0u;
+        if (site == 2) {
+            const BdsqrPass p = la_bdsqr3_pass(v[0], v[1], v[2], v[3], v[4], smax);
+            const BdsqrPass r = la_bdsqr3_shift<false>(v[0], v[1], v[2], v[3], v[4], smax);
+            bad = p.zero != r.zero || !same(p.shift, r.shift);
+        } else {
+            bad = !same(la_bdsqr3_entry(v[0], v[1], v[2], v[3], v[4]), la_bdsqr3_sminoa<false>(v[0], v[1], v[2], v[3], v[4]) / kSqrt3);
+        }
+    } else {
+        // the read-out: sin_theta over (1e-5, 1] (and now and then under it: mask fails), qk scaled as a numerator
+        const float st = ((h6 >> 32) & 7u) == 0u ? hval(h2, -40, 30) : fabsf(hval(h2, -17, 18));
+        float qk = hval(h, e0, 3);
+        qk = special(qk, sp, (uint32_t)h6);
+        const ExpDof e{fabsf(hval(h3, -2, 3)), st, fabsf(st) > 1e-5f, false};
+        in = !exp_dof_redo(e, qk);
+        want = !e.mask || (absbits(qk) >= kBitsNumLo && absbits(qk) <= kBitsDivHi);
+        const float got = in ? exp_dof_finish(e, qk) : e.angle * (qk / e.sin_theta);
+        bad = !same(got, e.mask ? e.angle * (qk / e.sin_theta) : 0.0f);
+    }
+    const unsigned long long nin = __popcll(__ballot(in)), nver = __popcll(__ballot(in != want)), nbad = __popcll(__ballot(bad));
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&g_s_done[site], 64ull);
+        atomicAdd(&g_s_in[site], nin);
+        if (nver) atomicAdd(&g_s_verdict[site], nver);
+        if (nbad) atomicAdd(&g_s_bad[site], nbad);
+    }
+    if (bad) first_bad(atomicAdd(&g_bad[C_OUT], 1ull), __float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), (uint32_t)site);
+}
+
 static bool sync_ok(const char *what)
 {
     const hipError_t e = hipDeviceSynchronize(), l = hipGetLastError();
@@ -327,6 +515,66 @@ static int run_sampled()
     return (total || !ok) ? 1 : 0;
 }
 
+
+static int run_single()
+{
+    hipLaunchKernelGGL(k_single_n, dim3(((unsigned)kNFams << 23) / 256u), dim3(256), 0, 0);
+    for (int k = 0; k < 2; ++k)
+        for (uint32_t c = 0; c < 4; ++c) hipLaunchKernelGGL(k_single_c, dim3((1u << 30) / 256u), dim3(256), 0, 0, c << 30, k);
+    for (int site = 0; site < kSites; ++site) hipLaunchKernelGGL(k_single_sites, dim3((1u << 24) / 256u), dim3(256), 0, 0, site);
+    if (!sync_ok("single")) return 2;
+    unsigned long long nbad[kNFams], nin[kNFams], nwant[kNFams], nver[kNFams], cbad[2], cin[2], cwant[2], cver[2], cdone[2];
+    unsigned long long sbad[kSites], sin_[kSites], sver[kSites], sdone[kSites], done[8];
+    (void)hipMemcpyFromSymbol(done, HIP_SYMBOL(g_done), sizeof done);
+    (void)hipMemcpyFromSymbol(nbad, HIP_SYMBOL(g_n_bad), sizeof nbad);
+    (void)hipMemcpyFromSymbol(nin, HIP_SYMBOL(g_n_in), sizeof nin);
+    (void)hipMemcpyFromSymbol(nwant, HIP_SYMBOL(g_n_want), sizeof nwant);
+    (void)hipMemcpyFromSymbol(nver, HIP_SYMBOL(g_n_verdict), sizeof nver);
+    (void)hipMemcpyFromSymbol(cbad, HIP_SYMBOL(g_c_bad), sizeof cbad);
+    (void)hipMemcpyFromSymbol(cin, HIP_SYMBOL(g_c_in), sizeof cin);
+    (void)hipMemcpyFromSymbol(cwant, HIP_SYMBOL(g_c_want), sizeof cwant);
+    (void)hipMemcpyFromSymbol(cver, HIP_SYMBOL(g_c_verdict), sizeof cver);
+    (void)hipMemcpyFromSymbol(cdone, HIP_SYMBOL(g_c_done), sizeof cdone);
+    (void)hipMemcpyFromSymbol(sbad, HIP_SYMBOL(g_s_bad), sizeof sbad);
+    (void)hipMemcpyFromSymbol(sin_, HIP_SYMBOL(g_s_in), sizeof sin_);
+    (void)hipMemcpyFromSymbol(sver, HIP_SYMBOL(g_s_verdict), sizeof sver);
+    (void)hipMemcpyFromSymbol(sdone, HIP_SYMBOL(g_s_done), sizeof sdone);
+    printf("RTG_FDIV_CORRECTIONS = %d, RTG_FIT_FAST_DIV_TU = %d\n", (int)RTG_FDIV_CORRECTIONS, (int)RTG_FIT_FAST_DIV_TU);
+    unsigned long long total = 0, verdicts = 0;
+    bool covered = done[C_RAND] == (unsigned long long)kNCls * kNFams << 23;
+    const char *nn[kNFams] = {"b in [2^-47, 2^-46)", "b in [1, 2)", "b in [2^46, 2^47)", "b in [2^-48, 2^-47), outside",
+                              "b in (2^47, 2^48), outside"};
+    for (int f = 0; f < kNFams; ++f) {
+        printf("[N.%d] fdiv1 behind fdiv1_in_n, every mantissa, %s: %llu quotients, %llu mismatches, in-region %llu (worked out here: %llu, %llu verdicts differ)\n",
+               f, nn[f], (unsigned long long)kNCls << 23, nbad[f], nin[f], nwant[f], nver[f]);
+        total += nbad[f];
+        verdicts += nver[f] + (nin[f] != nwant[f]);
+        if (nwant[f] != (f < 3 ? 5ull << 23 : 0ull)) covered = false;
+    }
+    const char *cn[2] = {"a / sqrt(3) (la_bdsqr3_entry)", "a / 5 (mean5)"};
+    for (int k = 0; k < 2; ++k) {
+        printf("[C.%d] %s, every f32 a: %llu quotients, %llu mismatches, in-region %llu (worked out here: %llu, %llu verdicts differ)\n",
+               k, cn[k], cdone[k], cbad[k], cin[k], cwant[k], cver[k]);
+        total += cbad[k];
+        verdicts += cver[k] + (cin[k] != cwant[k]);
+        if (cdone[k] != 1ull << 32 || cwant[k] != 2ull * (((unsigned long long)(kBitsConstHi - kBitsNumLo)) + 1ull)) covered = false;
+    }
+    const char *sn[kSites] = {"[G.1] la_larfg<1>", "[G.2] la_larfg<2>", "[P] la_bdsqr3_pass", "[T] la_bdsqr3_entry",
+                              "[X] exp-map read-out"};
+    for (int k = 0; k < kSites; ++k) {
+        printf("%s against its a / b form: %llu operand sets, %llu mismatches, test passed on %llu (%llu verdicts differ)\n", sn[k],
+               sdone[k], sbad[k], sin_[k], sver[k]);
+        total += sbad[k];
+        verdicts += sver[k];
+        // both branches must have run: a test that never passes (or never fails) checks nothing
+        if (sdone[k] != 1ull << 24 || sin_[k] < 1ull << 20 || sdone[k] - sin_[k] < 1ull << 20) covered = false;
+    }
+    print_first(total);
+    if (verdicts) printf("a guard admitted operands outside its region, or refused operands inside it\n");
+    if (!covered) printf("a check did not cover its inputs\n");
+    return (total || verdicts) ? 1 : covered ? 0 : 2;
+}
+
 int main(int argc, char **argv)
 {
     if (argc >= 2 && !strcmp(argv[1], "exhaustive")) {
@@ -335,6 +583,7 @@ int main(int argc, char **argv)
         return run_exhaustive((uint32_t)chunks);
     }
     if (argc >= 2 && !strcmp(argv[1], "sampled")) return run_sampled();
-    printf("usage: check_fdiv1 exhaustive [chunks] | sampled\n");
+    if (argc >= 2 && !strcmp(argv[1], "single")) return run_single();
+    printf("usage: check_fdiv1 exhaustive [chunks] | sampled | single\n");
     return 2;
 }
