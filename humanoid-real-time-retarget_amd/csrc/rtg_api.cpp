@@ -289,10 +289,11 @@ int check_fk_backward(const char *fn, int64_t B, const void *grad_g_rot, const v
     return RTG_OK;
 }
 
-// rtg_dof_fit_f32 (R == nullptr), rtg_dof_fit_root_f32 (R: the root block) and rtg_dof_fit_orient_f32 (O too: the
-// orientation block, rot_joint its K host-side joint indices): one checked path, three kernels
+// rtg_dof_fit_f32 (R == nullptr), rtg_dof_fit_root_f32 (R: the root block), rtg_dof_fit_orient_f32 (O too: the
+// orientation block, rot_joint its K host-side joint indices) and rtg_dof_fit_prior_f32 (H too: the posture prior and
+// the projection): one checked path, five kernels
 int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const DofFitRootArgs *R, rtg_stream_t stream,
-                DofFitOriArgs *O = nullptr, const int32_t *rot_joint = nullptr)
+                DofFitOriArgs *O = nullptr, const int32_t *rot_joint = nullptr, const DofFitPriorArgs *H = nullptr)
 {
     // everything that needs no handle first
     if (A.B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)A.B);
@@ -337,9 +338,17 @@ int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const
         }
         if (O->K == 0) O->target_rot = O->rot_weight = nullptr;   // not looked at
     }
+    if (H) {
+        if (H->flags & ~RTG_FIT_PROJECT) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: flags=%d has unknown bits", fn, H->flags);
+        if (H->prior_weight && !H->prior)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: prior_weight given without prior", fn);
+        if (!H->prior && !H->flags) H = nullptr;   // neither term nor projection: rtg_dof_fit_orient_f32 itself
+    }
     if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL model", fn);
     if (clip && !m->has_limits)
         return fail(RTG_ERR_INVALID_ARGUMENT, "%s: clip_angles requested but the model has no DOF limits", fn);
+    if (H && (H->flags & RTG_FIT_PROJECT) && !m->has_limits)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: RTG_FIT_PROJECT requested but the model has no DOF limits", fn);
     const int J = m->topo->J;
     if (J > kGroupMaxJ)
         return fail(RTG_ERR_UNSUPPORTED, "%s: serves models of 1..%d joints (this one has %d)", fn, kGroupMaxJ, J);
@@ -353,8 +362,12 @@ int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const
         A.m = A.v = A.dof_out = A.grad = nullptr;
         if (!R || !R->fit_root) A.iters = 0;
         if (!A.loss && !root_out) return RTG_OK;
+        H = nullptr;   // no angles: nothing to hold or to project, and neither pointer is dereferenced
     }
-    if (O && O->K > 0)   // K == 0 is the pose fit itself: its kernel measured 250 us per iteration against 313 through the oriented one
+    if (H)
+        RTG_TRY(launch_dof_fit_prior(m->topo->view(), m->view(), clip != 0, A, *R, *O, *H, as_stream(stream)),
+                O->K > 0 ? "k_dof_fit_orient_prior" : "k_dof_fit_prior");
+    else if (O && O->K > 0)   // K == 0 is the pose fit itself: its kernel measured 250 us per iteration against 313 through the oriented one
         RTG_TRY(launch_dof_fit_orient(m->topo->view(), m->view(), clip != 0, A, *R, *O, as_stream(stream)),
                 "k_dof_fit_orient");
     else if (R)
@@ -647,6 +660,22 @@ int rtg_dof_fit_orient_f32(rtg_dof_model_t m, const float *target_pos, const flo
     const DofFitRootArgs R{fit_root, lr_root_t, lr_root_rot, root_state, root_rot_out, root_t_out, grad_root};
     DofFitOriArgs O{target_rot, rot_weight, K, {}};
     return run_dof_fit("rtg_dof_fit_orient_f32", m, clip, A, &R, stream, &O, rot_joint);
+}
+
+int rtg_dof_fit_prior_f32(rtg_dof_model_t m, const float *target_pos, const float *weight, const int32_t *rot_joint,
+                          const float *target_rot, const float *rot_weight, int32_t K, const float *prior,
+                          const float *prior_weight, int32_t flags, const float *root_rot, const float *root_t,
+                          const float *dof_in, int64_t B, int clip, int32_t fit_root, int32_t iters, float lr,
+                          float lr_root_t, float lr_root_rot, float beta1, float beta2, float eps, int32_t step0, float *mo,
+                          float *v, float *root_state, float *dof_out, float *root_rot_out, float *root_t_out, float *loss,
+                          float *grad, float *grad_root, rtg_stream_t stream)
+{
+    const DofFitArgs A{target_pos, weight, root_rot, root_t, dof_in, B, iters, step0, lr, beta1, beta2, eps,
+                       mo, v, dof_out, loss, grad};
+    const DofFitRootArgs R{fit_root, lr_root_t, lr_root_rot, root_state, root_rot_out, root_t_out, grad_root};
+    DofFitOriArgs O{target_rot, rot_weight, K, {}};
+    const DofFitPriorArgs H{prior, prior_weight, flags};
+    return run_dof_fit("rtg_dof_fit_prior_f32", m, clip, A, &R, stream, &O, rot_joint, &H);
 }
 
 // ---------------------------------------------------------------- SkeletonState.retarget_to

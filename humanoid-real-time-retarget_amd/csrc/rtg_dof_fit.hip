@@ -33,11 +33,24 @@
 // in the launch arguments (checked on the host), so a joint's {slot, rot_weight} entry is filled from them.  The loss
 // adds the links after the positions, in k order, by the lane that writes the frame's loss.
 //
+// k_dof_fit_prior_group / k_dof_fit_orient_prior_group (rtg_dof_fit_prior_f32, K == 0 / K > 0) are the root tile and
+// the oriented tile with a posture prior on the angles and a projection onto the limits (PRIOR): L_f gains
+// sum_d prior_weight[d] (a_d - prior_d)^2 on the iterate a -- not on the clamped angle the forward model uses, so the
+// term pulls a run-away iterate back -- and its gradient 2 prior_weight[d] (a_d - prior_d) joins dL/da_d in the lane
+// that holds it, before the Adam step; with RTG_FIT_PROJECT that lane clamps the angle to the limits the step already
+// holds after its step (torch.clamp: NaN passes; the moments stay).  Whether a prior is given and whether to project
+// are launch arguments (wave-uniform).  The prior rows are loaded with the angles, before the tile writes anything, so
+// they may alias dof_in or dof_out.  The loss adds the term per sub-lane (its DOFs u, u + L, ... in index order) to that
+// lane's position part.
+//
 // LDS images of a tile: FitImages below (every image starts 16-byte aligned).
 // 33-link Hu, F = 16 (10 steps): 29.3 KiB; a 64-joint chain, F = 8, 64 steps: 43.9 KiB (the largest: gsteps <= J).
 // With the root image and the two more step sizes per Adam step: 31.1 KiB (still 5 tiles per CU) and 45.1 KiB.
 // ORI adds 8 J + 16 F K bytes, sized by the launch's own K: Hu keeps 5 tiles per CU up to K = 2 and has 4 from there
 // (K = 8: 34,160 B of the 40,960 a tile may have there); the 64-joint chain with K = 8: 47,680 B.
+// PRIOR adds 4 F (J - 1) + 4 (J - 1) bytes: Hu 34,016 B (K = 8: 36,336 B), the chain 48,416 B (K = 8: 49,952 B).
+// Measured: a Hu tile keeps its fifth place on a CU up to 32,000 B of dynamic LDS, not 32,768, so the
+// PRIOR tiles -- and every ORI tile -- run four to a CU, and that is where their time over k_dof_fit_root_group sits.
 //
 // Arithmetic: as in rtg_fk_grad.hip no operation order is owed to a reference (explicit fmaf, the device sincosf,
 // -ffp-contract=fast); the forward here is the float32 restatement of rtg_dof_fk_f32's, not its bit-exact f64 sincos.
@@ -90,9 +103,11 @@ struct FitImages {
                      // (the moments are out by then) [F 7]: grad_root's rows {dL/dt, dL/dq}
     f4v *Rh;         // ORI: [F K] the unit target rotations of the oriented links
     OriEnt *otab;    // ORI: [J] per joint {slot in 0..K-1 or -1: not oriented, rot_weight}
+    float *Pr;       // PRIOR: [F (J-1)] the prior rows (zeros where no prior is given)
+    float *Pw;       // PRIOR: [J-1] prior_weight
     size_t floats;
-    // K < 0: no orientation images
-    __host__ __device__ FitImages(float *base, int J, int F, int steps, bool root, int K = -1)
+    // K < 0: no orientation images; the prior images come last, so every other offset is what it is without them
+    __host__ __device__ FitImages(float *base, int J, int F, int steps, bool root, int K = -1, bool prior = false)
     {
         LdsCarve c(base);
         G = c.take<f4v>((size_t)F * J);
@@ -111,6 +126,8 @@ struct FitImages {
         Rs = c.take<float>(root ? 14 * F : 0);
         Rh = c.take<f4v>(K > 0 ? (size_t)F * K : 0);
         otab = c.take<OriEnt>(K >= 0 ? J : 0);
+        Pr = c.take<float>(prior ? (size_t)F * (J - 1) : 0);
+        Pw = c.take<float>(prior ? J - 1 : 0);
         floats = c.floats;
     }
 };
@@ -211,6 +228,22 @@ RTG_DEV float orient_loss(const FitImages &I, const DofFitOriArgs &O, int J, int
     return l;
 }
 
+// PRIOR: this lane's part of the posture term sum_d prior_weight[d] (a_d - prior_d)^2 of frame fr: sub-lane u takes
+// the DOFs u, u + L, ... in index order, and the caller adds it to the lane's position part, so the loss keeps one order
+template <int F>
+RTG_DEV float prior_loss_part(const FitImages &I, int nd, bool live, int fr, int sub)
+{
+    using G = Grp<F>;
+    float acc = 0.0f;
+    if (live) {
+        for (int d = sub; d < nd; d += G::L) {
+            const float e = I.A[fr * nd + d] - I.Pr[fr * nd + d];
+            acc = __builtin_fmaf(I.Pw[d], e * e, acc);
+        }
+    }
+    return acc;
+}
+
 struct AdamStep {
     float b1, omb1, b2, omb2, eps;
     float step, rbc2s;   // lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)
@@ -271,10 +304,13 @@ RTG_DEV void fit_root_reverse(const FitImages &I, int J, int K, int fr, int firs
 
 // the reverse sweep; EVAL: the gradient rows into the M image, else the Adam step of each angle where its gradient
 // appears; ROOT: the sweep ends with the root's step (fit_root_reverse); ORI: an oriented joint's own rotation adjoint
-// leads its pull (orient_adjoint)
-template <bool CLIP, bool EVAL, int F, bool ROOT, bool ORI>
+// leads its pull (orient_adjoint); PRIOR: with `prior` the posture term's 2 prior_weight[d] (a - prior) joins the
+// angle's gradient where that appears (a: the iterate, not the clamped angle), and with `project` the angle is clamped
+// to its limits after its Adam step (torch.clamp: NaN passes; the moments are not touched).  The two reads of the prior
+// images are issued at the top of the joint's step, off the chain that ends in angle_grad.
+template <bool CLIP, bool EVAL, int F, bool ROOT, bool ORI, bool PRIOR = false>
 RTG_DEV void fit_reverse(const FitImages &I, int J, int K, int gsteps, bool live, int fr, int sub, const AdamStep &S,
-                         int fit_root)
+                         int fit_root, bool prior = false, bool project = false)
 {
     using G = Grp<F>;
     const int base = fr * J, nd = J - 1;
@@ -284,6 +320,11 @@ RTG_DEV void fit_reverse(const FitImages &I, int J, int K, int gsteps, bool live
         if (s > 0) en = I.sch[(s - 1) * G::L + sub];   // the next step's entry: its latency under this step
         const int j = e.code & 0xFF, p = (e.code >> 8) & 0xFF;
         if (live && j != 0xFF && j != 0) {
+            float pv = 0.0f, pw = 0.0f;
+            if constexpr (PRIOR) {
+                pv = I.Pr[fr * nd + j - 1];
+                pw = I.Pw[j - 1];
+            }
             V pb;
             const f4v a = child_pull(orient_adjoint<ORI>(I, K, fr, base + j, j), I.G, I.P, base, j,
                                      (e.code >> 16) & 0xFF, I.nsib, pb);
@@ -294,15 +335,22 @@ RTG_DEV void fit_reverse(const FitImages &I, int J, int K, int gsteps, bool live
             const AngleRot r = angle_rot<CLIP>(ang, __float_as_int(t.x), t.y, t.z);
             const JointAdj o = joint_adjoint(Gp, Gj, angle_quat(r), V{e.lx, e.ly, e.lz}, q_of(a), pb);
             I.G[base + j] = v_of(o.gp);
-            const float g = angle_grad(r, o.lqb);
+            float g = angle_grad(r, o.lqb);
+            if constexpr (PRIOR) {   // on a +-0 gradient this is fl(2 pw) fl(a - p): one rounding each
+                if (prior) g = __builtin_fmaf(2.0f * pw, ang - pv, g);
+            }
             if (EVAL) {
                 I.M[i] = g;
-            } else {   // torch.optim.Adam's step on the unprojected iterate
+            } else {   // torch.optim.Adam's step on the iterate; PRIOR with project: then the clamp to the limits
                 const float m = __builtin_fmaf(S.omb1, g, S.b1 * I.M[i]);
                 const float v = __builtin_fmaf(S.omb2 * g, g, S.b2 * I.V[i]);
                 I.M[i] = m;
                 I.V[i] = v;
-                I.A[i] = __builtin_fmaf(-S.step, m / __builtin_fmaf(__builtin_sqrtf(v), S.rbc2s, S.eps), ang);
+                float x = __builtin_fmaf(-S.step, m / __builtin_fmaf(__builtin_sqrtf(v), S.rbc2s, S.eps), ang);
+                if constexpr (PRIOR) {
+                    if (project) x = x < t.y ? t.y : (x > t.z ? t.z : x);
+                }
+                I.A[i] = x;
             }
         }
         if (ROOT && live && j == 0) fit_root_reverse<EVAL, ORI>(I, J, K, fr, (e.code >> 16) & 0xFF, fit_root, S);
@@ -314,12 +362,14 @@ using RootStateRows = LaneRows<float, 4>;   // a tile's root_state rows: 14 F <=
 using OriRows = LaneRows<f4v, 2>;           // a tile's target rotations: F K <= 128 records
 
 // one tile of the fit; ROOT: the root's rows come from the root image and its adjoints are taken (R: the root's
-// arguments, not looked at otherwise); ORI: with orientation targets (O: theirs, likewise)
-template <bool CLIP, int F, bool ROOT, bool ORI>
+// arguments, not looked at otherwise); ORI: with orientation targets (O: theirs, likewise); PRIOR: with the posture
+// prior and the projection onto the limits (H: theirs, likewise; what H asks for is wave-uniform, like fit_root)
+template <bool CLIP, int F, bool ROOT, bool ORI, bool PRIOR = false>
 RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs &A, const DofFitRootArgs &R,
-                          const DofFitOriArgs &O)
+                          const DofFitOriArgs &O, const DofFitPriorArgs &H = DofFitPriorArgs{})
 {
     static_assert(ROOT || !ORI, "the oriented tile carries the root image");
+    static_assert(ROOT || !PRIOR, "the prior tile carries the root image");
     extern __shared__ __attribute__((aligned(16))) float ft_lds[];
     using G = Grp<F>;
     const int J = T.J, lane = (int)threadIdx.x, nd = J - 1;
@@ -327,9 +377,10 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
     const int nfr = tile_frames<F>(A.B, f0);
     const int npos = 3 * nfr * J, nang = nfr * nd;
     const int K = ORI ? O.K : 0;
-    const FitImages I(ft_lds, J, F, T.gsteps, ROOT, ORI ? K : -1);
+    const FitImages I(ft_lds, J, F, T.gsteps, ROOT, ORI ? K : -1, PRIOR);
     float *lossp = I.lossp, *adam = I.adam;
     const int fit_root = ROOT ? R.fit_root : 0;
+    const bool prior = PRIOR && H.prior != nullptr, project = PRIOR && (H.flags & RTG_FIT_PROJECT) != 0;
 
     // every global load of the tile first (a lane past the rows re-reads element 0), then the LDS images
     const bool state = A.m != nullptr;
@@ -342,6 +393,11 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
         v0.load(A.v + f0 * nd, nang);
     }
     if (rstate) rs.load(R.state + f0 * 14, 14 * nfr);
+    ScalarRows<F> pr = {};   // PRIOR: the tile's prior rows, read here -- before the tile writes a row -- so they may alias
+                             // dof_in or dof_out
+    if constexpr (PRIOR) {
+        if (prior) pr.load(H.prior + f0 * nd, nang);
+    }
     OriRows tr = {};
     if (ORI && K > 0) tr.load(O.target_rot + f0 * K * 4, nfr * K);
     const float *trow = A.target_pos + f0 * J * 3;
@@ -355,6 +411,18 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
     m0.store(I.M, nang);
     v0.store(I.V, nang);
     tp.to_lds(I.T, trow, npos);
+    if constexpr (PRIOR) {
+        pr.store(I.Pr, nang);
+        for (int d = lane; d < nd; d += 64) I.Pw[d] = prior && H.prior_weight ? ld_const(H.prior_weight + d) : (prior ? 1.0f : 0.0f);
+        if (!CLIP && project)   // the table carries the limits only under the clip: this lane's own entries, again
+            for (int j = lane; j < J; j += 64) {
+                if (j == 0) continue;
+                f4v t = I.tab[j];
+                t.y = ld_const(D.lower + (j - 1));
+                t.z = ld_const(D.upper + (j - 1));
+                I.tab[j] = t;
+            }
+    }
     if (ORI) {   // the unit targets, and each joint's entry from the launch's link list
 #pragma unroll
         for (int k = 0; k < 2; ++k) tr.v[k] = root_unit(tr.v[k]);
@@ -410,7 +478,7 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
         }
         fit_forward<CLIP, F, ROOT>(I, J, T.gsteps, live, fr, sub, fit_root);
         (void)fit_residual<F, ROOT>(I, J, live, fr, sub);
-        fit_reverse<CLIP, false, F, ROOT, ORI>(I, J, K, T.gsteps, live, fr, sub, S, fit_root);
+        fit_reverse<CLIP, false, F, ROOT, ORI, PRIOR>(I, J, K, T.gsteps, live, fr, sub, S, fit_root, prior, project);
     }
 
     // the iterate and its state out (coalesced), then loss and gradient there by one more sweep
@@ -427,7 +495,10 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
     if (!A.loss && !A.grad && !(ROOT && R.grad)) return;
     wave_sync();   // the M image is read out before the evaluation sweep writes gradients into it
     fit_forward<CLIP, F, ROOT>(I, J, T.gsteps, live, fr, sub, fit_root);
-    const float part = fit_residual<F, ROOT>(I, J, live, fr, sub);
+    float part = fit_residual<F, ROOT>(I, J, live, fr, sub);
+    if constexpr (PRIOR) {
+        if (prior) part += prior_loss_part<F>(I, nd, live, fr, sub);
+    }
     if (A.loss) {
         lossp[lane] = part;
         wave_sync();
@@ -440,7 +511,7 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
         }
     }
     if (A.grad || (ROOT && R.grad)) {
-        fit_reverse<CLIP, true, F, ROOT, ORI>(I, J, K, T.gsteps, live, fr, sub, S, fit_root);
+        fit_reverse<CLIP, true, F, ROOT, ORI, PRIOR>(I, J, K, T.gsteps, live, fr, sub, S, fit_root, prior, project);
         if (A.grad) ScalarRows<F>::copy_out(I.M, A.grad + f0 * nd, nang);
         if (ROOT && R.grad) RootStateRows::copy_out(I.Rs, R.grad + f0 * 7, 7 * nfr);
     }
@@ -463,6 +534,21 @@ __global__ __launch_bounds__(64) void k_dof_fit_orient_group(TopoView T, DofView
                                                              DofFitOriArgs O)
 {
     dof_fit_tile<CLIP, F, true, true>(T, D, A, R, O);
+}
+
+// rtg_dof_fit_prior_f32 without oriented links (the ORI instantiation measured 25 % slower at K = 0) and with them
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_prior_group(TopoView T, DofView D, DofFitArgs A, DofFitRootArgs R,
+                                                            DofFitPriorArgs H)
+{
+    dof_fit_tile<CLIP, F, true, false, true>(T, D, A, R, DofFitOriArgs{}, H);
+}
+
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_orient_prior_group(TopoView T, DofView D, DofFitArgs A, DofFitRootArgs R,
+                                                                   DofFitOriArgs O, DofFitPriorArgs H)
+{
+    dof_fit_tile<CLIP, F, true, true, true>(T, D, A, R, O, H);
 }
 
 template <bool ROOT>
@@ -514,6 +600,32 @@ hipError_t launch_dof_fit_orient(const TopoView &T, const DofView &D, bool clip,
         attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_orient_group<cl(), f()>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
         if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_orient_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A, R, O);
+    }, clip);
+    if (attr != hipSuccess) return attr;
+    return hipGetLastError();
+}
+
+hipError_t launch_dof_fit_prior(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
+                                const DofFitRootArgs &R, const DofFitOriArgs &O, const DofFitPriorArgs &H, hipStream_t s)
+{
+    if (!T.gsched || O.K < 0 || O.K > RTG_FIT_MAX_ROT_LINKS) return hipErrorInvalidValue;
+    if ((H.flags & RTG_FIT_PROJECT) && (!D.lower || !D.upper)) return hipErrorInvalidValue;   // the kernel reads them
+    for (int k = 0; k < O.K; ++k)   // the kernel indexes rows with them
+        if (O.joint[k] < 0 || O.joint[k] >= T.J) return hipErrorInvalidValue;
+    const int F = T.gF;
+    const size_t lds = sizeof(float) * FitImages(nullptr, T.J, F, T.gsteps, true, O.K > 0 ? O.K : -1, true).floats;
+    if (lds > kFitMaxLdsBytes) return hipErrorInvalidValue;
+    hipError_t attr = hipSuccess;
+    group_dispatch(F, [&](auto f, auto cl) {
+        if (O.K > 0) {
+            attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_orient_prior_group<cl(), f()>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
+            if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_orient_prior_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A, R, O, H);
+        } else {
+            attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_prior_group<cl(), f()>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
+            if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_prior_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A, R, H);
+        }
     }, clip);
     if (attr != hipSuccess) return attr;
     return hipGetLastError();

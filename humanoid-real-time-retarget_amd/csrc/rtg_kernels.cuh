@@ -123,6 +123,15 @@ struct DofFitOriArgs {
 };
 hipError_t launch_dof_fit_orient(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
                                  const DofFitRootArgs &R, const DofFitOriArgs &O, hipStream_t s);
+// rtg_dof_fit_prior_f32: the root launch (O.K == 0) or the oriented one with the posture prior and the projection.
+// prior (B,J-1) or nullptr: no term; prior_weight (J-1) or nullptr: ones; flags: RTG_FIT_PROJECT (the model then has
+// limits: host-checked)
+struct DofFitPriorArgs {
+    const float *prior, *prior_weight;
+    int32_t flags;
+};
+hipError_t launch_dof_fit_prior(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
+                                const DofFitRootArgs &R, const DofFitOriArgs &O, const DofFitPriorArgs &H, hipStream_t s);
 // SkeletonState.retarget_to (poselib skeleton3d.py:742-889) as one launch, rtg_retarget_to.hip.
 // The host tables of a mapping of K (source joint, target joint) pairs: S_red / T_red are the trees with only the
 // mapped joints kept, each hung from its nearest kept ancestor (drop_nodes_by_names, :226-259).

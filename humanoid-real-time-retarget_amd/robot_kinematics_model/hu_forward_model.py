@@ -59,6 +59,13 @@ class HuForwardModel(BaseForwardModel):
                 joints.append(int(link))
         return dict(rot_joints=joints, target_rot=target_rotations, rot_weight=rotation_weight)
 
+    def _posture_prior(self, prior_angles, prior_weight, project_angles):
+        """fit_keypoints' / fit_pose's posture arguments as ops': (L, J-1, 1) or (L, J-1) prior angles, a number or
+        (J-1,) weights, the projection (it needs the limits)."""
+        if project_angles and not self._model.has_limits:
+            raise ValueError("project_angles needs DOF limits with one entry per DOF")
+        return dict(prior=prior_angles, prior_weight=prior_weight, project=bool(project_angles))
+
     def forward_kinematics(self, motion_joint_angles, motion_root_translation, motion_root_rotation, clip_angles):
         """(L, J-1, 1) angles, (L, 3) root translation, (L, 1, 4) root rotation -> ((L, J, 4), (L, J, 3))."""
         if clip_angles and not self._model.has_limits:
@@ -71,15 +78,17 @@ class HuForwardModel(BaseForwardModel):
     def fit_keypoints(self, target_positions, motion_root_translation, motion_root_rotation,
                       motion_joint_angles=None, weight=None, iters=32, lr=0.02, betas=(0.9, 0.999), eps=1e-8,
                       clip_angles=True, state=None, return_grad=False, target_rotations=None, rotation_links=None,
-                      rotation_weight=None):
+                      rotation_weight=None, prior_angles=None, prior_weight=None, project_angles=False):
         """Not in the reference, which only ships the forward model of its optimisation-based converter: the loop that
         model is for -- a keypoint loss sum_j weight[j] |g_pos[:, j] - target_positions[:, j]|^2 minimised over the
         joint angles with torch.optim.Adam -- as one launch (ops.dof_fit).  (L, J, 3) targets, (L, 3) root translation,
         (L, 1, 4) root rotation, (L, J-1, 1) starting angles (default: zeros) -> ((L, J-1, 1) angles, (L,) loss,
         state[, (L, J-1, 1) gradient]); ``state`` from an earlier call continues its optimiser.  The angles are not
-        projected onto the limits: apply _clip_angles (or a clamp) to the result for the final pose.
+        projected onto the limits unless ``project_angles`` is set: without it apply _clip_angles (or a clamp) to the
+        result for the final pose.
         ``target_rotations`` (L, K, 4), ``rotation_links`` (K node names or joint indices, K <= 8) and
-        ``rotation_weight`` (K,) add fit_pose's orientation term for those links, the root given."""
+        ``rotation_weight`` (K,) add fit_pose's orientation term for those links, the root given.  ``prior_angles``,
+        ``prior_weight``, ``project_angles``: fit_pose's posture prior and projection."""
         if clip_angles and not self._model.has_limits:
             raise ValueError("clip_angles needs DOF limits with one entry per DOF")
         dev = home_device(target_positions, motion_root_translation, motion_root_rotation)
@@ -87,7 +96,8 @@ class HuForwardModel(BaseForwardModel):
         res = ops.dof_fit(self._model, target_positions, motion_root_rotation, motion_root_translation,
                           dof0=motion_joint_angles, weight=weight, iters=iters, lr=lr, betas=betas, eps=eps,
                           clip=bool(clip_angles), state=state, return_grad=return_grad,
-                          **self._rotation_targets(target_rotations, rotation_links, rotation_weight))
+                          **self._rotation_targets(target_rotations, rotation_links, rotation_weight),
+                          **self._posture_prior(prior_angles, prior_weight, project_angles))
         dof, loss, new_state = res[:3]
         shaped = lambda a: a.reshape(tuple(loss.shape) + (n, 1)).to(dev)
         out = (shaped(dof), loss.to(dev), new_state)
@@ -96,7 +106,7 @@ class HuForwardModel(BaseForwardModel):
     def fit_pose(self, target_positions, motion_root_translation, motion_root_rotation, motion_joint_angles=None,
                  weight=None, iters=32, lr=0.02, lr_root_t=None, lr_root_rot=None, fit_root_t=True, fit_root_rot=True,
                  betas=(0.9, 0.999), eps=1e-8, clip_angles=True, state=None, return_grad=False, target_rotations=None,
-                 rotation_links=None, rotation_weight=None):
+                 rotation_links=None, rotation_weight=None, prior_angles=None, prior_weight=None, project_angles=False):
         """fit_keypoints with the floating base among the parameters (ops.pose_fit): mocap keypoints come from a body
         of other proportions, and with the root pinned the legs cannot reach them.  (L, J, 3) targets, (L, 3) root
         translation and (L, 1, 4) root rotation to start from (or given, where fit_root_t / fit_root_rot is False),
@@ -107,7 +117,11 @@ class HuForwardModel(BaseForwardModel):
         ``rotation_weight`` (K,, default ones): global rotations those links are pulled towards in the same launch, by
         the loss term rotation_weight[k] (2 sin(theta_k / 2))^2 of the angle to the target -- "this hand points this
         way, this foot is flat".  Keypoints alone leave wrists, ankles, the head and every link's twist where the
-        start had them."""
+        start had them.
+        ``prior_angles`` (L, J-1, 1) or (L, J-1) and ``prior_weight`` (a number or (J-1,), default ones) add the posture
+        term sum_d prior_weight[d] (angle_d - prior_d)^2 on the iterate: it holds DOFs no target observes, and a
+        redundant arm's swivel, to a rest pose or to the last frame's solution.  ``project_angles`` clamps every angle
+        to its limits after each step, so an unreachable target cannot push the iterate past a limit without bound."""
         if clip_angles and not self._model.has_limits:
             raise ValueError("clip_angles needs DOF limits with one entry per DOF")
         dev = home_device(target_positions, motion_root_translation, motion_root_rotation)
@@ -116,12 +130,50 @@ class HuForwardModel(BaseForwardModel):
                            dof0=motion_joint_angles, weight=weight, iters=iters, lr=lr, lr_root_t=lr_root_t,
                            lr_root_rot=lr_root_rot, fit_root_t=fit_root_t, fit_root_rot=fit_root_rot, betas=betas,
                            eps=eps, clip=bool(clip_angles), state=state, return_grad=return_grad,
-                           **self._rotation_targets(target_rotations, rotation_links, rotation_weight))
+                           **self._rotation_targets(target_rotations, rotation_links, rotation_weight),
+                           **self._posture_prior(prior_angles, prior_weight, project_angles))
         lead = tuple(res.loss.shape)
         shaped = lambda a: a.reshape(lead + (n, 1)).to(dev)
         out = (shaped(res.dof), res.root_t.to(dev), res.root_rot.reshape(lead + (1, 4)).to(dev), res.loss.to(dev),
                res.state)
         return out + (shaped(res.grad), res.grad_root.to(dev)) if return_grad else out
+
+    def fit_motion(self, target_positions, motion_root_translation, motion_root_rotation, motion_joint_angles=None,
+                   smooth_weight=0.1, rounds=8, iters=8, **fit_pose_keywords):
+        """fit_pose for a clip whose rows are consecutive frames: frames fitted on their own jitter with the keypoint
+        noise, so the fit runs ``rounds`` times ``iters`` steps, and before each round every frame's angles get a
+        posture prior towards the mean of its two neighbours in the current iterate,
+        prior[f] = (a[max(f-1, 0)] + a[min(f+1, L-1)]) / 2 (the ends repeat, like the reference's "nearest" Gaussian
+        filters), with ``smooth_weight`` per rad^2.  Each round is one fit_pose launch from the current angles and
+        root that carries the optimiser state.  ``smooth_weight == 0`` passes no prior: that is one fit_pose of
+        rounds * iters steps, bit for bit.  Only the angles are smoothed: the root can be regularised through
+        weight[0] and an orientation target on link 0.  The other keywords are fit_pose's (``prior_angles`` and
+        ``state`` are this method's to set; ``prior_weight`` scales smooth_weight per DOF).  Returns what fit_pose
+        returns, after the last round."""
+        for k in ("prior_angles", "state"):
+            if k in fit_pose_keywords:
+                raise ValueError(f"fit_motion sets {k} itself")
+        rounds, smooth_weight = int(rounds), float(smooth_weight)
+        if rounds < 1:
+            raise ValueError(f"rounds must be at least 1, got {rounds}")
+        if not smooth_weight >= 0.0:
+            raise ValueError(f"smooth_weight must not be negative, got {smooth_weight}")
+        pw = fit_pose_keywords.pop("prior_weight", None)
+        want_grad = bool(fit_pose_keywords.pop("return_grad", False))
+        a, t, q, state = motion_joint_angles, motion_root_translation, motion_root_rotation, None
+        for r in range(rounds):
+            prior = {}
+            if smooth_weight > 0.0:
+                if a is None:   # fit_pose's default start
+                    a = torch.zeros(tuple(target_positions.shape[:-2]) + (self.num_joints - 1, 1),
+                                    device=target_positions.device, dtype=torch.float32)
+                a = torch.as_tensor(a)
+                prior = dict(prior_angles=0.5 * (torch.cat([a[:1], a[:-1]]) + torch.cat([a[1:], a[-1:]])),
+                             prior_weight=smooth_weight if pw is None else smooth_weight * torch.as_tensor(pw))
+            res = self.fit_pose(target_positions, t, q, a, iters=iters, state=state,
+                                return_grad=want_grad and r == rounds - 1, **prior, **fit_pose_keywords)
+            a, t, q, state = res[0], res[1], res[2], res[4]
+        return res
 
     def _clip_angles(self, motion_joint_angles):
         """:27-33, forward value: (clamp(a, lo, hi) - a) + a, elementwise on the angles' device."""

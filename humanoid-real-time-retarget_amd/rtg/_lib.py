@@ -127,6 +127,9 @@ SIGNATURES = {
     # (rot_joint is a host pointer: K int32 values read during the call)
     "rtg_dof_fit_orient_f32": (c_int, [c_void_p] * 6 + [c_int32] + [c_void_p] * 3 + [c_int64, c_int, c_int32, c_int32] +
                                       [c_float] * 6 + [c_int32] + [c_void_p] * 10),
+    # (the same with (prior, prior_weight, flags) after K)
+    "rtg_dof_fit_prior_f32": (c_int, [c_void_p] * 6 + [c_int32] + [c_void_p] * 2 + [c_int32] + [c_void_p] * 3 +
+                                     [c_int64, c_int, c_int32, c_int32] + [c_float] * 6 + [c_int32] + [c_void_p] * 10),
     "rtg_retarget_plan_create": (c_int, [c_void_p, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int32,
                                          POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                          POINTER(c_float), c_float, POINTER(c_void_p)]),

@@ -486,6 +486,43 @@ def _orient_inputs(model, lead, rot_joints, target_rot, rot_weight):
     return Orient((ctypes.c_int32 * max(K, 1))(*joints), K, tr, rw)
 
 
+FIT_PROJECT = 1   # rtg.h RTG_FIT_PROJECT
+
+Prior = collections.namedtuple("Prior", "rows weight flags")   # rows / weight: device tensors or None
+
+
+def _prior_inputs(model, d, prior, prior_weight, project):
+    """The posture prior and the projection of a fit, checked before the C ABI sees a pointer: prior (..., J-1) [or
+    (..., J-1, 1)] over the angles' own shape ``d.shape``, as a contiguous float32 device tensor (never part of the
+    graph); prior_weight a number or (J-1,), None for ones; project needs a model with limits.  None when none of the
+    three is given."""
+    if prior is None and prior_weight is None and not project:
+        return None
+    if prior is None and prior_weight is not None:
+        raise ValueError("prior_weight needs a prior")
+    if project and not model.has_limits:
+        raise ValueError("project needs a model with DOF limits")
+    n = model.num_dofs
+    rows = pw = None
+    if prior is not None:
+        p = _as_tensor(prior)
+        if p.dtype not in (torch.float16, torch.bfloat16, torch.float32, torch.float64):
+            raise ValueError(f"prior must be floating point, got {p.dtype}")
+        if p.dim() >= 2 and p.shape[-1] == 1 and p.shape[-2] == n:
+            p = p[..., 0]
+        rows = dev_f32(p.detach(), (n,), "prior")
+        if tuple(rows.shape) != tuple(d.shape):
+            raise ValueError(f"prior {tuple(rows.shape)} does not match the angles {tuple(d.shape)}")
+    if prior_weight is not None:
+        w = _as_tensor(prior_weight)
+        if w.dim() == 0:
+            w = w.reshape(1).expand(n)
+        pw = dev_f32(w.detach(), (n,), "prior_weight")
+        if pw.dim() != 1:
+            raise ValueError(f"prior_weight must be a number or ({n},), got {tuple(pw.shape)}")
+    return Prior(rows, pw, FIT_PROJECT if project else 0)
+
+
 def _fit_state(model, d, dof0, iters, state):
     """What dof_fit and pose_fit share around their launches: ``iters`` range-checked; the angles' optimiser state
     ``(m, v, step)`` -- fresh (zeros, 0) for ``state`` None, else the caller's, copied (the launch updates it in
@@ -521,7 +558,7 @@ def _fit_launch(model, clip, tp, w, rr, rt, d, iters=0, lr=0.0, betas=(0.9, 0.99
 
 def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: int = 32, lr: float = 0.02,
             betas=(0.9, 0.999), eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False,
-            rot_joints=None, target_rot=None, rot_weight=None):
+            rot_joints=None, target_rot=None, rot_weight=None, prior=None, prior_weight=None, project: bool = False):
     """Fit the joint angles of a DofModel to target keypoints: ``iters`` steps of torch.optim.Adam (no weight decay, no
     amsgrad) on L_f = sum_j weight[j] |P_j(a_f) - target_pos[f, j]|^2, P the positions of dof_forward_kinematics --
     forward model, loss, gradient and optimiser in ONE launch (rtg_dof_fit_f32).
@@ -530,37 +567,47 @@ def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: 
     (..., J-1, 1)] the start, default zeros; weight (J,) or None for all ones.  ``state`` is the optimiser's
     ``(m, v, step)`` from an earlier call (None: a fresh optimiser); it is returned updated, so calls chain: two calls
     of n steps give the bits of one call of 2n.  The iterate is not projected onto the limits (``clip`` only clips
-    inside the forward model, straight-through); the final pose is the clamp the caller applies.
+    inside the forward model, straight-through) unless ``project`` is set; without it the final pose is the clamp the
+    caller applies.
 
     Returns ``(dof, loss, state)`` -- the angles after the last step (dof0's shape), the per-frame loss there (...),
     and the new state -- plus the gradient there (dof's shape) when ``return_grad``.  ``iters=0`` only evaluates.
     ``rot_joints``, ``target_rot``, ``rot_weight``: pose_fit's orientation targets, with the root given
     (rtg_dof_fit_orient_f32 with fit_root = 0; an oriented root then only adds to the loss).
+    ``prior``, ``prior_weight``, ``project``: pose_fit's posture prior and projection (rtg_dof_fit_prior_f32 with
+    fit_root = 0).
     Raises RtgError without a GPU: there is no CPU fallback."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof0, weight)
     iters, m, v, step, as_dof0 = _fit_state(model, d, dof0, iters, state)
     orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
-    if orient is None:
+    pri = _prior_inputs(model, d, prior, prior_weight, project)
+    if orient is None and pri is None:
         out, loss, grad = _fit_launch(model, clip, tp, w, rr, rt, d.detach(), iters, lr, betas, eps, step, m, v,
                                       want_dof=True, want_grad=bool(return_grad))
     else:   # the root is given: its state is neither read nor written, the buffer only pairs with m and v
         rs = torch.zeros(tuple(tp.shape[:-2]) + (14,), device=d.device, dtype=torch.float32)
         out, _, _, loss, grad, _ = _pose_launch(model, clip, 0, tp, w, rr, rt, d.detach(), iters, lr, 0.0, 0.0, betas, eps,
                                                 step, m if m.numel() else rs, v if v.numel() else rs, rs,
-                                                want_iterate=True, want_grad=bool(return_grad), orient=orient)
+                                                want_iterate=True, want_grad=bool(return_grad), orient=orient, prior=pri)
     res = (as_dof0(out), loss, (m, v, step + iters))
     return res + (as_dof0(grad),) if return_grad else res
 
 
 def keypoint_loss(model, dof, target_pos, root_rot, root_t, weight=None, clip: bool = False, rot_joints=None,
-                  target_rot=None, rot_weight=None):
+                  target_rot=None, rot_weight=None, prior=None, prior_weight=None):
     """The per-frame keypoint loss L_f = sum_j weight[j] |P_j(dof_f) - target_pos[f, j]|^2 of dof_fit, (...), as the
     evaluate-only launch of rtg_dof_fit_f32.  Differentiable in ``dof`` (only): the launch computes the gradient
     along with the loss, and backward scales its rows by the upstream cotangent -- for callers who keep their own
     optimiser.  Under no_grad, or when dof does not require grad, it is the plain launch without the gradient.
-    ``rot_joints``, ``target_rot``, ``rot_weight``: dof_fit's orientation targets."""
+    ``rot_joints``, ``target_rot``, ``rot_weight``: dof_fit's orientation targets.  ``prior``, ``prior_weight``: its
+    posture term sum_d prior_weight[d] (dof_d - prior_d)^2 (the loss is not differentiable in them)."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof, weight)
     orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
+    pri = _prior_inputs(model, d, prior, prior_weight, False)
+    if pri is not None:
+        if torch.is_grad_enabled() and d.requires_grad:
+            return _PriorPoseLoss.apply(model, bool(clip), 0, d, rr.detach(), rt.detach(), tp, w, orient, pri)
+        return _pose_launch(model, clip, 0, tp, w, rr, rt, d.detach(), orient=orient, prior=pri)[3]
     if orient is not None:
         if torch.is_grad_enabled() and d.requires_grad:
             return _OrientPoseLoss.apply(model, bool(clip), 0, d, rr.detach(), rt.detach(), tp, w, orient)
@@ -592,9 +639,9 @@ PoseFitGrad = collections.namedtuple("PoseFitGrad", "dof root_rot root_t loss st
 
 def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_root_t=0.0, lr_root_rot=0.0,
                  betas=(0.9, 0.999), eps=1e-8, step0=0, m=None, v=None, root_state=None, want_iterate=False,
-                 want_loss=True, want_grad=False, orient=None):
-    """rtg_dof_fit_root_f32 -- with ``orient`` (an Orient) rtg_dof_fit_orient_f32 -- on prepared tensors; m, v,
-    root_state are updated in place.  Returns (dof_out, root_rot_out, root_t_out, loss, grad, grad_root), None where
+                 want_loss=True, want_grad=False, orient=None, prior=None):
+    """rtg_dof_fit_root_f32 -- with ``orient`` (an Orient) rtg_dof_fit_orient_f32, with ``prior`` (a Prior)
+    rtg_dof_fit_prior_f32 -- on prepared tensors; m, v, root_state are updated in place.  Returns (dof_out, root_rot_out, root_t_out, loss, grad, grad_root), None where
     not asked for."""
     lead = tuple(tp.shape[:-2])
     B = int(torch.Size(lead).numel())
@@ -605,7 +652,11 @@ def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_ro
     tail = (ptr(rr), ptr(rt), ptr(d), B, int(bool(clip)), int(fit_root), int(iters), float(lr), float(lr_root_t),
             float(lr_root_rot), float(betas[0]), float(betas[1]), float(eps), int(step0), ptr(m), ptr(v), ptr(root_state),
             ptr(out), ptr(rr_out), ptr(rt_out), ptr(loss), ptr(grad), ptr(grad_root), stream_handle())
-    if orient is None:
+    if prior is not None:
+        o = orient if orient is not None else Orient(None, 0, None, None)
+        check(lib().rtg_dof_fit_prior_f32(model.handle, ptr(tp), ptr(w), o.joints, ptr(o.target_rot), ptr(o.rot_weight),
+                                          o.K, ptr(prior.rows), ptr(prior.weight), prior.flags, *tail))
+    elif orient is None:
         check(lib().rtg_dof_fit_root_f32(model.handle, ptr(tp), ptr(w), *tail))
     else:
         check(lib().rtg_dof_fit_orient_f32(model.handle, ptr(tp), ptr(w), orient.joints, ptr(orient.target_rot),
@@ -616,7 +667,7 @@ def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_ro
 def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iters: int = 32, lr: float = 0.02,
              lr_root_t=None, lr_root_rot=None, fit_root_t: bool = True, fit_root_rot: bool = True, betas=(0.9, 0.999),
              eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False, rot_joints=None,
-             target_rot=None, rot_weight=None):
+             target_rot=None, rot_weight=None, prior=None, prior_weight=None, project: bool = False):
     """dof_fit with the floating base among the parameters: the joint angles and -- where ``fit_root_t`` /
     ``fit_root_rot`` -- the root translation and rotation of every frame, fitted to target keypoints by ``iters`` steps
     of torch.optim.Adam with three parameter groups (``lr`` for the angles, ``lr_root_t``, ``lr_root_rot``; None: ``lr``)
@@ -636,6 +687,16 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
     poses leaf joints (wrists, ankles, the head) and a link's twist; positions alone give those DOFs a gradient of
     exactly 0.  The term is stationary at theta = pi.  With none of the three given this is the position-only launch.
 
+    Posture prior and projection (rtg_dof_fit_prior_f32, still one launch): ``prior`` (..., J-1) [or (..., J-1, 1)]
+    adds sum_d prior_weight[d] (a_d - prior_d)^2 to the loss, a the iterate itself (not the clamped angle of ``clip``),
+    ``prior_weight`` a number or (J-1,), None for ones: what holds an unobserved DOF or a redundant chain's swivel to a
+    rest pose or to the last frame's solution (``prior=dof0`` is "stay near where you started").  ``project``: each
+    angle is clamped to its limits after its Adam step (the loop ``opt.step(); a.clamp_(lower, upper)``; the moments are
+    not touched), so the iterate cannot run away past a limit under ``clip``'s straight-through gradient; it needs a
+    model with limits.  Without ``project`` the iterate is not projected.  The root is not regularised here:
+    weight[0] with target_pos[..., 0, :] is a prior on its translation, an orientation target on joint 0 on its
+    rotation.  With none of the three given this is the launch without them, bit for bit.
+
     Returns the named tuple ``(dof, root_rot, root_t, loss, state)`` -- the iterate after the last step (root_rot
     (..., 4), unit where fitted), the per-frame loss there -- plus ``grad`` (dof's shape) and ``grad_root`` (..., 7) =
     {dL/dt, dL/dq} there when ``return_grad``.  ``iters=0`` only evaluates.  Raises RtgError without a GPU: there is
@@ -649,12 +710,13 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
         rs = dev_f32(state[2], (14,), "root_state").reshape(lead + (14,)).clone()
     fit_root = (FIT_ROOT_T if fit_root_t else 0) | (FIT_ROOT_ROT if fit_root_rot else 0)
     orient = _orient_inputs(model, lead, rot_joints, target_rot, rot_weight)
+    pri = _prior_inputs(model, d, prior, prior_weight, project)
     # (a one-joint model has no angle moments: their arguments only say that a state is given)
     out, rr_out, rt_out, loss, grad, grad_root = _pose_launch(
         model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach(), iters, lr,
         lr if lr_root_t is None else lr_root_t, lr if lr_root_rot is None else lr_root_rot, betas, eps, step,
         m if m.numel() else rs, v if v.numel() else rs, rs, want_iterate=True, want_grad=bool(return_grad),
-        orient=orient)
+        orient=orient, prior=pri)
     new_state = (m, v, rs, step + iters)
     if return_grad:
         return PoseFitGrad(as_dof0(out), rr_out, rt_out, loss, new_state, as_dof0(grad), grad_root)
@@ -662,17 +724,22 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
 
 
 def pose_loss(model, dof, root_rot, root_t, target_pos, weight=None, clip: bool = False, normalize_root: bool = True,
-              rot_joints=None, target_rot=None, rot_weight=None):
+              rot_joints=None, target_rot=None, rot_weight=None, prior=None, prior_weight=None):
     """The per-frame keypoint loss of pose_fit, (...), as the evaluate-only launch of rtg_dof_fit_root_f32,
     differentiable in ``dof``, ``root_rot`` and ``root_t``: the launch computes the three gradients along with the
     loss and backward scales their rows by the upstream cotangent -- for callers who keep their own optimiser.
     ``normalize_root``: the root rotation enters as q / |q| and its gradient is tangent (pose_fit's model of a fitted
     rotation); False: as given, like keypoint_loss.  Under no_grad, or when no input requires grad, it is the plain
-    launch without the gradients.  ``rot_joints``, ``target_rot``, ``rot_weight``: pose_fit's orientation targets (the
-    loss is not differentiable in them)."""
+    launch without the gradients.  ``rot_joints``, ``target_rot``, ``rot_weight``: pose_fit's orientation targets;
+    ``prior``, ``prior_weight``: its posture term (the loss is not differentiable in any of them)."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof, weight)
     fit_root = FIT_ROOT_ROT if normalize_root else 0   # no step is taken: the mask only selects the model
     orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
+    pri = _prior_inputs(model, d, prior, prior_weight, False)
+    if pri is not None:
+        if torch.is_grad_enabled() and (d.requires_grad or rr.requires_grad or rt.requires_grad):
+            return _PriorPoseLoss.apply(model, bool(clip), fit_root, d, rr, rt, tp, w, orient, pri)
+        return _pose_launch(model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach(), orient=orient, prior=pri)[3]
     if torch.is_grad_enabled() and (d.requires_grad or rr.requires_grad or rt.requires_grad):
         if orient is not None:
             return _OrientPoseLoss.apply(model, bool(clip), fit_root, d, rr, rt, tp, w, orient)
@@ -710,6 +777,23 @@ class _OrientPoseLoss(torch.autograd.Function):
         grad, grad_root = ctx.saved_tensors
         c = grad_loss.unsqueeze(-1)
         return None, None, None, grad * c, grad_root[..., 3:] * c, grad_root[..., :3] * c, None, None, None
+
+
+class _PriorPoseLoss(torch.autograd.Function):
+    """_OrientPoseLoss (orient may be None) with the posture term: the evaluate-only launch of rtg_dof_fit_prior_f32."""
+    @staticmethod
+    def forward(ctx, model, clip, fit_root, d, rr, rt, tp, w, orient, prior):
+        _, _, _, loss, grad, grad_root = _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, want_grad=True,
+                                                      orient=orient, prior=prior)
+        ctx.save_for_backward(grad, grad_root)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        grad, grad_root = ctx.saved_tensors
+        c = grad_loss.unsqueeze(-1)
+        return None, None, None, grad * c, grad_root[..., 3:] * c, grad_root[..., :3] * c, None, None, None, None
 
 
 def rescale_motion(topo: Topology, motion, dir=None):

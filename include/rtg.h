@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*); rtg_dof_fit_f32,
-                                  rtg_dof_fit_root_f32 and rtg_dof_fit_orient_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
+                                  rtg_dof_fit_root_f32, rtg_dof_fit_orient_f32 and rtg_dof_fit_prior_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
                                6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
                                5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
                                4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
@@ -171,7 +171,8 @@ int rtg_fk_backward_f32(rtg_topology_t topo, const float *local_rot, const float
  * steps of Adam (no weight decay, no amsgrad) on the angles, k = 1..iters, t = step0 + k, g = dL_f/da_f:
  *     m = beta1 m + (1 - beta1) g,  v = beta2 v + (1 - beta2) g^2,
  *     a -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).
- * The iterate is not projected onto the limits (like the torch loop: the final pose is the clamp the caller applies).
+ * The iterate is not projected onto the limits (like the torch loop: the final pose is the clamp the caller applies);
+ * rtg_dof_fit_prior_f32's RTG_FIT_PROJECT projects it after every step.
  * iters == 0 is the fused evaluate-only call.
  *   target_pos (B,J,3); weight (J) or NULL = all 1; root_rot (B,4), root_t (B,3): given, not fitted;
  *   dof_in (B,J-1) the start; step0: Adam steps already taken; m, v (B,J-1): the moments, read and written in place --
@@ -264,6 +265,45 @@ int rtg_dof_fit_orient_f32(rtg_dof_model_t model, const float *target_pos, const
                            float beta2, float eps, int32_t step0, float *m, float *v, float *root_state,
                            float *dof_out, float *root_rot_out, float *root_t_out, float *loss, float *grad,
                            float *grad_root, rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * rtg_dof_fit_orient_f32 with a posture prior on the angles and, on request, the iterate projected onto the joint
+ * limits (a new symbol under ABI 7).  A DOF that no target observes, or the swivel of a redundant chain, has nothing
+ * to hold it; the prior holds it to a rest pose, to the previous frame's solution or to a clip's smoothed neighbours.
+ * Per frame f
+ *     L_f = rtg_dof_fit_orient_f32's loss + sum_d prior_weight[d] (a_{f,d} - prior[f,d])^2,
+ * a the ITERATE (the parameter), not the clamped angle the forward model uses under `clip`: the term pulls an iterate
+ * that ran past a limit back.  Its gradient 2 prior_weight[d] (a - prior) is added to dL/da_d before the Adam step;
+ * loss and grad at dof_out include the term.
+ *   prior (B,J-1) device memory, or NULL: the term is absent (not zero times something); it may alias dof_in or
+ *   dof_out ("stay near where you started": a tile reads its own rows before it writes them).  prior_weight (J-1)
+ *   device memory, or NULL = all 1; it needs prior.
+ *   flags: RTG_FIT_PROJECT -- after each Adam step of an angle, a <- a < lower ? lower : (a > upper ? upper : a)
+ *   (torch.clamp: NaN passes).  The moments are not touched: this is the loop `opt.step(); a.clamp_(lower, upper)`.
+ *   It needs a model with limits, whatever `clip` is.  iters == 0 projects nothing: dof_out carries dof_in's bits.
+ *   Everything else is rtg_dof_fit_orient_f32's.  The root is not regularised here: weight[0] with target_pos[f,0]
+ *   is a prior on its translation, an orientation target on joint 0 one on its rotation.
+ * Guarantees: (a) prior == NULL with flags == 0 gives rtg_dof_fit_orient_f32's outputs bit for bit.  (b) With
+ * prior_weight all zero and finite inputs every output equals (a)'s as a number (a zero may change sign).  (c) A DOF
+ * to which rtg_dof_fit_orient_f32 gives a gradient of +-0 gets exactly fl(2 prior_weight[d]) * fl(a - prior) in
+ * float32, one rounding each; with prior_weight[d] == 0 it still gets +-0 and from a zero state keeps its bits.
+ * (d) A frame depends on its own rows alone, runs are bit-identical (the loss keeps one summation order), and n
+ * launches of one step that carry (m, v, root_state, step0) equal one launch of n steps, with and without the
+ * projection.  (e) After a launch with RTG_FIT_PROJECT and iters >= 1 every angle of dof_out that is not NaN lies in
+ * [lower, upper] exactly.  (f) A NaN prior row makes that frame's loss and gradient NaN, and no other frame's.
+ * Errors: rtg_dof_fit_orient_f32's, and unknown flags bits, prior_weight without prior, RTG_FIT_PROJECT on a model
+ * without limits -> RTG_ERR_INVALID_ARGUMENT; all before any device work.  For a one-joint model neither pointer is
+ * dereferenced.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------- */
+#define RTG_FIT_PROJECT 1   /* clamp each angle to its limits after its Adam step */
+int rtg_dof_fit_prior_f32(rtg_dof_model_t model, const float *target_pos, const float *weight,
+                          const int32_t *rot_joint, const float *target_rot, const float *rot_weight, int32_t K,
+                          const float *prior, const float *prior_weight, int32_t flags, const float *root_rot,
+                          const float *root_t, const float *dof_in, int64_t B, int clip, int32_t fit_root,
+                          int32_t iters, float lr, float lr_root_t, float lr_root_rot, float beta1, float beta2,
+                          float eps, int32_t step0, float *m, float *v, float *root_state, float *dof_out,
+                          float *root_rot_out, float *root_t_out, float *loss, float *grad, float *grad_root,
+                          rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * SkeletonState.retarget_to (poselib skeleton3d.py:742-889): the generic skeleton-to-skeleton retarget, rotations

@@ -29,6 +29,12 @@
               set), and the composed iteration (ops.dof_forward_kinematics, the torch loss with the rotation term,
               backward() with both cotangents, fused torch Adam with three groups), interleaved rounds
   orient_fit_traffic -- a few launches of rtg_dof_fit_orient_f32 (K = 8) and nothing else, for a counter run of its own
+  prior_fit -- the pose fit with the posture prior and the projection (rtg_dof_fit_prior_f32, fit_root = 3, same shapes
+              and start as `pose_fit`) per iteration: a prior, a prior and the projection, the projection alone, both
+              with K = 5 links, against rtg_dof_fit_root_f32 of this build and of the build RTG_PARENT_LIB names (when
+              set), rtg_dof_fit_orient_f32 at K = 5, and the composed iteration with the same term and clamp,
+              interleaved rounds
+  prior_fit_traffic -- a few launches of rtg_dof_fit_prior_f32 and nothing else, for a counter run of its own
   motion_sample -- the fused motion sampler (rtg_motion_sample_f32, C ABI, preallocated outputs; Hu v5, 64 clips x 4096
               frames, N=262144 queries; uniform / random / frame-instant queries, with global outputs + velocities
               and local only) against the composed chain (index rule in torch, index_select, quat_slerp,
@@ -760,6 +766,93 @@ def orient_fit_traffic(B=262144, iters=32, K=8):
     torch.cuda.synchronize()
     return {"B": B, "K": K, "copy_bytes_each_way": 4 << 26,
             "launches": "3 x 256 MiB copy, 4 x iters=%d, K=%d without a state (dof, root, loss out)" % (iters, K)}
+
+
+def _prior_fit_call(M, tgt, joints, trot, prior, flags, rr0, rt0, start, B, iters, mask, outs):
+    import ctypes
+    from rtg.runtime import ptr, stream_handle
+    f = _lib.lib().rtg_dof_fit_prior_f32
+    K = len(joints)
+    jarr = (ctypes.c_int32 * max(K, 1))(*joints)
+    args = (M.handle, ptr(tgt), None, jarr, ptr(trot) if K else None, None, K, ptr(prior), None, flags, ptr(rr0), ptr(rt0),
+            ptr(start), B, 1, mask, iters, 0.02, 0.02, 0.02, 0.9, 0.999, 1e-8, 0, None, None, None, *(ptr(o) for o in outs),
+            stream_handle())
+    _lib.check(f(*args))
+    return lambda: f(*args)
+
+
+def _prior_rows(start):
+    """A prior 0.1 rad (rms) around the start: any finite rows cost the same."""
+    gen = torch.Generator(device="cuda").manual_seed(29)
+    return (start + 0.1 * torch.randn(start.shape, device="cuda", generator=gen)).contiguous()
+
+
+def prior_fit(B=262144, rounds=4, iters=32):
+    """The pose fit with the posture prior (rtg_dof_fit_prior_f32, fit_root = 3, C ABI, preallocated outputs, 33-link
+    Hu, clip on, no state) per iteration: with a prior, with a prior and the projection, with both and K = 5 links,
+    against rtg_dof_fit_root_f32 of this build, of the build RTG_PARENT_LIB names (when set), and the composed iteration
+    with the same term and clamp; interleaved rounds."""
+    M, tgt, rr0, rt0, start, g_rot = _pose_fit_setup(B, want_rot=True)
+    J = 33
+    new = lambda *s: torch.empty(s, device="cuda")
+    outs = (new(B, 32), new(B, 4), new(B, 3), new(B), None, None)
+    prior = _prior_rows(start)
+    j5 = ORIENT_LINKS[5]
+    trot = g_rot[:, list(j5)].contiguous()
+    calls = {"root_us_per_iteration": _pose_fit_call(M, tgt, rr0, rt0, start, B, iters, 3, outs),
+             "prior_us_per_iteration": _prior_fit_call(M, tgt, (), None, prior, 0, rr0, rt0, start, B, iters, 3, outs),
+             "prior_project_us_per_iteration": _prior_fit_call(M, tgt, (), None, prior, 1, rr0, rt0, start, B, iters, 3, outs),
+             "project_only_us_per_iteration": _prior_fit_call(M, tgt, (), None, None, 1, rr0, rt0, start, B, iters, 3, outs),
+             "orient_k5_us_per_iteration": _orient_fit_call(M, tgt, j5, trot, rr0, rt0, start, B, iters, 3, outs),
+             "orient_k5_prior_project_us_per_iteration": _prior_fit_call(M, tgt, j5, trot, prior, 1, rr0, rt0, start, B,
+                                                                         iters, 3, outs)}
+    parent = os.environ.get("RTG_PARENT_LIB")
+    if parent:
+        calls["parent_root_us_per_iteration"] = _other_build_pose_fit(parent, tgt, rr0, rt0, start, B, iters, outs)
+    a, q, t = (x.clone().requires_grad_(True) for x in (start, rr0, rt0))
+    opt = torch.optim.Adam([dict(params=[a]), dict(params=[t]), dict(params=[q])], lr=0.02, fused=True)
+    hu = __import__("importlib").import_module("retarget.robot_config.Hu")
+    lo, hi = (torch.as_tensor(np.asarray(x), dtype=torch.float32, device="cuda") for x in (hu.Hu_DOF_LOWER, hu.Hu_DOF_UPPER))
+
+    def composed():
+        opt.zero_grad(set_to_none=True)
+        gp = ops.dof_forward_kinematics(M, a, torch.nn.functional.normalize(q, dim=-1, eps=1e-9), t, clip=True)[1]
+        ((gp - tgt).square().sum() + (a - prior).square().sum()).backward()
+        opt.step()
+        with torch.no_grad():
+            q.copy_(torch.nn.functional.normalize(q, dim=-1, eps=1e-9))
+            a.clamp_(lo, hi)
+
+    res = {k: [] for k in calls}
+    res["composed_prior_project_us_per_iteration"] = []
+    for _ in range(rounds):   # interleaved: all see the same box state
+        for k, call in calls.items():
+            res[k].append(time_events(call, reps=5, warm=1) * 1e3 / iters)
+        res["composed_prior_project_us_per_iteration"].append(time_events(composed, reps=10, warm=2) * 1e3)
+    rd, wr = J * 12 + (J - 1) * 4 + 28, (J - 1) * 4 + 4 + 28
+    return {"B": B, "J": J, "iters": iters, **res, "parent_lib": parent, "links": list(j5),
+            "algorithmic_bytes_per_frame": {"read": rd + (J - 1) * 4, "of_which_prior": (J - 1) * 4, "read_per_link": 16,
+                                            "written": wr}}
+
+
+def prior_fit_traffic(B=262144, iters=32):
+    """A few launches of rtg_dof_fit_prior_f32 (fit_root = 3, a prior and the projection, K = 0, no state) and nothing
+    else, for a counter run of its own (FETCH_SIZE or WRITE_SIZE, one per run) against the algorithmic bytes `prior_fit`
+    prints."""
+    M, tgt, rr0, rt0, start = _pose_fit_setup(B)
+    new = lambda *s: torch.empty(s, device="cuda")
+    outs = (new(B, 32), new(B, 4), new(B, 3), new(B), None, None)
+    prior = _prior_rows(start)
+    src, dst = torch.randn(1 << 26, device="cuda"), torch.empty(1 << 26, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(3):   # known bytes: the counters' unit
+        dst.copy_(src)
+    call = _prior_fit_call(M, tgt, (), None, prior, 1, rr0, rt0, start, B, iters, 3, outs)
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    return {"B": B, "copy_bytes_each_way": 4 << 26,
+            "launches": "3 x 256 MiB copy, 4 x iters=%d with a prior and the projection, no state (dof, root, loss out)" % iters}
 
 
 def motion_sample(N=262144, rounds=4, clips=64, frames=4096):
