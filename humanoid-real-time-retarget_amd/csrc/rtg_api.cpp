@@ -289,11 +289,72 @@ int check_fk_backward(const char *fn, int64_t B, const void *grad_g_rot, const v
     return RTG_OK;
 }
 
+// rtg_dof_fit_apart_f32's host struct, checked as far as no handle is needed, into the launch's arguments; `on`: the
+// term is there (a sphere, and a pair or a plane with mask bits)
+int fill_fit_apart(const char *fn, const rtg_fit_apart &a, DofFitApartArgs &Z, bool &on)
+{
+    if (a.S < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: S=%d < 0", fn, a.S);
+    if (a.Pn < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: Pn=%d < 0", fn, a.Pn);
+    if (a.S > RTG_FIT_MAX_SPHERES)
+        return fail(RTG_ERR_UNSUPPORTED, "%s: S=%d spheres, at most %d", fn, a.S, RTG_FIT_MAX_SPHERES);
+    if (a.Pn > RTG_FIT_MAX_PAIRS)
+        return fail(RTG_ERR_UNSUPPORTED, "%s: Pn=%d pairs, at most %d", fn, a.Pn, RTG_FIT_MAX_PAIRS);
+    if (a.S > 0 && (!a.sphere_link || !a.sphere))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: S=%d with sphere_link or sphere NULL", fn, a.S);
+    if (a.Pn > 0 && !a.pair) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: Pn=%d with pair NULL", fn, a.Pn);
+    if (!std::isfinite(a.margin)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: margin=%g must be finite", fn, (double)a.margin);
+    Z.S = a.S;
+    Z.Pn = a.Pn;
+    Z.margin = a.margin;
+    for (int s = 0; s < a.S; ++s) {
+        const float *row = a.sphere + 4 * s;
+        if (!std::isfinite(row[0]) || !std::isfinite(row[1]) || !std::isfinite(row[2]) || !std::isfinite(row[3]))
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: sphere[%d] is not finite", fn, s);
+        if (row[3] < 0.0f)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: sphere[%d] has the negative radius %g", fn, s, (double)row[3]);
+        if (a.sphere_link[s] < 0)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: sphere_link[%d]=%d < 0", fn, s, a.sphere_link[s]);
+        Z.link[s] = a.sphere_link[s];
+        for (int c = 0; c < 4; ++c) Z.sphere[s][c] = row[c];
+    }
+    for (int p = 0; p < a.Pn; ++p) {
+        const int32_t i = a.pair[2 * p], k = a.pair[2 * p + 1];
+        if (i < 0 || i >= a.S || k < 0 || k >= a.S)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: pair[%d]=(%d, %d) is outside 0..%d", fn, p, i, k, a.S - 1);
+        if (i == k) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: pair[%d] joins sphere %d with itself", fn, p, i);
+        const float w = a.pair_weight ? a.pair_weight[p] : 1.0f;
+        if (!std::isfinite(w) || w < 0.0f)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: pair_weight[%d]=%g must be finite and not negative", fn, p, (double)w);
+        Z.pair[p] = i | (k << 8);
+        Z.pair_weight[p] = w;
+    }
+    if (a.plane) {   // without one the mask and the weight are not looked at
+        const float *n = a.plane;
+        if (!std::isfinite(n[0]) || !std::isfinite(n[1]) || !std::isfinite(n[2]) || !std::isfinite(n[3]))
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: plane is not finite", fn);
+        const double len = std::sqrt((double)n[0] * n[0] + (double)n[1] * n[1] + (double)n[2] * n[2]);
+        if (!(len > 0.0)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: plane normal has zero length", fn);
+        if (!std::isfinite(a.floor_weight) || a.floor_weight < 0.0f)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: floor_weight=%g must be finite and not negative", fn,
+                        (double)a.floor_weight);
+        if (a.S < 32 && (a.floor_mask >> a.S) != 0u)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: floor_mask=0x%x has bits at or above S=%d", fn, a.floor_mask, a.S);
+        for (int c = 0; c < 3; ++c) Z.plane[c] = (float)(n[c] / len);
+        Z.plane[3] = n[3];
+        Z.floor_mask = a.floor_mask;
+        Z.floor_weight = a.floor_weight;
+    }
+    on = a.S > 0 && (a.Pn > 0 || Z.floor_mask != 0u);
+    return RTG_OK;
+}
+
 // rtg_dof_fit_f32 (R == nullptr), rtg_dof_fit_root_f32 (R: the root block), rtg_dof_fit_orient_f32 (O too: the
-// orientation block, rot_joint its K host-side joint indices) and rtg_dof_fit_prior_f32 (H too: the posture prior and
-// the projection): one checked path, five kernels
+// orientation block, rot_joint its K host-side joint indices), rtg_dof_fit_prior_f32 (H too: the posture prior and
+// the projection) and rtg_dof_fit_apart_f32 (apart too: the keep-apart spheres and the floor): one checked path,
+// seven kernels
 int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const DofFitRootArgs *R, rtg_stream_t stream,
-                DofFitOriArgs *O = nullptr, const int32_t *rot_joint = nullptr, const DofFitPriorArgs *H = nullptr)
+                DofFitOriArgs *O = nullptr, const int32_t *rot_joint = nullptr, const DofFitPriorArgs *H = nullptr,
+                const rtg_fit_apart *apart = nullptr)
 {
     // everything that needs no handle first
     if (A.B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)A.B);
@@ -344,6 +405,9 @@ int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const
             return fail(RTG_ERR_INVALID_ARGUMENT, "%s: prior_weight given without prior", fn);
         if (!H->prior && !H->flags) H = nullptr;   // neither term nor projection: rtg_dof_fit_orient_f32 itself
     }
+    DofFitApartArgs Z{};
+    bool keep_apart = false;   // no sphere, or neither a pair nor a floor: rtg_dof_fit_prior_f32 itself
+    if (apart) RTG_CHECK(fill_fit_apart(fn, *apart, Z, keep_apart));
     if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL model", fn);
     if (clip && !m->has_limits)
         return fail(RTG_ERR_INVALID_ARGUMENT, "%s: clip_angles requested but the model has no DOF limits", fn);
@@ -355,6 +419,9 @@ int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const
     for (int k = 0; O && k < O->K; ++k)
         if (O->joint[k] >= J)
             return fail(RTG_ERR_INVALID_ARGUMENT, "%s: rot_joint[%d]=%d is outside 0..%d", fn, k, O->joint[k], J - 1);
+    for (int s = 0; s < Z.S; ++s)
+        if (Z.link[s] >= J)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: sphere_link[%d]=%d is outside 0..%d", fn, s, Z.link[s], J - 1);
     if (A.B == 0) return RTG_OK;
     if (J > 1 && !A.dof_in) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
     if (J == 1) {   // no angles: only a fitted root can step; the kernel's unconditional first-element loads get readable memory
@@ -364,7 +431,11 @@ int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const
         if (!A.loss && !root_out) return RTG_OK;
         H = nullptr;   // no angles: nothing to hold or to project, and neither pointer is dereferenced
     }
-    if (H)
+    if (keep_apart)
+        RTG_TRY(launch_dof_fit_apart(m->topo->view(), m->view(), clip != 0, A, *R, *O, H ? *H : DofFitPriorArgs{}, Z,
+                                     as_stream(stream)),
+                O->K > 0 ? "k_dof_fit_orient_apart" : "k_dof_fit_apart");
+    else if (H)
         RTG_TRY(launch_dof_fit_prior(m->topo->view(), m->view(), clip != 0, A, *R, *O, *H, as_stream(stream)),
                 O->K > 0 ? "k_dof_fit_orient_prior" : "k_dof_fit_prior");
     else if (O && O->K > 0)   // K == 0 is the pose fit itself: its kernel measured 250 us per iteration against 313 through the oriented one
@@ -676,6 +747,22 @@ int rtg_dof_fit_prior_f32(rtg_dof_model_t m, const float *target_pos, const floa
     DofFitOriArgs O{target_rot, rot_weight, K, {}};
     const DofFitPriorArgs H{prior, prior_weight, flags};
     return run_dof_fit("rtg_dof_fit_prior_f32", m, clip, A, &R, stream, &O, rot_joint, &H);
+}
+
+int rtg_dof_fit_apart_f32(rtg_dof_model_t m, const float *target_pos, const float *weight, const int32_t *rot_joint,
+                          const float *target_rot, const float *rot_weight, int32_t K, const float *prior,
+                          const float *prior_weight, int32_t flags, const float *root_rot, const float *root_t,
+                          const float *dof_in, int64_t B, int clip, int32_t fit_root, int32_t iters, float lr,
+                          float lr_root_t, float lr_root_rot, float beta1, float beta2, float eps, int32_t step0, float *mo,
+                          float *v, float *root_state, float *dof_out, float *root_rot_out, float *root_t_out, float *loss,
+                          float *grad, float *grad_root, const rtg_fit_apart *apart, rtg_stream_t stream)
+{
+    const DofFitArgs A{target_pos, weight, root_rot, root_t, dof_in, B, iters, step0, lr, beta1, beta2, eps,
+                       mo, v, dof_out, loss, grad};
+    const DofFitRootArgs R{fit_root, lr_root_t, lr_root_rot, root_state, root_rot_out, root_t_out, grad_root};
+    DofFitOriArgs O{target_rot, rot_weight, K, {}};
+    const DofFitPriorArgs H{prior, prior_weight, flags};
+    return run_dof_fit("rtg_dof_fit_apart_f32", m, clip, A, &R, stream, &O, rot_joint, &H, apart);
 }
 
 // ---------------------------------------------------------------- SkeletonState.retarget_to

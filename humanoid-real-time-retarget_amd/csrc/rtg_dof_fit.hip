@@ -43,6 +43,21 @@
 // they may alias dof_in or dof_out.  The loss adds the term per sub-lane (its DOFs u, u + L, ... in index order) to that
 // lane's position part.
 //
+// k_dof_fit_apart_group / k_dof_fit_orient_apart_group (rtg_dof_fit_apart_f32, K == 0 / K > 0) are the prior tiles with
+// keep-apart spheres and a floor (APART): S <= RTG_FIT_MAX_SPHERES spheres ride on links, c_s = P_j + rot(G_j, o_s),
+// and L_f gains sum_p pair_weight[p] max(0, r_a + r_b + margin - |c_a - c_b|)^2 over Pn <= RTG_FIT_MAX_PAIRS pairs and
+// floor_weight max(0, r_s + h0 - n . c_s)^2 over the spheres of a mask.  The term is a pass between the forward sweep
+// and the residuals (apart_pass): sub-lane u of a frame owns the spheres u, u + L, ...; it writes their centres, and
+// once the frame's centres are in LDS walks the pair list -- a wave-uniform loop, the lane's part under a predicate --
+// and the floor to form g_s = dL/dc_s of its spheres (pairs in pair order, then the floor; no atomics), which then
+// takes c_s's place in the image.  fit_residual adds the g_s of a link's spheres to the link's residual row in sphere
+// order (row 0 for the root's), and a joint's spheres with a non-zero offset add sum_s d(g_s . rot(G_j, o_s)) / dG_j --
+// joint_adjoint's closed form -- to the joint's own upstream rotation adjoint, where orient_adjoint's enters, from G_j
+// before the row is overwritten; a zero offset adds nothing there, not a zero.  The loss: pair p is counted by the
+// owner of a_p, a floor term by the sphere's owner, and the lane's part joins its position part like the prior's.
+// Spheres, pairs and plane travel in the launch arguments (host-checked) and are read with constant indices only, on
+// their way into small LDS tables; the per-joint table holds the bit mask of a joint's spheres.
+//
 // LDS images of a tile: FitImages below (every image starts 16-byte aligned).
 // 33-link Hu, F = 16 (10 steps): 29.3 KiB; a 64-joint chain, F = 8, 64 steps: 43.9 KiB (the largest: gsteps <= J).
 // With the root image and the two more step sizes per Adam step: 31.1 KiB (still 5 tiles per CU) and 45.1 KiB.
@@ -51,6 +66,10 @@
 // PRIOR adds 4 F (J - 1) + 4 (J - 1) bytes: Hu 34,016 B (K = 8: 36,336 B), the chain 48,416 B (K = 8: 49,952 B).
 // Measured: a Hu tile keeps its fifth place on a CU up to 32,000 B of dynamic LDS, not 32,768, so the
 // PRIOR tiles -- and every ORI tile -- run four to a CU, and that is where their time over k_dof_fit_root_group sits.
+// APART adds ApartImages behind them, sized by the launch's own S and Pn: 12 F S (centres) + 16 S + 4 S + 4 J + 8 Pn
+// bytes, each image padded to 16.  Hu with S = 16, Pn = 32: 3,072 + 256 + 64 + 144 + 256 = 3,792 B, a tile of
+// 37,808 B (K = 8: 40,128 B) -- under the 40,960 B that keep four tiles on a CU; the chain: 2,368 B, 50,784 B
+// (K = 8: 52,320 B).
 //
 // Arithmetic: as in rtg_fk_grad.hip no operation order is owed to a reference (explicit fmaf, the device sincosf,
 // -ffp-contract=fast); the forward here is the float32 restatement of rtg_dof_fk_f32's, not its bit-exact f64 sincos.
@@ -132,6 +151,30 @@ struct FitImages {
     }
 };
 
+// APART: the keep-apart images, carved behind the tile's FitImages (base: the first float after them), so every offset
+// there is what it is without them.  A carve of their own: the tiles without the term do not see it at all, and their
+// code is the parent's instruction for instruction
+struct ApartImages {
+    float *C;        // [F S 3] the sphere centres, then in place their gradients g_s
+    f4v *sph;        // [S] per sphere {offset in its link's frame, radius}
+    int *slink;      // [S] a sphere's joint
+    int *jtab;       // [J] per joint the bit mask of its spheres, and << 16 of those with a non-zero offset
+    int *pair;       // [Pn, padded to whole fours with 0] a | b << 8
+    float *pairw;    // [Pn, padded likewise with 0] pair_weight
+    size_t floats;
+    __host__ __device__ ApartImages(float *base, int J, int F, int S, int Pn)
+    {
+        LdsCarve c(base);
+        C = c.take<float>((size_t)3 * F * S);
+        sph = c.take<f4v>(S);
+        slink = c.take<int>(S);
+        jtab = c.take<int>(J);
+        pair = c.take<int>(Pn);
+        pairw = c.take<float>(Pn);
+        floats = c.floats;
+    }
+};
+
 // G_0 = q / max(|q|, 1e-9) of a fitted root rotation: no sign flip (q and -q are one rotation and the iterate stays
 // continuous); NaN passes
 RTG_DEV f4v root_unit(f4v q)
@@ -179,8 +222,9 @@ RTG_DEV void fit_forward(const FitImages &I, int J, int gsteps, bool live, int f
 
 // positions -> residual adjoints in place (the root's row stays where the root's adjoint is not taken; ROOT: it is
 // dL/dt's own term); returns this lane's part of the frame's loss, its joints in index order
-template <int F, bool ROOT>
-RTG_DEV float fit_residual(const FitImages &I, int J, bool live, int fr, int sub)
+// APART (S spheres): the row then takes the centre gradients g_s of the link's spheres, in sphere order
+template <int F, bool ROOT, bool APART = false>
+RTG_DEV float fit_residual(const FitImages &I, int J, bool live, int fr, int sub, const ApartImages *X = nullptr, int S = 0)
 {
     using G = Grp<F>;
     float acc = 0.0f;
@@ -193,12 +237,131 @@ RTG_DEV float fit_residual(const FitImages &I, int J, bool live, int fr, int sub
             acc = __builtin_fmaf(w, fdot3(d, d), acc);
             if (ROOT || j != 0) {
                 const float w2 = 2.0f * w;
-                pj[0] = w2 * d.x; pj[1] = w2 * d.y; pj[2] = w2 * d.z;
+                if constexpr (APART) {
+                    V r{w2 * d.x, w2 * d.y, w2 * d.z};
+                    for (int m = X->jtab[j] & 0xFFFF; m; m &= m - 1) {
+                        const float *g = X->C + 3 * (fr * S + __builtin_ctz(m));
+                        r.x += g[0]; r.y += g[1]; r.z += g[2];
+                    }
+                    pj[0] = r.x; pj[1] = r.y; pj[2] = r.z;
+                } else {
+                    pj[0] = w2 * d.x; pj[1] = w2 * d.y; pj[2] = w2 * d.z;
+                }
             }
         }
     }
     wave_sync();
     return acc;
+}
+
+// APART: the keep-apart pass between the forward sweep and the residuals.  Sub-lane u of a frame owns the spheres
+// u, u + L, ...: it writes their centres c_s = P_j + rot(G_j, o_s) from the forward's rows, then -- the centres of the
+// whole frame in LDS -- walks the pair list (wave-uniform, the lane's part under a predicate) and the floor and forms
+// g_s = dL/dc_s of each of its spheres: its pairs' terms in pair order, then the floor's.  g_s takes c_s's place in
+// the image once every walk has read the centres.  Returns the lane's part of the term's loss: pair p by the owner of
+// a_p, in pair order, then the lane's floor terms in sphere order.  h = max(0, .) as torch.clamp does it: NaN passes.
+template <int F>
+RTG_DEV float apart_pass(const FitImages &I, const ApartImages &X, const DofFitApartArgs &Z, int J, bool live, int fr,
+                         int sub)
+{
+    using G = Grp<F>;
+    constexpr int NS = RTG_FIT_MAX_SPHERES / G::L;
+    const int S = Z.S, base = fr * J;
+    float *C = X.C + 3 * fr * S;
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int s = k * G::L + sub;
+            if (s < S) {
+                const f4v o = X.sph[s];
+                const int j = X.slink[s];
+                const V rv = qrotate(q_of(I.G[base + j]), V{o.x, o.y, o.z});
+                const float *pj = I.P + 3 * (base + j);
+                C[3 * s] = rv.x + pj[0]; C[3 * s + 1] = rv.y + pj[1]; C[3 * s + 2] = rv.z + pj[2];
+            }
+        }
+    }
+    wave_sync();
+    V g[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) g[k] = V{0.0f, 0.0f, 0.0f};
+    float acc = 0.0f;
+    // every lane computes every pair and takes its part by selects: no branch in the body, so the steps of several
+    // pairs overlap (one wave per SIMD: a chain of dependent steps per pair would cost its full latency 32 times)
+    // (four pairs per trip, the table padded with pairs of weight 0 that join sphere 0 with itself: they add +-0)
+    for (int p0 = 0; p0 < Z.Pn; p0 += 4) {
+#pragma unroll
+      for (int p = p0; p < p0 + 4; ++p) {
+        const int ab = __builtin_amdgcn_readfirstlane(X.pair[p]);
+        const int a = ab & 0xFF, b = ab >> 8;
+        const bool ia = (a & (G::L - 1)) == sub, ib = (b & (G::L - 1)) == sub;
+        const float w = X.pairw[p];
+        const float *ca = C + 3 * a, *cb = C + 3 * b;
+        const V d{ca[0] - cb[0], ca[1] - cb[1], ca[2] - cb[2]};
+        const float dd = __builtin_sqrtf(fdot3(d, d));
+        const float x = (X.sph[a].w + X.sph[b].w + Z.margin) - dd;
+        const float h = x < 0.0f ? 0.0f : x;
+        const float c = -2.0f * w * h / (dd < 1e-9f ? 1e-9f : dd);
+        const V t{c * d.x, c * d.y, c * d.z};
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {   // a != b: a lane owns at most one end of the pair in slot k
+            const bool ka = ia && k == (a >> G::LOG_L), kb = ib && k == (b >> G::LOG_L);
+            g[k].x += ka ? t.x : (kb ? -t.x : 0.0f);
+            g[k].y += ka ? t.y : (kb ? -t.y : 0.0f);
+            g[k].z += ka ? t.z : (kb ? -t.z : 0.0f);
+        }
+        acc = ia ? __builtin_fmaf(w, h * h, acc) : acc;
+      }
+    }
+    if (Z.floor_mask != 0u && live) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int s = k * G::L + sub;
+            if (s < S && ((Z.floor_mask >> s) & 1u)) {
+                const V n{Z.plane[0], Z.plane[1], Z.plane[2]};
+                const float x = (X.sph[s].w + Z.plane[3]) - fdot3(n, V{C[3 * s], C[3 * s + 1], C[3 * s + 2]});
+                const float h = x < 0.0f ? 0.0f : x;
+                const float c = -2.0f * Z.floor_weight * h;
+                acc = __builtin_fmaf(Z.floor_weight, h * h, acc);
+                g[k].x += c * n.x; g[k].y += c * n.y; g[k].z += c * n.z;
+            }
+        }
+    }
+    wave_sync();   // every walk has read the centres: the gradients take their place
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int s = k * G::L + sub;
+            if (s < S) { C[3 * s] = g[k].x; C[3 * s + 1] = g[k].y; C[3 * s + 2] = g[k].z; }
+        }
+    }
+    wave_sync();
+    return acc;
+}
+
+// APART: joint j's part of dL/dG_j from its spheres with a non-zero offset, sum_s d(g_s . rot(G_j, o_s)) / dG_j in
+// sphere order -- joint_adjoint's closed form with Gp -> G_j, zl -> o_s, pb -> g_s -- from the forward's G_j (the
+// caller forms it before the row is overwritten); a joint without such a sphere: +0, nothing read
+RTG_DEV f4v apart_adjoint(const FitImages &I, const ApartImages &X, int S, int fr, int row, int j)
+{
+    f4v out{0.0f, 0.0f, 0.0f, 0.0f};
+    int m = (int)((unsigned)X.jtab[j] >> 16);
+    if (m == 0) return out;
+    const f4v Gj = I.G[row];
+    const V a{Gj.x, Gj.y, Gj.z};
+    for (; m; m &= m - 1) {
+        const int s = __builtin_ctz(m);
+        const f4v o = X.sph[s];
+        const float *gs = X.C + 3 * (fr * S + s);
+        const V zl{o.x, o.y, o.z}, pb{gs[0], gs[1], gs[2]};
+        const V c{zl.y * pb.z - zl.z * pb.y, zl.z * pb.x - zl.x * pb.z, zl.x * pb.y - zl.y * pb.x};
+        const float gv = fdot3(pb, zl), av = fdot3(a, zl), ga = fdot3(pb, a);
+        out.x += 2.0f * __builtin_fmaf(Gj.w, c.x, __builtin_fmaf(ga, zl.x, __builtin_fmaf(av, pb.x, -gv * a.x)));
+        out.y += 2.0f * __builtin_fmaf(Gj.w, c.y, __builtin_fmaf(ga, zl.y, __builtin_fmaf(av, pb.y, -gv * a.y)));
+        out.z += 2.0f * __builtin_fmaf(Gj.w, c.z, __builtin_fmaf(ga, zl.z, __builtin_fmaf(av, pb.z, -gv * a.z)));
+        out.w += 2.0f * __builtin_fmaf(Gj.w, gv, fdot3(a, c));
+    }
+    return out;
 }
 
 // ORI: joint j's own upstream rotation adjoint, -8 w c Rh with c = <G_j, Rh>, from the forward's G_j (the caller
@@ -264,12 +427,15 @@ RTG_DEV float adam_step(const AdamStep &S, float step, float g, float &m, float 
 // (the unnormalised model, as rtg_dof_fk_backward_f32 reports it).  ORI: an oriented root's own adjoint leads the pull
 // (G_0 as the model uses it: the row the forward sweep preset, which nothing has overwritten).  EVAL: grad_root's row into the Rs image, else the
 // Adam steps of the fitted blocks, q renormalised after its step.
-template <bool EVAL, bool ORI>
-RTG_DEV void fit_root_reverse(const FitImages &I, int J, int K, int fr, int first_child, int fit_root, const AdamStep &S)
+template <bool EVAL, bool ORI, bool APART = false>
+RTG_DEV void fit_root_reverse(const FitImages &I, int J, int K, int fr, int first_child, int fit_root, const AdamStep &S,
+                              const ApartImages *X = nullptr, int NSPH = 0)
 {
     const int base = fr * J;
     V pb;
-    f4v g = child_pull(orient_adjoint<ORI>(I, K, fr, base, 0), I.G, I.P, base, 0, first_child, I.nsib, pb);
+    f4v own = orient_adjoint<ORI>(I, K, fr, base, 0);
+    if constexpr (APART) own += apart_adjoint(I, *X, NSPH, fr, base, 0);   // the root's spheres: G_0 as the model uses it
+    f4v g = child_pull(own, I.G, I.P, base, 0, first_child, I.nsib, pb);
     const f4v q = I.Rq[fr];
     if (fit_root & RTG_FIT_ROOT_ROT) {
         const float n = __builtin_sqrtf(fdot4(q_of(q), q_of(q)));
@@ -308,9 +474,10 @@ RTG_DEV void fit_root_reverse(const FitImages &I, int J, int K, int fr, int firs
 // angle's gradient where that appears (a: the iterate, not the clamped angle), and with `project` the angle is clamped
 // to its limits after its Adam step (torch.clamp: NaN passes; the moments are not touched).  The two reads of the prior
 // images are issued at the top of the joint's step, off the chain that ends in angle_grad.
-template <bool CLIP, bool EVAL, int F, bool ROOT, bool ORI, bool PRIOR = false>
+// APART (NSPH spheres): a joint's spheres with a non-zero offset add apart_adjoint to its own rotation adjoint.
+template <bool CLIP, bool EVAL, int F, bool ROOT, bool ORI, bool PRIOR = false, bool APART = false>
 RTG_DEV void fit_reverse(const FitImages &I, int J, int K, int gsteps, bool live, int fr, int sub, const AdamStep &S,
-                         int fit_root, bool prior = false, bool project = false)
+                         int fit_root, bool prior = false, bool project = false, const ApartImages *X = nullptr, int NSPH = 0)
 {
     using G = Grp<F>;
     const int base = fr * J, nd = J - 1;
@@ -326,8 +493,9 @@ RTG_DEV void fit_reverse(const FitImages &I, int J, int K, int gsteps, bool live
                 pw = I.Pw[j - 1];
             }
             V pb;
-            const f4v a = child_pull(orient_adjoint<ORI>(I, K, fr, base + j, j), I.G, I.P, base, j,
-                                     (e.code >> 16) & 0xFF, I.nsib, pb);
+            f4v own = orient_adjoint<ORI>(I, K, fr, base + j, j);
+            if constexpr (APART) own += apart_adjoint(I, *X, NSPH, fr, base + j, j);
+            const f4v a = child_pull(own, I.G, I.P, base, j, (e.code >> 16) & 0xFF, I.nsib, pb);
             const Q Gp = q_of(I.G[base + p]), Gj = q_of(I.G[base + j]);
             const f4v t = I.tab[j];
             const int i = fr * nd + j - 1;
@@ -353,7 +521,7 @@ RTG_DEV void fit_reverse(const FitImages &I, int J, int K, int gsteps, bool live
                 I.A[i] = x;
             }
         }
-        if (ROOT && live && j == 0) fit_root_reverse<EVAL, ORI>(I, J, K, fr, (e.code >> 16) & 0xFF, fit_root, S);
+        if (ROOT && live && j == 0) fit_root_reverse<EVAL, ORI, APART>(I, J, K, fr, (e.code >> 16) & 0xFF, fit_root, S, X, NSPH);
         wave_sync();   // this step's rows before the next step's parents pull them (other lanes)
     }
 }
@@ -363,13 +531,16 @@ using OriRows = LaneRows<f4v, 2>;           // a tile's target rotations: F K <=
 
 // one tile of the fit; ROOT: the root's rows come from the root image and its adjoints are taken (R: the root's
 // arguments, not looked at otherwise); ORI: with orientation targets (O: theirs, likewise); PRIOR: with the posture
-// prior and the projection onto the limits (H: theirs, likewise; what H asks for is wave-uniform, like fit_root)
-template <bool CLIP, int F, bool ROOT, bool ORI, bool PRIOR = false>
+// prior and the projection onto the limits (H: theirs, likewise; what H asks for is wave-uniform, like fit_root);
+// APART: with keep-apart spheres and a floor (Z: theirs, likewise; S >= 1 and a pair or the plane: the host sees to it)
+template <bool CLIP, int F, bool ROOT, bool ORI, bool PRIOR = false, bool APART = false>
 RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs &A, const DofFitRootArgs &R,
-                          const DofFitOriArgs &O, const DofFitPriorArgs &H = DofFitPriorArgs{})
+                          const DofFitOriArgs &O, const DofFitPriorArgs &H = DofFitPriorArgs{},
+                          const DofFitApartArgs &Z = DofFitApartArgs{})
 {
     static_assert(ROOT || !ORI, "the oriented tile carries the root image");
     static_assert(ROOT || !PRIOR, "the prior tile carries the root image");
+    static_assert(PRIOR || !APART, "the keep-apart tile is the prior tile's");
     extern __shared__ __attribute__((aligned(16))) float ft_lds[];
     using G = Grp<F>;
     const int J = T.J, lane = (int)threadIdx.x, nd = J - 1;
@@ -378,6 +549,8 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
     const int npos = 3 * nfr * J, nang = nfr * nd;
     const int K = ORI ? O.K : 0;
     const FitImages I(ft_lds, J, F, T.gsteps, ROOT, ORI ? K : -1, PRIOR);
+    const int NSPH = APART ? Z.S : 0;
+    [[maybe_unused]] const ApartImages X(APART ? ft_lds + I.floats : nullptr, J, F, NSPH, APART ? Z.Pn : 0);
     float *lossp = I.lossp, *adam = I.adam;
     const int fit_root = ROOT ? R.fit_root : 0;
     const bool prior = PRIOR && H.prior != nullptr, project = PRIOR && (H.flags & RTG_FIT_PROJECT) != 0;
@@ -435,6 +608,42 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
             I.otab[j] = OriEnt{slot, slot >= 0 && O.rot_weight ? ld_const(O.rot_weight + slot) : 1.0f};
         }
     }
+    if constexpr (APART) {   // the spheres, the pairs and each joint's spheres from the launch's lists
+        f4v sv{0.0f, 0.0f, 0.0f, 0.0f};
+        int lk = 0;
+#pragma unroll
+        for (int s = 0; s < RTG_FIT_MAX_SPHERES; ++s)
+            if (lane == s) {
+                sv = f4v{Z.sphere[s][0], Z.sphere[s][1], Z.sphere[s][2], Z.sphere[s][3]};
+                lk = Z.link[s];
+            }
+        if (lane < NSPH) {
+            X.sph[lane] = sv;
+            X.slink[lane] = lk;
+        }
+        int ab = 0;
+        float pw = 0.0f;
+#pragma unroll
+        for (int p = 0; p < RTG_FIT_MAX_PAIRS; ++p)
+            if (lane == p) {
+                ab = Z.pair[p];
+                pw = Z.pair_weight[p];
+            }
+        if (lane < ((Z.Pn + 3) & ~3)) {   // the carve pads the tables to whole fours: the pad holds pairs of weight 0
+            X.pair[lane] = lane < Z.Pn ? ab : 0;
+            X.pairw[lane] = lane < Z.Pn ? pw : 0.0f;
+        }
+        for (int j = lane; j < J; j += 64) {
+            int m = 0;
+#pragma unroll
+            for (int s = 0; s < RTG_FIT_MAX_SPHERES; ++s)
+                if (s < NSPH && Z.link[s] == j) {
+                    m |= 1 << s;
+                    if (Z.sphere[s][0] != 0.0f || Z.sphere[s][1] != 0.0f || Z.sphere[s][2] != 0.0f) m |= 0x10000 << s;
+                }
+            X.jtab[j] = m;
+        }
+    }
     if (ROOT) {   // the root image; fit_forward presets the root's rows from it
         if (lane < nfr) I.Rq[lane] = rr;
         if (lane < 3 * nfr) I.Rt[lane] = rt;
@@ -477,8 +686,15 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
             S.step_q = adam[128 + 2 * ((k - 1) & 63) + 1];
         }
         fit_forward<CLIP, F, ROOT>(I, J, T.gsteps, live, fr, sub, fit_root);
-        (void)fit_residual<F, ROOT>(I, J, live, fr, sub);
-        fit_reverse<CLIP, false, F, ROOT, ORI, PRIOR>(I, J, K, T.gsteps, live, fr, sub, S, fit_root, prior, project);
+        if constexpr (APART) {
+            (void)apart_pass<F>(I, X, Z, J, live, fr, sub);
+            (void)fit_residual<F, ROOT, true>(I, J, live, fr, sub, &X, NSPH);
+            fit_reverse<CLIP, false, F, ROOT, ORI, PRIOR, true>(I, J, K, T.gsteps, live, fr, sub, S, fit_root, prior, project,
+                                                                &X, NSPH);
+        } else {
+            (void)fit_residual<F, ROOT>(I, J, live, fr, sub);
+            fit_reverse<CLIP, false, F, ROOT, ORI, PRIOR>(I, J, K, T.gsteps, live, fr, sub, S, fit_root, prior, project);
+        }
     }
 
     // the iterate and its state out (coalesced), then loss and gradient there by one more sweep
@@ -495,10 +711,13 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
     if (!A.loss && !A.grad && !(ROOT && R.grad)) return;
     wave_sync();   // the M image is read out before the evaluation sweep writes gradients into it
     fit_forward<CLIP, F, ROOT>(I, J, T.gsteps, live, fr, sub, fit_root);
-    float part = fit_residual<F, ROOT>(I, J, live, fr, sub);
+    float apart = 0.0f;
+    if constexpr (APART) apart = apart_pass<F>(I, X, Z, J, live, fr, sub);
+    float part = fit_residual<F, ROOT, APART>(I, J, live, fr, sub, &X, NSPH);
     if constexpr (PRIOR) {
         if (prior) part += prior_loss_part<F>(I, nd, live, fr, sub);
     }
+    if constexpr (APART) part += apart;
     if (A.loss) {
         lossp[lane] = part;
         wave_sync();
@@ -511,7 +730,7 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
         }
     }
     if (A.grad || (ROOT && R.grad)) {
-        fit_reverse<CLIP, true, F, ROOT, ORI, PRIOR>(I, J, K, T.gsteps, live, fr, sub, S, fit_root, prior, project);
+        fit_reverse<CLIP, true, F, ROOT, ORI, PRIOR, APART>(I, J, K, T.gsteps, live, fr, sub, S, fit_root, prior, project, &X, NSPH);
         if (A.grad) ScalarRows<F>::copy_out(I.M, A.grad + f0 * nd, nang);
         if (ROOT && R.grad) RootStateRows::copy_out(I.Rs, R.grad + f0 * 7, 7 * nfr);
     }
@@ -549,6 +768,21 @@ __global__ __launch_bounds__(64) void k_dof_fit_orient_prior_group(TopoView T, D
                                                                    DofFitOriArgs O, DofFitPriorArgs H)
 {
     dof_fit_tile<CLIP, F, true, true, true>(T, D, A, R, O, H);
+}
+
+// rtg_dof_fit_apart_f32 (with a sphere and a pair or the plane) without oriented links and with them
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_apart_group(TopoView T, DofView D, DofFitArgs A, DofFitRootArgs R,
+                                                            DofFitPriorArgs H, DofFitApartArgs Z)
+{
+    dof_fit_tile<CLIP, F, true, false, true, true>(T, D, A, R, DofFitOriArgs{}, H, Z);
+}
+
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_orient_apart_group(TopoView T, DofView D, DofFitArgs A, DofFitRootArgs R,
+                                                                   DofFitOriArgs O, DofFitPriorArgs H, DofFitApartArgs Z)
+{
+    dof_fit_tile<CLIP, F, true, true, true, true>(T, D, A, R, O, H, Z);
 }
 
 template <bool ROOT>
@@ -625,6 +859,40 @@ hipError_t launch_dof_fit_prior(const TopoView &T, const DofView &D, bool clip, 
             attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_prior_group<cl(), f()>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
             if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_prior_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A, R, H);
+        }
+    }, clip);
+    if (attr != hipSuccess) return attr;
+    return hipGetLastError();
+}
+
+hipError_t launch_dof_fit_apart(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
+                                const DofFitRootArgs &R, const DofFitOriArgs &O, const DofFitPriorArgs &H,
+                                const DofFitApartArgs &Z, hipStream_t s)
+{
+    if (!T.gsched || O.K < 0 || O.K > RTG_FIT_MAX_ROT_LINKS) return hipErrorInvalidValue;
+    if ((H.flags & RTG_FIT_PROJECT) && (!D.lower || !D.upper)) return hipErrorInvalidValue;   // the kernel reads them
+    for (int k = 0; k < O.K; ++k)   // the kernel indexes rows with them
+        if (O.joint[k] < 0 || O.joint[k] >= T.J) return hipErrorInvalidValue;
+    if (Z.S < 1 || Z.S > RTG_FIT_MAX_SPHERES || Z.Pn < 0 || Z.Pn > RTG_FIT_MAX_PAIRS) return hipErrorInvalidValue;
+    if (Z.S < 32 && (Z.floor_mask >> Z.S) != 0u) return hipErrorInvalidValue;
+    for (int i = 0; i < Z.S; ++i)   // likewise
+        if (Z.link[i] < 0 || Z.link[i] >= T.J) return hipErrorInvalidValue;
+    for (int p = 0; p < Z.Pn; ++p)
+        if ((Z.pair[p] & 0xFF) >= Z.S || (Z.pair[p] >> 8) < 0 || (Z.pair[p] >> 8) >= Z.S) return hipErrorInvalidValue;
+    const int F = T.gF;
+    const size_t lds = sizeof(float) * (FitImages(nullptr, T.J, F, T.gsteps, true, O.K > 0 ? O.K : -1, true).floats +
+                                        ApartImages(nullptr, T.J, F, Z.S, Z.Pn).floats);
+    if (lds > kFitMaxLdsBytes) return hipErrorInvalidValue;
+    hipError_t attr = hipSuccess;
+    group_dispatch(F, [&](auto f, auto cl) {
+        if (O.K > 0) {
+            attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_orient_apart_group<cl(), f()>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
+            if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_orient_apart_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A, R, O, H, Z);
+        } else {
+            attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dof_fit_apart_group<cl(), f()>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
+            if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_apart_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A, R, H, Z);
         }
     }, clip);
     if (attr != hipSuccess) return attr;

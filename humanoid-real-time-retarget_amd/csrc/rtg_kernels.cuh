@@ -132,6 +132,23 @@ struct DofFitPriorArgs {
 };
 hipError_t launch_dof_fit_prior(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
                                 const DofFitRootArgs &R, const DofFitOriArgs &O, const DofFitPriorArgs &H, hipStream_t s);
+// rtg_dof_fit_apart_f32: the prior launch with keep-apart spheres and a floor.  Everything travels in the launch
+// arguments (host-checked: links in 0..J-1, pair ends distinct and in 0..S-1, radii and weights finite and not
+// negative, the plane's normal unit, mask bits below S).  link: a sphere's joint; sphere: {offset in the link's frame,
+// radius}; pair: a | b << 8; floor_mask == 0: no plane
+struct DofFitApartArgs {
+    int32_t S, Pn;
+    uint32_t floor_mask;
+    float margin, floor_weight;
+    float plane[4];   // {unit normal, h0}
+    int32_t link[RTG_FIT_MAX_SPHERES];
+    float sphere[RTG_FIT_MAX_SPHERES][4];
+    int32_t pair[RTG_FIT_MAX_PAIRS];
+    float pair_weight[RTG_FIT_MAX_PAIRS];
+};
+hipError_t launch_dof_fit_apart(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
+                                const DofFitRootArgs &R, const DofFitOriArgs &O, const DofFitPriorArgs &H,
+                                const DofFitApartArgs &Z, hipStream_t s);
 // SkeletonState.retarget_to (poselib skeleton3d.py:742-889) as one launch, rtg_retarget_to.hip.
 // The host tables of a mapping of K (source joint, target joint) pairs: S_red / T_red are the trees with only the
 // mapped joints kept, each hung from its nearest kept ancestor (drop_nodes_by_names, :226-259).

@@ -78,7 +78,7 @@ class HuForwardModel(BaseForwardModel):
     def fit_keypoints(self, target_positions, motion_root_translation, motion_root_rotation,
                       motion_joint_angles=None, weight=None, iters=32, lr=0.02, betas=(0.9, 0.999), eps=1e-8,
                       clip_angles=True, state=None, return_grad=False, target_rotations=None, rotation_links=None,
-                      rotation_weight=None, prior_angles=None, prior_weight=None, project_angles=False):
+                      rotation_weight=None, prior_angles=None, prior_weight=None, project_angles=False, apart=None):
         """Not in the reference, which only ships the forward model of its optimisation-based converter: the loop that
         model is for -- a keypoint loss sum_j weight[j] |g_pos[:, j] - target_positions[:, j]|^2 minimised over the
         joint angles with torch.optim.Adam -- as one launch (ops.dof_fit).  (L, J, 3) targets, (L, 3) root translation,
@@ -88,7 +88,8 @@ class HuForwardModel(BaseForwardModel):
         result for the final pose.
         ``target_rotations`` (L, K, 4), ``rotation_links`` (K node names or joint indices, K <= 8) and
         ``rotation_weight`` (K,) add fit_pose's orientation term for those links, the root given.  ``prior_angles``,
-        ``prior_weight``, ``project_angles``: fit_pose's posture prior and projection."""
+        ``prior_weight``, ``project_angles``: fit_pose's posture prior and projection.  ``apart``: its keep-apart spheres
+        and floor."""
         if clip_angles and not self._model.has_limits:
             raise ValueError("clip_angles needs DOF limits with one entry per DOF")
         dev = home_device(target_positions, motion_root_translation, motion_root_rotation)
@@ -97,7 +98,7 @@ class HuForwardModel(BaseForwardModel):
                           dof0=motion_joint_angles, weight=weight, iters=iters, lr=lr, betas=betas, eps=eps,
                           clip=bool(clip_angles), state=state, return_grad=return_grad,
                           **self._rotation_targets(target_rotations, rotation_links, rotation_weight),
-                          **self._posture_prior(prior_angles, prior_weight, project_angles))
+                          **self._posture_prior(prior_angles, prior_weight, project_angles), apart=apart)
         dof, loss, new_state = res[:3]
         shaped = lambda a: a.reshape(tuple(loss.shape) + (n, 1)).to(dev)
         out = (shaped(dof), loss.to(dev), new_state)
@@ -106,7 +107,8 @@ class HuForwardModel(BaseForwardModel):
     def fit_pose(self, target_positions, motion_root_translation, motion_root_rotation, motion_joint_angles=None,
                  weight=None, iters=32, lr=0.02, lr_root_t=None, lr_root_rot=None, fit_root_t=True, fit_root_rot=True,
                  betas=(0.9, 0.999), eps=1e-8, clip_angles=True, state=None, return_grad=False, target_rotations=None,
-                 rotation_links=None, rotation_weight=None, prior_angles=None, prior_weight=None, project_angles=False):
+                 rotation_links=None, rotation_weight=None, prior_angles=None, prior_weight=None, project_angles=False,
+                 apart=None):
         """fit_keypoints with the floating base among the parameters (ops.pose_fit): mocap keypoints come from a body
         of other proportions, and with the root pinned the legs cannot reach them.  (L, J, 3) targets, (L, 3) root
         translation and (L, 1, 4) root rotation to start from (or given, where fit_root_t / fit_root_rot is False),
@@ -121,7 +123,12 @@ class HuForwardModel(BaseForwardModel):
         ``prior_angles`` (L, J-1, 1) or (L, J-1) and ``prior_weight`` (a number or (J-1,), default ones) add the posture
         term sum_d prior_weight[d] (angle_d - prior_d)^2 on the iterate: it holds DOFs no target observes, and a
         redundant arm's swivel, to a rest pose or to the last frame's solution.  ``project_angles`` clamps every angle
-        to its limits after each step, so an unreachable target cannot push the iterate past a limit without bound."""
+        to its limits after each step, so an unreachable target cannot push the iterate past a limit without bound.
+        ``apart``: keep-apart spheres and a floor, built once with ``rtg.ops.apart(self, links, radii, ...)`` (links by
+        node name or joint index): spheres riding on links, pairs of them pushed apart where they overlap, and spheres
+        held above a ground plane -- what keeps a wrist out of the torso, one gripper out of the other and an ankle
+        above the floor when the keypoints come from a body of other proportions.  No default radii are shipped: the
+        repository holds Hu's skeleton only, no collision geometry; measure them or take them from the robot's URDF."""
         if clip_angles and not self._model.has_limits:
             raise ValueError("clip_angles needs DOF limits with one entry per DOF")
         dev = home_device(target_positions, motion_root_translation, motion_root_rotation)
@@ -131,7 +138,7 @@ class HuForwardModel(BaseForwardModel):
                            lr_root_rot=lr_root_rot, fit_root_t=fit_root_t, fit_root_rot=fit_root_rot, betas=betas,
                            eps=eps, clip=bool(clip_angles), state=state, return_grad=return_grad,
                            **self._rotation_targets(target_rotations, rotation_links, rotation_weight),
-                           **self._posture_prior(prior_angles, prior_weight, project_angles))
+                           **self._posture_prior(prior_angles, prior_weight, project_angles), apart=apart)
         lead = tuple(res.loss.shape)
         shaped = lambda a: a.reshape(lead + (n, 1)).to(dev)
         out = (shaped(res.dof), res.root_t.to(dev), res.root_rot.reshape(lead + (1, 4)).to(dev), res.loss.to(dev),
@@ -148,8 +155,8 @@ class HuForwardModel(BaseForwardModel):
         root that carries the optimiser state.  ``smooth_weight == 0`` passes no prior: that is one fit_pose of
         rounds * iters steps, bit for bit.  Only the angles are smoothed: the root can be regularised through
         weight[0] and an orientation target on link 0.  The other keywords are fit_pose's (``prior_angles`` and
-        ``state`` are this method's to set; ``prior_weight`` scales smooth_weight per DOF).  Returns what fit_pose
-        returns, after the last round."""
+        ``state`` are this method's to set; ``prior_weight`` scales smooth_weight per DOF; ``apart`` goes to every
+        round).  Returns what fit_pose returns, after the last round."""
         for k in ("prior_angles", "state"):
             if k in fit_pose_keywords:
                 raise ValueError(f"fit_motion sets {k} itself")

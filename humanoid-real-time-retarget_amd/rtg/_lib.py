@@ -86,6 +86,13 @@ class FkSegment(ctypes.Structure):
                 ("g_pos", c_void_p), ("B", c_int64)]
 
 
+class FitApart(ctypes.Structure):
+    """rtg.h rtg_fit_apart: a host struct of host pointers, read before rtg_dof_fit_apart_f32 returns."""
+    _fields_ = [("S", c_int32), ("sphere_link", POINTER(c_int32)), ("sphere", POINTER(c_float)), ("Pn", c_int32),
+                ("pair", POINTER(c_int32)), ("pair_weight", POINTER(c_float)), ("margin", c_float),
+                ("plane", POINTER(c_float)), ("floor_mask", ctypes.c_uint32), ("floor_weight", c_float)]
+
+
 class LocalRotationSegment(ctypes.Structure):
     _fields_ = [("topo", c_void_p), ("g_rot", c_void_p), ("local_rot", c_void_p), ("B", c_int64)]
 
@@ -130,6 +137,10 @@ SIGNATURES = {
     # (the same with (prior, prior_weight, flags) after K)
     "rtg_dof_fit_prior_f32": (c_int, [c_void_p] * 6 + [c_int32] + [c_void_p] * 2 + [c_int32] + [c_void_p] * 3 +
                                      [c_int64, c_int, c_int32, c_int32] + [c_float] * 6 + [c_int32] + [c_void_p] * 10),
+    # (the same with the host struct `apart` before the stream)
+    "rtg_dof_fit_apart_f32": (c_int, [c_void_p] * 6 + [c_int32] + [c_void_p] * 2 + [c_int32] + [c_void_p] * 3 +
+                                     [c_int64, c_int, c_int32, c_int32] + [c_float] * 6 + [c_int32] + [c_void_p] * 9 +
+                                     [POINTER(FitApart), c_void_p]),
     "rtg_retarget_plan_create": (c_int, [c_void_p, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int32,
                                          POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                          POINTER(c_float), c_float, POINTER(c_void_p)]),

@@ -523,6 +523,114 @@ def _prior_inputs(model, d, prior, prior_weight, project):
     return Prior(rows, pw, FIT_PROJECT if project else 0)
 
 
+FIT_MAX_SPHERES, FIT_MAX_PAIRS = 16, 32   # rtg.h RTG_FIT_MAX_SPHERES, RTG_FIT_MAX_PAIRS
+
+# what ops.apart builds: ``spec`` is the rtg_fit_apart of the call (a host struct; the other fields are the host arrays
+# it points into, which also say what it holds: links (S,) int32, spheres (S,4) {offset, radius}, pairs (Pn,2) int32,
+# pair_weight (Pn,) or None, plane (4,) {unit-length or not normal, h0} or None)
+Apart = collections.namedtuple("Apart", "spec links spheres pairs pair_weight margin plane floor_mask floor_weight")
+
+
+def apart(model, links, radii, offsets=None, pairs=None, pair_weight=None, margin: float = 0.0, floor=None,
+          floor_links=None, floor_weight: float = 1.0):
+    """The keep-apart term of pose_fit and its relatives (rtg_dof_fit_apart_f32), built once and passed as ``apart=``:
+    S <= 16 spheres riding on links, Pn <= 32 pairs of them that are pushed apart where they overlap, and a floor.
+
+    ``model``: a DofModel, or anything with the tree's ``parents`` (or ``parent_indices``) and, for links given by
+    name, ``node_names``.  ``links`` (S) names or joint indices, one per sphere (a link may carry several); ``radii``
+    (S) or a number; ``offsets`` (S, 3) in the link's frame, default zeros (a sphere at the link's origin moves with
+    the link's position alone and adds no rotation gradient).  ``pairs`` (Pn, 2) sphere indices; None: every pair of
+    spheres whose links are neither the same nor parent and child (neighbours overlap by construction) -- it raises
+    when that is more than 32.  ``pair_weight`` (Pn) or a number, None for ones.  Pair (a, b) adds
+    pair_weight max(0, r_a + r_b + margin - |c_a - c_b|)^2 to a frame's loss.  ``floor``: (n_x, n_y, n_z, h0), the
+    half-space n . x >= h0 (n of any non-zero length); the spheres on ``floor_links`` (None: every sphere) add
+    floor_weight max(0, r + h0 - n . c)^2.  Nothing here is differentiable.
+
+    No radii are shipped: the repository holds Hu's skeleton only, no collision geometry -- measure them on the robot
+    or take them from its URDF."""
+    import numpy as np
+    parents = getattr(model, "parents", None)
+    if parents is None and getattr(model, "topo", None) is not None:
+        parents = model.topo.parents
+    if parents is None:
+        parents = getattr(model, "parent_indices", None)
+    if parents is None:
+        raise ValueError("apart needs the tree: a DofModel, or an object with parents")
+    par = [int(x) for x in (parents.tolist() if hasattr(parents, "tolist") else parents)]
+    J = len(par)
+    names = list(getattr(model, "node_names", None) or [])
+
+    def joint(link, what):
+        if isinstance(link, str):
+            if link not in names:
+                raise ValueError(f"{what}: the skeleton has no node named {link!r}")
+            return names.index(link)
+        j = int(link)
+        if not 0 <= j < J:
+            raise ValueError(f"{what}: joint {j} is outside 0..{J - 1}")
+        return j
+
+    lk = np.asarray([joint(x, "links") for x in links], np.int32)
+    S = len(lk)
+    if S > FIT_MAX_SPHERES:
+        raise ValueError(f"at most {FIT_MAX_SPHERES} spheres, got {S}")
+    r = np.broadcast_to(np.asarray(radii, np.float32), (S,)) if np.ndim(radii) == 0 else np.asarray(radii, np.float32)
+    off = np.zeros((S, 3), np.float32) if offsets is None else np.asarray(offsets, np.float32)
+    if r.shape != (S,) or off.shape != (S, 3):
+        raise ValueError(f"radii must be ({S},) and offsets ({S}, 3), got {r.shape} and {off.shape}")
+    if not (np.isfinite(r).all() and (r >= 0).all() and np.isfinite(off).all()):
+        raise ValueError("radii must be finite and not negative, offsets finite")
+    spheres = np.ascontiguousarray(np.concatenate([off, r[:, None]], axis=1), np.float32)
+    if pairs is None:
+        related = lambda a, b: lk[a] == lk[b] or par[lk[a]] == lk[b] or par[lk[b]] == lk[a]
+        pr = [(a, b) for a in range(S) for b in range(a + 1, S) if not related(a, b)]
+        if len(pr) > FIT_MAX_PAIRS:
+            raise ValueError(f"{S} spheres give {len(pr)} pairs of unrelated links, at most {FIT_MAX_PAIRS}: pass pairs")
+    else:
+        pr = [(int(a), int(b)) for a, b in pairs]
+        if len(pr) > FIT_MAX_PAIRS:
+            raise ValueError(f"at most {FIT_MAX_PAIRS} pairs, got {len(pr)}")
+        if any(not (0 <= a < S and 0 <= b < S) or a == b for a, b in pr):
+            raise ValueError(f"pairs must join two different spheres in 0..{S - 1}, got {pr}")
+    pr = np.ascontiguousarray(np.asarray(pr, np.int32).reshape(-1, 2))
+    Pn = len(pr)
+    pw = None
+    if pair_weight is not None:
+        pw = np.ascontiguousarray(np.broadcast_to(np.asarray(pair_weight, np.float32), (Pn,)))
+        if not (np.isfinite(pw).all() and (pw >= 0).all()):
+            raise ValueError("pair_weight must be finite and not negative")
+    margin = float(margin)
+    if not np.isfinite(margin):
+        raise ValueError(f"margin must be finite, got {margin}")
+    plane, mask = None, 0
+    if floor is not None:
+        plane = np.ascontiguousarray(np.asarray(floor, np.float32).reshape(-1))
+        if plane.shape != (4,) or not np.isfinite(plane).all() or not np.abs(plane[:3]).max() > 0:
+            raise ValueError(f"floor must be four finite numbers (n_x, n_y, n_z, h0) with n not zero, got {floor!r}")
+        if floor_links is None:
+            mask = (1 << S) - 1
+        else:
+            on = {joint(x, "floor_links") for x in floor_links}
+            mask = sum(1 << i for i in range(S) if int(lk[i]) in on)
+    elif floor_links is not None:
+        raise ValueError("floor_links needs a floor")
+    floor_weight = float(floor_weight)
+    if not (np.isfinite(floor_weight) and floor_weight >= 0):
+        raise ValueError(f"floor_weight must be finite and not negative, got {floor_weight}")
+    fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)
+    at = lambda a, t: a.ctypes.data_as(t) if a is not None and a.size else None
+    spec = _lib.FitApart(S, at(lk, ip), at(spheres, fp), Pn, at(pr, ip), at(pw, fp), margin, at(plane, fp), mask,
+                         floor_weight)
+    return Apart(spec, lk, spheres, pr, pw, margin, plane, mask, floor_weight)
+
+
+def _apart_input(apart):
+    """``apart=`` of the fits: None, or what ops.apart built."""
+    if apart is not None and not isinstance(apart, Apart):
+        raise ValueError("apart must be built with ops.apart")
+    return apart
+
+
 def _fit_state(model, d, dof0, iters, state):
     """What dof_fit and pose_fit share around their launches: ``iters`` range-checked; the angles' optimiser state
     ``(m, v, step)`` -- fresh (zeros, 0) for ``state`` None, else the caller's, copied (the launch updates it in
@@ -558,7 +666,8 @@ def _fit_launch(model, clip, tp, w, rr, rt, d, iters=0, lr=0.0, betas=(0.9, 0.99
 
 def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: int = 32, lr: float = 0.02,
             betas=(0.9, 0.999), eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False,
-            rot_joints=None, target_rot=None, rot_weight=None, prior=None, prior_weight=None, project: bool = False):
+            rot_joints=None, target_rot=None, rot_weight=None, prior=None, prior_weight=None, project: bool = False,
+            apart=None):
     """Fit the joint angles of a DofModel to target keypoints: ``iters`` steps of torch.optim.Adam (no weight decay, no
     amsgrad) on L_f = sum_j weight[j] |P_j(a_f) - target_pos[f, j]|^2, P the positions of dof_forward_kinematics --
     forward model, loss, gradient and optimiser in ONE launch (rtg_dof_fit_f32).
@@ -575,35 +684,43 @@ def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: 
     ``rot_joints``, ``target_rot``, ``rot_weight``: pose_fit's orientation targets, with the root given
     (rtg_dof_fit_orient_f32 with fit_root = 0; an oriented root then only adds to the loss).
     ``prior``, ``prior_weight``, ``project``: pose_fit's posture prior and projection (rtg_dof_fit_prior_f32 with
+    fit_root = 0).  ``apart``: pose_fit's keep-apart spheres and floor (ops.apart; rtg_dof_fit_apart_f32 with
     fit_root = 0).
     Raises RtgError without a GPU: there is no CPU fallback."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof0, weight)
     iters, m, v, step, as_dof0 = _fit_state(model, d, dof0, iters, state)
     orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
     pri = _prior_inputs(model, d, prior, prior_weight, project)
-    if orient is None and pri is None:
+    apart = _apart_input(apart)
+    if orient is None and pri is None and apart is None:
         out, loss, grad = _fit_launch(model, clip, tp, w, rr, rt, d.detach(), iters, lr, betas, eps, step, m, v,
                                       want_dof=True, want_grad=bool(return_grad))
     else:   # the root is given: its state is neither read nor written, the buffer only pairs with m and v
         rs = torch.zeros(tuple(tp.shape[:-2]) + (14,), device=d.device, dtype=torch.float32)
         out, _, _, loss, grad, _ = _pose_launch(model, clip, 0, tp, w, rr, rt, d.detach(), iters, lr, 0.0, 0.0, betas, eps,
                                                 step, m if m.numel() else rs, v if v.numel() else rs, rs,
-                                                want_iterate=True, want_grad=bool(return_grad), orient=orient, prior=pri)
+                                                want_iterate=True, want_grad=bool(return_grad), orient=orient, prior=pri,
+                                                apart=apart)
     res = (as_dof0(out), loss, (m, v, step + iters))
     return res + (as_dof0(grad),) if return_grad else res
 
 
 def keypoint_loss(model, dof, target_pos, root_rot, root_t, weight=None, clip: bool = False, rot_joints=None,
-                  target_rot=None, rot_weight=None, prior=None, prior_weight=None):
+                  target_rot=None, rot_weight=None, prior=None, prior_weight=None, apart=None):
     """The per-frame keypoint loss L_f = sum_j weight[j] |P_j(dof_f) - target_pos[f, j]|^2 of dof_fit, (...), as the
     evaluate-only launch of rtg_dof_fit_f32.  Differentiable in ``dof`` (only): the launch computes the gradient
     along with the loss, and backward scales its rows by the upstream cotangent -- for callers who keep their own
     optimiser.  Under no_grad, or when dof does not require grad, it is the plain launch without the gradient.
     ``rot_joints``, ``target_rot``, ``rot_weight``: dof_fit's orientation targets.  ``prior``, ``prior_weight``: its
-    posture term sum_d prior_weight[d] (dof_d - prior_d)^2 (the loss is not differentiable in them)."""
+    posture term sum_d prior_weight[d] (dof_d - prior_d)^2 (the loss is not differentiable in them).  ``apart``: its
+    keep-apart spheres and floor (ops.apart; not differentiable in the spec either)."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof, weight)
     orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
     pri = _prior_inputs(model, d, prior, prior_weight, False)
+    if _apart_input(apart) is not None:
+        if torch.is_grad_enabled() and d.requires_grad:
+            return _ApartPoseLoss.apply(model, bool(clip), 0, d, rr.detach(), rt.detach(), tp, w, orient, pri, apart)
+        return _pose_launch(model, clip, 0, tp, w, rr, rt, d.detach(), orient=orient, prior=pri, apart=apart)[3]
     if pri is not None:
         if torch.is_grad_enabled() and d.requires_grad:
             return _PriorPoseLoss.apply(model, bool(clip), 0, d, rr.detach(), rt.detach(), tp, w, orient, pri)
@@ -639,9 +756,9 @@ PoseFitGrad = collections.namedtuple("PoseFitGrad", "dof root_rot root_t loss st
 
 def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_root_t=0.0, lr_root_rot=0.0,
                  betas=(0.9, 0.999), eps=1e-8, step0=0, m=None, v=None, root_state=None, want_iterate=False,
-                 want_loss=True, want_grad=False, orient=None, prior=None):
+                 want_loss=True, want_grad=False, orient=None, prior=None, apart=None):
     """rtg_dof_fit_root_f32 -- with ``orient`` (an Orient) rtg_dof_fit_orient_f32, with ``prior`` (a Prior)
-    rtg_dof_fit_prior_f32 -- on prepared tensors; m, v, root_state are updated in place.  Returns (dof_out, root_rot_out, root_t_out, loss, grad, grad_root), None where
+    rtg_dof_fit_prior_f32, with ``apart`` (an Apart) rtg_dof_fit_apart_f32 -- on prepared tensors; m, v, root_state are updated in place.  Returns (dof_out, root_rot_out, root_t_out, loss, grad, grad_root), None where
     not asked for."""
     lead = tuple(tp.shape[:-2])
     B = int(torch.Size(lead).numel())
@@ -652,7 +769,13 @@ def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_ro
     tail = (ptr(rr), ptr(rt), ptr(d), B, int(bool(clip)), int(fit_root), int(iters), float(lr), float(lr_root_t),
             float(lr_root_rot), float(betas[0]), float(betas[1]), float(eps), int(step0), ptr(m), ptr(v), ptr(root_state),
             ptr(out), ptr(rr_out), ptr(rt_out), ptr(loss), ptr(grad), ptr(grad_root), stream_handle())
-    if prior is not None:
+    if apart is not None:
+        o = orient if orient is not None else Orient(None, 0, None, None)
+        h = prior if prior is not None else Prior(None, None, 0)
+        check(lib().rtg_dof_fit_apart_f32(model.handle, ptr(tp), ptr(w), o.joints, ptr(o.target_rot), ptr(o.rot_weight),
+                                          o.K, ptr(h.rows), ptr(h.weight), h.flags, *tail[:-1], ctypes.byref(apart.spec),
+                                          tail[-1]))
+    elif prior is not None:
         o = orient if orient is not None else Orient(None, 0, None, None)
         check(lib().rtg_dof_fit_prior_f32(model.handle, ptr(tp), ptr(w), o.joints, ptr(o.target_rot), ptr(o.rot_weight),
                                           o.K, ptr(prior.rows), ptr(prior.weight), prior.flags, *tail))
@@ -667,7 +790,7 @@ def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_ro
 def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iters: int = 32, lr: float = 0.02,
              lr_root_t=None, lr_root_rot=None, fit_root_t: bool = True, fit_root_rot: bool = True, betas=(0.9, 0.999),
              eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False, rot_joints=None,
-             target_rot=None, rot_weight=None, prior=None, prior_weight=None, project: bool = False):
+             target_rot=None, rot_weight=None, prior=None, prior_weight=None, project: bool = False, apart=None):
     """dof_fit with the floating base among the parameters: the joint angles and -- where ``fit_root_t`` /
     ``fit_root_rot`` -- the root translation and rotation of every frame, fitted to target keypoints by ``iters`` steps
     of torch.optim.Adam with three parameter groups (``lr`` for the angles, ``lr_root_t``, ``lr_root_rot``; None: ``lr``)
@@ -697,6 +820,12 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
     weight[0] with target_pos[..., 0, :] is a prior on its translation, an orientation target on joint 0 on its
     rotation.  With none of the three given this is the launch without them, bit for bit.
 
+    Keep-apart spheres and a floor (rtg_dof_fit_apart_f32, still one launch): ``apart``, built once with ops.apart --
+    spheres riding on links, pairs of them pushed apart where they overlap by pair_weight max(0, r_a + r_b + margin -
+    |c_a - c_b|)^2, and spheres held above a plane by floor_weight max(0, r + h0 - n . c)^2.  It is what keeps a wrist
+    out of the torso, one gripper out of the other and an ankle above the ground when the keypoints come from a body of
+    other proportions.  The term acts on the iterate inside the launch; None is the launch without it, bit for bit.
+
     Returns the named tuple ``(dof, root_rot, root_t, loss, state)`` -- the iterate after the last step (root_rot
     (..., 4), unit where fitted), the per-frame loss there -- plus ``grad`` (dof's shape) and ``grad_root`` (..., 7) =
     {dL/dt, dL/dq} there when ``return_grad``.  ``iters=0`` only evaluates.  Raises RtgError without a GPU: there is
@@ -716,7 +845,7 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
         model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach(), iters, lr,
         lr if lr_root_t is None else lr_root_t, lr if lr_root_rot is None else lr_root_rot, betas, eps, step,
         m if m.numel() else rs, v if v.numel() else rs, rs, want_iterate=True, want_grad=bool(return_grad),
-        orient=orient, prior=pri)
+        orient=orient, prior=pri, apart=_apart_input(apart))
     new_state = (m, v, rs, step + iters)
     if return_grad:
         return PoseFitGrad(as_dof0(out), rr_out, rt_out, loss, new_state, as_dof0(grad), grad_root)
@@ -724,18 +853,24 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
 
 
 def pose_loss(model, dof, root_rot, root_t, target_pos, weight=None, clip: bool = False, normalize_root: bool = True,
-              rot_joints=None, target_rot=None, rot_weight=None, prior=None, prior_weight=None):
+              rot_joints=None, target_rot=None, rot_weight=None, prior=None, prior_weight=None, apart=None):
     """The per-frame keypoint loss of pose_fit, (...), as the evaluate-only launch of rtg_dof_fit_root_f32,
     differentiable in ``dof``, ``root_rot`` and ``root_t``: the launch computes the three gradients along with the
     loss and backward scales their rows by the upstream cotangent -- for callers who keep their own optimiser.
     ``normalize_root``: the root rotation enters as q / |q| and its gradient is tangent (pose_fit's model of a fitted
     rotation); False: as given, like keypoint_loss.  Under no_grad, or when no input requires grad, it is the plain
     launch without the gradients.  ``rot_joints``, ``target_rot``, ``rot_weight``: pose_fit's orientation targets;
-    ``prior``, ``prior_weight``: its posture term (the loss is not differentiable in any of them)."""
+    ``prior``, ``prior_weight``: its posture term; ``apart``: its keep-apart spheres and floor (ops.apart) (the loss is
+    not differentiable in any of them)."""
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof, weight)
     fit_root = FIT_ROOT_ROT if normalize_root else 0   # no step is taken: the mask only selects the model
     orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
     pri = _prior_inputs(model, d, prior, prior_weight, False)
+    if _apart_input(apart) is not None:
+        if torch.is_grad_enabled() and (d.requires_grad or rr.requires_grad or rt.requires_grad):
+            return _ApartPoseLoss.apply(model, bool(clip), fit_root, d, rr, rt, tp, w, orient, pri, apart)
+        return _pose_launch(model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach(), orient=orient, prior=pri,
+                            apart=apart)[3]
     if pri is not None:
         if torch.is_grad_enabled() and (d.requires_grad or rr.requires_grad or rt.requires_grad):
             return _PriorPoseLoss.apply(model, bool(clip), fit_root, d, rr, rt, tp, w, orient, pri)
@@ -794,6 +929,24 @@ class _PriorPoseLoss(torch.autograd.Function):
         grad, grad_root = ctx.saved_tensors
         c = grad_loss.unsqueeze(-1)
         return None, None, None, grad * c, grad_root[..., 3:] * c, grad_root[..., :3] * c, None, None, None, None
+
+
+class _ApartPoseLoss(torch.autograd.Function):
+    """_PriorPoseLoss (orient and prior may be None) with the keep-apart term: the evaluate-only launch of
+    rtg_dof_fit_apart_f32."""
+    @staticmethod
+    def forward(ctx, model, clip, fit_root, d, rr, rt, tp, w, orient, prior, apart):
+        _, _, _, loss, grad, grad_root = _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, want_grad=True,
+                                                      orient=orient, prior=prior, apart=apart)
+        ctx.save_for_backward(grad, grad_root)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        grad, grad_root = ctx.saved_tensors
+        c = grad_loss.unsqueeze(-1)
+        return None, None, None, grad * c, grad_root[..., 3:] * c, grad_root[..., :3] * c, None, None, None, None, None
 
 
 def rescale_motion(topo: Topology, motion, dir=None):

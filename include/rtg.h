@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*); rtg_dof_fit_f32,
-                                  rtg_dof_fit_root_f32, rtg_dof_fit_orient_f32 and rtg_dof_fit_prior_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
+                                  rtg_dof_fit_root_f32, rtg_dof_fit_orient_f32, rtg_dof_fit_prior_f32 and rtg_dof_fit_apart_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
                                6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
                                5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
                                4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
@@ -304,6 +304,67 @@ int rtg_dof_fit_prior_f32(rtg_dof_model_t model, const float *target_pos, const 
                           float eps, int32_t step0, float *m, float *v, float *root_state, float *dof_out,
                           float *root_rot_out, float *root_t_out, float *loss, float *grad, float *grad_root,
                           rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * rtg_dof_fit_prior_f32 with keep-apart spheres and a floor (a new symbol under ABI 7).  Every other term pulls the
+ * robot towards something; keypoints of a body of other proportions then leave a wrist inside the torso, one gripper
+ * inside the other or an ankle under the ground.  Here up to RTG_FIT_MAX_SPHERES spheres ride on links, up to
+ * RTG_FIT_MAX_PAIRS pairs of them are pushed apart where they overlap, and spheres chosen by a mask are pushed out
+ * of one half-space.  Sphere s sits on link j_s = sphere_link[s] with offset o_s in the link's frame and radius r_s:
+ *     c_s = P_j + rot(G_j, o_s),  rot(q, v) = q v conj(q) as the forward model applies it to bone offsets,
+ * G_j the global rotation as the forward model holds it (the root's: rtg_dof_fit_orient_f32's rule).  Per frame f
+ *     L_f = rtg_dof_fit_prior_f32's loss + sum_p pair_weight[p] h_p^2 + sum_{s in floor_mask} floor_weight hf_s^2,
+ *     h_p = max(0, r_a + r_b + margin - |c_a - c_b|) for pair p = (a, b),  hf_s = max(0, r_s + h0 - n . c_s)
+ * for the plane {n, h0} (n . x = h0 is the floor, n points up out of it).  dL/dc_a of a pair is
+ * -2 pair_weight[p] h_p (c_a - c_b) / max(|c_a - c_b|, 1e-9) and dL/dc_b its negative; the floor gives
+ * -2 floor_weight hf_s n.  A sphere's g_s = dL/dc_s is the sum of its pairs' terms in pair order, then the floor's;
+ * dL/dP_j gains sum g_s over the link's spheres in sphere order and dL/dG_j gains sum_s d(g_s . rot(G_j, o_s)) / dG_j,
+ * which enters the reverse sweep where an orientation target's adjoint does.  A sphere with a zero offset adds no
+ * rotation term at all.  Everything else -- Adam, the prior, the projection, the outputs -- is
+ * rtg_dof_fit_prior_f32's.
+ *   apart: a HOST struct, read before the call returns (its values travel in the launch's arguments, so the call
+ *   neither allocates nor synchronises, and they are checked here); NULL: no term.  sphere_link (S) joint indices in
+ *   0..J-1 (a link may carry several spheres); sphere (S,4) rows {o_x, o_y, o_z, r}, r >= 0; pair (Pn,2) sphere
+ *   indices, a != b; pair_weight (Pn) >= 0, or NULL = all 1; margin (any finite value: negative lets spheres
+ *   overlap that far); plane {n_x, n_y, n_z, h0}, or NULL: no floor -- the normal of any non-zero length, normalised
+ *   here (h0 is taken as given, in units of the unit normal); floor_mask: bit s set = sphere s is held above the
+ *   plane; floor_weight >= 0.  Without a plane the mask and the weight are not looked at.
+ * Guarantees: (a) apart == NULL, S == 0, or neither a pair nor a plane with mask bits gives rtg_dof_fit_prior_f32's
+ * outputs bit for bit.  (b) With every pair apart and every masked sphere above the plane, and finite inputs, every
+ * output equals (a)'s as a number (a zero may change sign).  (c) Coincident centres add the finite
+ * pair_weight[p] (r_a + r_b + margin)^2 and no gradient.  (d) With zero offsets a DOF that rtg_dof_fit_prior_f32
+ * leaves at +-0 and that has no sphere strictly below it stays at +-0.  (e) A frame depends on its own rows alone,
+ * runs are bit-identical (every sum has one order), and n launches of one step that carry (m, v, root_state, step0)
+ * equal one launch of n steps.  (f) A NaN in a frame's rows makes that frame's loss and gradient NaN (h = max(0, .)
+ * passes NaN, as torch.clamp does) and no other frame's.
+ * Errors: rtg_dof_fit_prior_f32's, and S or Pn negative, S > 0 or Pn > 0 with its arrays NULL, a pair index outside
+ * 0..S-1 or a == b, a negative radius or weight, a non-finite radius, weight, margin, offset or plane, a plane normal
+ * of zero length, mask bits at or above S, a link outside 0..J-1 -> RTG_ERR_INVALID_ARGUMENT; S >
+ * RTG_FIT_MAX_SPHERES or Pn > RTG_FIT_MAX_PAIRS -> RTG_ERR_UNSUPPORTED; all before any device work.  B == 0 is a
+ * no-op.
+ * ---------------------------------------------------------------------- */
+#define RTG_FIT_MAX_SPHERES 16   /* the spheres' centres share the tile's LDS */
+#define RTG_FIT_MAX_PAIRS 32
+typedef struct rtg_fit_apart {
+    int32_t S;
+    const int32_t *sphere_link;   /* (S) */
+    const float *sphere;          /* (S,4) {offset, radius} */
+    int32_t Pn;
+    const int32_t *pair;          /* (Pn,2) */
+    const float *pair_weight;     /* (Pn), or NULL */
+    float margin;
+    const float *plane;           /* (4) {normal, h0}, or NULL */
+    uint32_t floor_mask;
+    float floor_weight;
+} rtg_fit_apart;
+int rtg_dof_fit_apart_f32(rtg_dof_model_t model, const float *target_pos, const float *weight,
+                          const int32_t *rot_joint, const float *target_rot, const float *rot_weight, int32_t K,
+                          const float *prior, const float *prior_weight, int32_t flags, const float *root_rot,
+                          const float *root_t, const float *dof_in, int64_t B, int clip, int32_t fit_root,
+                          int32_t iters, float lr, float lr_root_t, float lr_root_rot, float beta1, float beta2,
+                          float eps, int32_t step0, float *m, float *v, float *root_state, float *dof_out,
+                          float *root_rot_out, float *root_t_out, float *loss, float *grad, float *grad_root,
+                          const rtg_fit_apart *apart, rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * SkeletonState.retarget_to (poselib skeleton3d.py:742-889): the generic skeleton-to-skeleton retarget, rotations

@@ -34,6 +34,9 @@
               with K = 5 links, against rtg_dof_fit_root_f32 of this build and of the build RTG_PARENT_LIB names (when
               set), rtg_dof_fit_orient_f32 at K = 5, and the composed iteration with the same term and clamp,
               interleaved rounds
+  apart_fit -- the pose fit with keep-apart spheres and a floor (rtg_dof_fit_apart_f32, a prior and the projection on)
+              per iteration with S = 8 and S = 16 spheres, against rtg_dof_fit_prior_f32 of this build and of
+              RTG_PARENT_LIB, and the composed iteration with the same penalty
   prior_fit_traffic -- a few launches of rtg_dof_fit_prior_f32 and nothing else, for a counter run of its own
   motion_sample -- the fused motion sampler (rtg_motion_sample_f32, C ABI, preallocated outputs; Hu v5, 64 clips x 4096
               frames, N=262144 queries; uniform / random / frame-instant queries, with global outputs + velocities
@@ -682,15 +685,15 @@ def _orient_fit_call(M, tgt, joints, trot, rr0, rt0, start, B, iters, mask, outs
     return lambda: f(*args)
 
 
-def _other_build_pose_fit(path, tgt, rr0, rt0, start, B, iters, outs):
+def _other_build_pose_fit(path, tgt, rr0, rt0, start, B, iters, outs, prior=None, flags=0):
     """rtg_dof_fit_root_f32 (fit_root = 3) of another build of the library (its own handles), for a same-session
-    comparison."""
+    comparison; with ``prior`` its rtg_dof_fit_prior_f32 (K = 0) with that prior and those flags."""
     import ctypes
     import importlib
     from rtg.runtime import ptr, stream_handle
     hu = importlib.import_module("retarget.robot_config.Hu")
     other = ctypes.CDLL(os.path.abspath(path))
-    for name in ("rtg_topology_create", "rtg_dof_model_create", "rtg_dof_fit_root_f32"):
+    for name in ("rtg_topology_create", "rtg_dof_model_create", "rtg_dof_fit_root_f32", "rtg_dof_fit_prior_f32"):
         getattr(other, name).restype, getattr(other, name).argtypes = _lib.SIGNATURES[name]
     i32, f32 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
     host = lambda a, dt: np.ascontiguousarray(np.asarray(a), dt)
@@ -705,6 +708,10 @@ def _other_build_pose_fit(path, tgt, rr0, rt0, start, B, iters, outs):
                                       ctypes.byref(mh)) == 0
     args = (mh, ptr(tgt), None, ptr(rr0), ptr(rt0), ptr(start), B, 1, 3, iters, 0.02, 0.02, 0.02, 0.9, 0.999, 1e-8, 0,
             None, None, None, *(ptr(o) for o in outs), stream_handle())
+    if prior is not None:
+        pargs = (mh, ptr(tgt), None, None, None, None, 0, ptr(prior), None, flags) + args[3:]
+        assert other.rtg_dof_fit_prior_f32(*pargs) == 0
+        return lambda: other.rtg_dof_fit_prior_f32(*pargs)
     assert other.rtg_dof_fit_root_f32(*args) == 0
     return lambda: other.rtg_dof_fit_root_f32(*args)
 
@@ -853,6 +860,101 @@ def prior_fit_traffic(B=262144, iters=32):
     torch.cuda.synchronize()
     return {"B": B, "copy_bytes_each_way": 4 << 26,
             "launches": "3 x 256 MiB copy, 4 x iters=%d with a prior and the projection, no state (dof, root, loss out)" % iters}
+
+
+# made-up collision spheres for the timing alone (the repository holds Hu's skeleton, no collision geometry): S = 8:
+# the torso, the pelvis, both wrist yaw links, both elbow pitch links, both toe links; S = 16: and the neck link, both
+# knees, both shoulders, both grippers and a second torso sphere.  {link, offset, radius}
+APART_SPHERES = ((13, (0, 0, 0.25), 0.16), (0, (0, 0, 0), 0.14), (20, (0.05, 0, 0), 0.05), (29, (0.05, 0, 0), 0.05),
+                 (17, (0, 0, 0), 0.05), (26, (0, 0, 0), 0.05), (6, (0.05, 0, 0), 0.05), (12, (0.05, 0, 0), 0.05),
+                 (32, (0, 0, 0.08), 0.1), (4, (0, 0, 0), 0.06), (10, (0, 0, 0), 0.06), (14, (0, 0, 0), 0.07),
+                 (23, (0, 0, 0), 0.07), (21, (0.08, 0, 0), 0.04), (30, (0.08, 0, 0), 0.04), (13, (0, 0, 0.05), 0.15))
+
+
+def _apart_spec(M, S):
+    """ops.apart on the first S of APART_SPHERES: the default pairs of its first 8 spheres plus, for S = 16, the
+    grippers and the neck against the torso's and each other's side (32 pairs at the most), and the floor z = 0 under
+    the toes, the knees and the wrists."""
+    links, offs, radii = zip(*APART_SPHERES[:S])
+    par = [int(p) for p in assets.parents("hu")]
+    rel = lambda a, b: links[a] == links[b] or par[links[a]] == links[b] or par[links[b]] == links[a]
+    pairs = [(a, b) for a in range(S) for b in range(a + 1, S) if not rel(a, b)]
+    order = sorted(pairs, key=lambda p: (max(p) >= 8, p))   # the first 8 spheres' pairs first
+    return ops.apart(M, links, radii, offs, pairs=order[:32], margin=0.01, floor=(0, 0, 1, 0.0),
+                     floor_links=[6, 12, 4, 10, 20, 29], floor_weight=10.0)
+
+
+def _apart_fit_call(M, tgt, prior, flags, spec, rr0, rt0, start, B, iters, mask, outs):
+    import ctypes
+    from rtg.runtime import ptr, stream_handle
+    f = _lib.lib().rtg_dof_fit_apart_f32
+    args = (M.handle, ptr(tgt), None, None, None, None, 0, ptr(prior), None, flags, ptr(rr0), ptr(rt0), ptr(start), B, 1,
+            mask, iters, 0.02, 0.02, 0.02, 0.9, 0.999, 1e-8, 0, None, None, None, *(ptr(o) for o in outs),
+            ctypes.byref(spec.spec), stream_handle())
+    _lib.check(f(*args))
+    return lambda: f(*args)
+
+
+def apart_fit(B=262144, rounds=4, iters=32):
+    """The pose fit with keep-apart spheres and a floor (rtg_dof_fit_apart_f32, fit_root = 3, a prior and the
+    projection, C ABI, preallocated outputs, 33-link Hu, clip on, no state) per iteration with S = 8 and S = 16 spheres,
+    against rtg_dof_fit_prior_f32 of this build with the same prior and projection, of the build RTG_PARENT_LIB names
+    (when set), and the composed iteration that carries the same penalty (S = 16) in torch; interleaved rounds."""
+    M, tgt, rr0, rt0, start, g_rot = _pose_fit_setup(B, want_rot=True)
+    new = lambda *s: torch.empty(s, device="cuda")
+    outs = (new(B, 32), new(B, 4), new(B, 3), new(B), None, None)
+    prior = _prior_rows(start)
+    specs = {S: _apart_spec(M, S) for S in (8, 16)}
+    calls = {"prior_project_us_per_iteration": _prior_fit_call(M, tgt, (), None, prior, 1, rr0, rt0, start, B, iters, 3, outs)}
+    for S, sp in specs.items():
+        calls[f"apart_s{S}_prior_project_us_per_iteration"] = _apart_fit_call(M, tgt, prior, 1, sp, rr0, rt0, start, B, iters,
+                                                                             3, outs)
+    parent = os.environ.get("RTG_PARENT_LIB")
+    if parent:
+        calls["parent_prior_project_us_per_iteration"] = _other_build_pose_fit(parent, tgt, rr0, rt0, start, B, iters, outs,
+                                                                               prior, 1)
+    a, q, t = (x.clone().requires_grad_(True) for x in (start, rr0, rt0))
+    opt = torch.optim.Adam([dict(params=[a]), dict(params=[t]), dict(params=[q])], lr=0.02, fused=True)
+    hu = __import__("importlib").import_module("retarget.robot_config.Hu")
+    lo, hi = (torch.as_tensor(np.asarray(x), dtype=torch.float32, device="cuda") for x in (hu.Hu_DOF_LOWER, hu.Hu_DOF_UPPER))
+    sp = specs[16]
+    dev = lambda x, dt=torch.float32: torch.as_tensor(np.asarray(x), dtype=dt, device="cuda")
+    lk, off, rad = dev(sp.links, torch.long), dev(sp.spheres[:, :3]), dev(sp.spheres[:, 3])
+    pa, pb = dev(sp.pairs[:, 0], torch.long), dev(sp.pairs[:, 1], torch.long)
+    on = dev([i for i in range(16) if sp.floor_mask >> i & 1], torch.long)
+    n, h0 = dev(sp.plane[:3]), float(sp.plane[3])
+
+    def composed():
+        opt.zero_grad(set_to_none=True)
+        gr, gp = ops.dof_forward_kinematics(M, a, torch.nn.functional.normalize(q, dim=-1, eps=1e-9), t, clip=True)
+        u, w = gr[:, lk, :3], gr[:, lk, 3:]   # unit rotations: v + 2 w (u x v) + 2 u x (u x v)
+        uv = torch.cross(u, off.expand(B, -1, -1), dim=-1)
+        c = gp[:, lk] + off + 2.0 * (w * uv + torch.cross(u, uv, dim=-1))
+        d = (c[:, pa] - c[:, pb]).square().sum(-1).clamp_min(1e-18).sqrt()
+        pen = (rad[pa] + rad[pb] + sp.margin - d).clamp_min(0).square().sum() + \
+            sp.floor_weight * (rad[on] + h0 - c[:, on] @ n).clamp_min(0).square().sum()
+        ((gp - tgt).square().sum() + (a - prior).square().sum() + pen).backward()
+        opt.step()
+        with torch.no_grad():
+            q.copy_(torch.nn.functional.normalize(q, dim=-1, eps=1e-9))
+            a.clamp_(lo, hi)
+
+    res = {k: [] for k in calls}
+    res["composed_s16_prior_project_us_per_iteration"] = []
+    for _ in range(rounds):   # interleaved: all see the same box state
+        for k, call in calls.items():
+            res[k].append(time_events(call, reps=5, warm=1) * 1e3 / iters)
+        res["composed_s16_prior_project_us_per_iteration"].append(time_events(composed, reps=10, warm=2) * 1e3)
+    return {"B": B, "J": 33, "iters": iters, **res, "parent_lib": parent,
+            "spheres": {str(S): int(s.spec.S) for S, s in specs.items()}, "pairs": {str(S): int(s.spec.Pn) for S, s in specs.items()},
+            "residency_tiles_per_cu": {"note": "dynamic LDS per tile", "s8_bytes": 34016 + _apart_lds(33, 16, 8, int(specs[8].spec.Pn)),
+                                       "s16_bytes": 34016 + _apart_lds(33, 16, 16, int(specs[16].spec.Pn))}}
+
+
+def _apart_lds(J, F, S, Pn):
+    """rtg_dof_fit.hip ApartImages: bytes of the keep-apart images of a tile (each image padded to 16 bytes)."""
+    pad = lambda n: (n + 3) // 4 * 4
+    return 4 * (pad(3 * F * S) + 4 * S + pad(S) + pad(J) + 2 * pad(Pn))
 
 
 def motion_sample(N=262144, rounds=4, clips=64, frames=4096):
