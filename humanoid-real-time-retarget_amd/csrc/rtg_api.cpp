@@ -124,6 +124,7 @@ struct rtg_topology_s {
     int32_t gF = 0, gsteps = 0;
     std::vector<int32_t> h_parents;   // host copies, for the plans built over this tree (rtg_retarget_plan_create)
     std::vector<Q> h_tree_quat;
+    std::vector<V> h_local_t;
     TopoView view() const
     {
         return TopoView{parents.get(), local_t.get(), tree_quat.get(), J, gsched.get(), gF, gsteps};
@@ -142,6 +143,12 @@ struct rtg_dof_model_s {
 // SkeletonState.retarget_to: the view (layout, R, scale, roots) and the device blob it points into.
 struct rtg_retarget_plan_s {
     RetargetView view{};
+    DevBuf<float> blob;
+};
+
+// Keypoint targets for the pose fit: the view (layout, constants) and the device blob it points into.
+struct rtg_fit_targets_plan_s {
+    FitTargetsView view{};
     DevBuf<float> blob;
 };
 
@@ -508,7 +515,8 @@ int rtg_topology_create(const int32_t *parents, const float *local_t, const floa
     for (int j = 0; j < J; ++j)
         tq[j] = tree_quat ? Q{tree_quat[4 * j], tree_quat[4 * j + 1], tree_quat[4 * j + 2], tree_quat[4 * j + 3]}
                           : Q{0.f, 0.f, 0.f, 1.f};
-    std::vector<V> lt(J);
+    std::vector<V> &lt = t->h_local_t;
+    lt.resize(J);
     for (int j = 0; j < J; ++j) lt[j] = v3(local_t, j);
     RTG_CHECK(t->parents.alloc(J, "hipMalloc(parents)"));
     RTG_CHECK(t->local_t.alloc(J, "hipMalloc(local_t)"));
@@ -874,6 +882,74 @@ int rtg_retarget_to_f32(rtg_retarget_plan_t p, const float *src_rot, const float
     RTG_TRY(launch_retarget_to(p->view, src_is_local != 0, src_rot, src_root_t, B, tgt_local_rot, tgt_root_t, nullptr,
                                as_stream(stream)),
             "k_retarget_to");
+    return RTG_OK;
+}
+
+// ---------------------------------------------------------------- keypoint targets for the pose fit
+int rtg_fit_targets_plan_tables(int32_t Js, const int32_t *tgt_parents, const float *tgt_local_t, int32_t Jt,
+                                const int32_t *src_joint, const int32_t *tgt_joint, int32_t K, int32_t *anchor,
+                                float *seg, float *weight, int32_t *src_of)
+{
+    const char *fn = "rtg_fit_targets_plan_tables";
+    if (!tgt_parents || !tgt_local_t) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL parents/local_t", fn);
+    RTG_CHECK(check_tree(fn, tgt_parents, Jt));   // the trees rtg_topology_create accepts
+    FitTargetsTables T;
+    std::string err;
+    if (!fit_targets_tables(Js, tgt_parents, tgt_local_t, Jt, src_joint, tgt_joint, K, T, err))
+        return fail_tables(fn, Js, Jt, err);
+    if (anchor) memcpy(anchor, T.anchor.data(), sizeof(int32_t) * K);
+    if (seg) memcpy(seg, T.seg.data(), sizeof(float) * 3 * K);
+    if (weight) memcpy(weight, T.weight.data(), sizeof(float) * Jt);
+    if (src_of) memcpy(src_of, T.src_of.data(), sizeof(int32_t) * Jt);
+    return RTG_OK;
+}
+
+int rtg_fit_targets_plan_create(rtg_topology_t src, rtg_topology_t tgt, const int32_t *src_joint,
+                                const int32_t *tgt_joint, int32_t K, const float *dir, const float *root_scale,
+                                const float *root_offset, rtg_fit_targets_plan_t *out)
+{
+    const char *fn = "rtg_fit_targets_plan_create";
+    if (!out) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: out is NULL", fn);
+    *out = nullptr;
+    if (!src || !tgt) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL topology", fn);
+    const int Js = src->J, Jt = tgt->J;
+    FitTargetsTables T;
+    std::string err;
+    if (!fit_targets_tables(Js, tgt->h_parents.data(), &tgt->h_local_t[0].x, Jt, src_joint, tgt_joint, K, T, err))
+        return fail_tables(fn, Js, Jt, err);
+    std::unique_ptr<rtg_fit_targets_plan_s> p(new (std::nothrow) rtg_fit_targets_plan_s());
+    if (!p) return fail(RTG_ERR_OUT_OF_MEMORY, "%s: host allocation failed", fn);
+    std::vector<float> blob;
+    FitTargetsView &V_ = p->view;
+    fit_targets_blob(T, src_joint, tgt_joint, blob, V_);
+    V_.dir_on = dir != nullptr, V_.scale_on = root_scale != nullptr, V_.offset_on = root_offset != nullptr;
+    if (dir) V_.dir = v3(dir, 0);
+    if (root_scale) V_.root_scale = v3(root_scale, 0);
+    if (root_offset) V_.root_offset = v3(root_offset, 0);
+    RTG_CHECK(p->blob.alloc_upload(blob.data(), blob.size(), "hipMalloc(plan blob)"));
+    V_.blob = p->blob.get();
+    *out = p.release();
+    return RTG_OK;
+}
+
+int rtg_fit_targets_plan_destroy(rtg_fit_targets_plan_t p)
+{
+    delete p;
+    return RTG_OK;
+}
+
+int rtg_fit_targets_f32(rtg_fit_targets_plan_t p, const float *src_pos, int64_t B, float *target_pos,
+                        rtg_stream_t stream)
+{
+    const char *fn = "rtg_fit_targets_f32";
+    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)B);   // needs no handle
+    if (!p) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL plan", fn);
+    if (B == 0) return RTG_OK;
+    if (!src_pos || !target_pos) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    if (B > (int64_t)0x7fffffff * 8) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: batch too large", fn);
+    const Span in{src_pos, (uint64_t)B * p->view.Js * 12u, "src_pos"}, o{target_pos, (uint64_t)B * p->view.Jt * 12u, "target_pos"};
+    RTG_CHECK(check_overlap(fn, &in, 1, &o, 1));
+    RTG_TRY(launch_fit_targets(p->view, src_pos, B, target_pos, as_stream(stream)), "k_fit_targets");
     return RTG_OK;
 }
 

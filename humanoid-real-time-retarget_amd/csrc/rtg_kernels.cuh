@@ -181,6 +181,33 @@ void retarget_blob(const RetargetTables &T, const int32_t *src_parents, const Q 
 // (4 K + 3 floats) of frame 0 there (the t-pose pass of plan creation)
 hipError_t launch_retarget_to(const RetargetView &P, bool local_in, const float *rot, const float *root_t, int64_t B,
                               float *out_rot, float *out_root_t, float *dump, hipStream_t s);
+// Keypoint targets for the pose fit (rtg.h rtg_fit_targets_*; rtg_retarget_to.hip).  The host tables of a mapping of
+// K (source joint, target link) pairs, numbered as given.
+struct FitTargetsTables {
+    int32_t Js = 0, Jt = 0, K = 0;
+    int32_t levels = 0;             // the deepest pair's depth in the reduced target tree (the root pair: 0)
+    std::vector<int32_t> anchor;    // (K) the pair of t_k's nearest mapped proper ancestor, -1 for the root pair
+    std::vector<int32_t> depth;     // (K)
+    std::vector<float> seg;         // (K,3) G[t_k] - G[t_a(k)] in float32
+    std::vector<float> weight;      // (Jt)
+    std::vector<int32_t> src_of;    // (Jt) the pair of link j's nearest mapped ancestor-or-self
+};
+bool fit_targets_tables(int32_t Js, const int32_t *tgt_parents, const float *tgt_local_t, int32_t Jt,
+                        const int32_t *src_joint, const int32_t *tgt_joint, int32_t K, FitTargetsTables &out,
+                        std::string &err);
+// The plan's device blob: K 16-byte entries {seg, code} with code = s_k | s_a << 6 | t_k << 12 | t_a << 18 |
+// depth << 24, then Jt int32 (the row an unmapped link copies, its own for a mapped one); the constants travel in the
+// launch arguments
+struct FitTargetsView {
+    const float *blob;          // device
+    int32_t Js, Jt, K, F;       // F: frames per wave, group_frames(max(Js, Jt))
+    int32_t levels;
+    int32_t dir_on, scale_on, offset_on;
+    V dir, root_scale, root_offset;
+};
+void fit_targets_blob(const FitTargetsTables &T, const int32_t *src_joint, const int32_t *tgt_joint,
+                      std::vector<float> &blob, FitTargetsView &view);
+hipError_t launch_fit_targets(const FitTargetsView &P, const float *src_pos, int64_t B, float *target_pos, hipStream_t s);
 // The zero-pose transform out[f, j] = qmul_norm(qmul_norm(q[f, src[j]], pre), post[j]) as one launch,
 // rtg_rot_ingest.hip.  The handle's device blob, in 16-byte units: pre | post (J_out) | src (J_out int32, padded) | the
 // near-unit table (2 kUnitTabK + 1 entries, written on the device by launch_rot_ingest_tab).

@@ -181,6 +181,113 @@ __global__ __launch_bounds__(64, 4) void k_retarget_to(RetargetView P, const flo
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- fit targets
+// Keypoint targets for the pose fit (rtg.h rtg_fit_targets_*): Retarget.rescale_motion_to_standard_size (main.py:37-47)
+// across two trees joined by K (source joint, target link) pairs.  A tile is one wave and F frames.  The source rows
+// come in as coalesced pieces into an LDS image; every (frame, pair) item then writes its own term into the output
+// image's row t_k -- the root pair its row, any other pair d / scale, k_rescale_motion's expressions on the pair's
+// source rows and its target segment -- and the rows are summed level by level of the reduced target tree,
+// out[t_k] = out[t_a(k)] + term, so every row is the one chain of additions taken parents first whichever lane does
+// it; the unmapped links copy their nearest mapped ancestor's row and the image leaves as whole-wave non-temporal
+// stores.  LDS: FitTargetsImages, 12 F (Js + Jt) + 16 K + 4 Jt bytes.
+struct FitTargetsImages {
+    float *src;   // [F Js 3] the source rows
+    float *out;   // [F Jt 3] the target rows
+    f4v *tab;     // [K] {norm(seg), -, -, code}
+    int *cp;      // [Jt] the row link j copies (its own when mapped)
+    size_t floats;
+    __host__ __device__ FitTargetsImages(float *base, const FitTargetsView &P)
+    {
+        LdsCarve c(base);
+        src = c.take<float>((size_t)3 * P.F * P.Js);
+        out = c.take<float>((size_t)3 * P.F * P.Jt);
+        tab = c.take<f4v>(P.K);
+        cp = c.take<int>(P.Jt);
+        floats = c.floats;
+    }
+};
+
+template <int F>
+__global__ __launch_bounds__(64) void k_fit_targets(FitTargetsView P, const float *__restrict__ src_pos, int64_t B,
+                                                    float *__restrict__ target_pos)
+{
+    extern __shared__ __attribute__((aligned(16))) float ft_lds[];
+    const int lane = (int)threadIdx.x;
+    const int Js = P.Js, Jt = P.Jt, K = P.K;
+    const int64_t f0 = (int64_t)blockIdx.x * F;
+    const int nfr = tile_frames<F>(B, f0);
+    const FitTargetsImages I(ft_lds, P);
+    float *src = I.src, *out = I.out;
+    f4v *tab = I.tab;
+    int *cp = I.cp;
+
+    // the tile's rows, all loads in flight; the plan's tables meanwhile (a segment's norm once per tile)
+    const float *g_src = src_pos + f0 * Js * 3;
+    PosRows<F> rows;
+    rows.load(g_src, 3 * nfr * Js);
+    {
+        const f4v *gb = reinterpret_cast<const f4v *>(P.blob);
+        for (int i = lane; i < K; i += 64) {
+            f4v e = gb[i];
+            e.x = lnorm3(V{e.x, e.y, e.z});
+            tab[i] = e;
+        }
+        const int *gc = reinterpret_cast<const int *>(gb + K);
+        for (int j = lane; j < Jt; j += 64) cp[j] = gc[j];
+    }
+    rows.to_lds(src, g_src, 3 * nfr * Js);
+    wave_sync();
+
+    auto mp = [&](const float *p) {   // coord_transform(dir) (main.py:170)
+        const V v{p[0], p[1], p[2]};
+        return P.dir_on ? V{v.x * P.dir.x, v.y * P.dir.y, v.z * P.dir.z} : v;
+    };
+    const int nk = nfr * K;
+    const float rK = item_rcp(K);
+    for (int i = lane; i < nk; i += 64) {   // every pair's own term
+        const Item it = item_split(i, rK, K);
+        const f4v e = tab[it.j];
+        const int code = __float_as_int(e.w);
+        const int sk = code & 63, sa = (code >> 6) & 63, tk = (code >> 12) & 63, depth = (code >> 24) & 63;
+        const float *sf = src + 3 * it.fr * Js;
+        V r = mp(sf + 3 * sk);
+        if (depth == 0) {   // the root pair
+            if (P.scale_on) r = V{r.x * P.root_scale.x, r.y * P.root_scale.y, r.z * P.root_scale.z};
+            if (P.offset_on) r = V{r.x + P.root_offset.x, r.y + P.root_offset.y, r.z + P.root_offset.z};
+        } else {
+            const V d = vsub(r, mp(sf + 3 * sa));
+            const float scale = lnorm3(d) / e.x;
+            r = vdiv(d, scale);
+        }
+        float *o = out + 3 * (it.fr * Jt + tk);
+        o[0] = r.x; o[1] = r.y; o[2] = r.z;
+    }
+    wave_sync();
+    for (int lv = 1; lv <= P.levels; ++lv) {   // parents first: a level's anchors are all of lower levels
+        for (int i = lane; i < nk; i += 64) {
+            const Item it = item_split(i, rK, K);
+            const int code = __float_as_int(tab[it.j].w);
+            if (((code >> 24) & 63) != lv) continue;
+            float *o = out + 3 * (it.fr * Jt + ((code >> 12) & 63));
+            const float *a = out + 3 * (it.fr * Jt + ((code >> 18) & 63));
+            o[0] = a[0] + o[0]; o[1] = a[1] + o[1]; o[2] = a[2] + o[2];
+        }
+        wave_sync();
+    }
+    const int nj = nfr * Jt;
+    const float rJ = item_rcp(Jt);
+    for (int i = lane; i < nj; i += 64) {   // the unmapped links
+        const Item it = item_split(i, rJ, Jt);
+        const int c = cp[it.j];
+        if (c == it.j) continue;
+        float *o = out + 3 * i;
+        const float *a = out + 3 * (it.fr * Jt + c);
+        o[0] = a[0]; o[1] = a[1]; o[2] = a[2];
+    }
+    wave_sync();
+    PosRows<F>::out(out, target_pos + f0 * Jt * 3, 3 * nj);
+}
+
 // ---------------------------------------------------------------------------------------------------- host
 static void reduce_tree(const int32_t *parents, int32_t J, const std::vector<char> &keep, std::vector<int32_t> &kept,
                         std::vector<int32_t> &red_par)
@@ -295,6 +402,93 @@ hipError_t launch_retarget_to(const RetargetView &P, bool local_in, const float 
         hipLaunchKernelGGL((k_retarget_to<li(), f()>), dim3(grid_for(B, P.F)), dim3(64), lds, s, P, rot, root_t, B, out_rot,
                            out_root_t, dump);
     }, local_in);
+    return hipGetLastError();
+}
+
+bool fit_targets_tables(int32_t Js, const int32_t *tp, const float *tlt, int32_t Jt, const int32_t *sj,
+                        const int32_t *tj, int32_t K, FitTargetsTables &out, std::string &err)
+{
+    char buf[160];
+    if (Js < 1 || Jt < 1 || Js > kGroupMaxJ || Jt > kGroupMaxJ) {
+        snprintf(buf, sizeof buf, "fit targets serve trees of 1..%d joints (source %d, target %d)", kGroupMaxJ, Js, Jt);
+        err = buf;
+        return false;
+    }
+    if (K < 1 || !sj || !tj) {
+        err = "the joint mapping is empty";
+        return false;
+    }
+    std::vector<int32_t> pair_of(Jt, -1), seen_s(Js, -1);
+    for (int i = 0; i < K; ++i) {
+        if (sj[i] < 0 || sj[i] >= Js || tj[i] < 0 || tj[i] >= Jt) {
+            snprintf(buf, sizeof buf, "mapping pair %d = (%d, %d) is out of range (source %d, target %d joints)", i,
+                     sj[i], tj[i], Js, Jt);
+            err = buf;
+            return false;
+        }
+        if (seen_s[sj[i]] >= 0 || pair_of[tj[i]] >= 0) {
+            const bool s = seen_s[sj[i]] >= 0;
+            snprintf(buf, sizeof buf, "%s joint %d is named twice (pairs %d and %d)", s ? "source" : "target",
+                     s ? sj[i] : tj[i], s ? seen_s[sj[i]] : pair_of[tj[i]], i);
+            err = buf;
+            return false;
+        }
+        seen_s[sj[i]] = pair_of[tj[i]] = i;
+    }
+    if (pair_of[0] < 0) {
+        err = "the target root is not mapped";
+        return false;
+    }
+    out = FitTargetsTables{};
+    out.Js = Js, out.Jt = Jt, out.K = K;
+    std::vector<float> G((size_t)3 * Jt, 0.0f);   // the zero pose's global translations, parents first, G[root] = 0
+    for (int j = 1; j < Jt; ++j)
+        for (int c = 0; c < 3; ++c) G[3 * j + c] = G[3 * tp[j] + c] + tlt[3 * j + c];
+    out.src_of.resize(Jt);
+    out.weight.resize(Jt);
+    for (int j = 0; j < Jt; ++j) {
+        int a = j;
+        while (pair_of[a] < 0) a = tp[a];   // ends at the root, which is mapped
+        out.src_of[j] = pair_of[a];
+        out.weight[j] = pair_of[j] >= 0 ? 1.0f : 0.0f;
+    }
+    out.anchor.assign(K, -1);
+    out.depth.assign(K, 0);
+    out.seg.assign((size_t)3 * K, 0.0f);
+    for (int j = 1; j < Jt; ++j) {   // ascending target index: an anchor's depth is there before its pairs ask
+        const int k = pair_of[j];
+        if (k < 0) continue;
+        const int a = out.src_of[tp[j]], ta = tj[a];
+        out.anchor[k] = a;
+        out.depth[k] = out.depth[a] + 1;
+        out.levels = std::max(out.levels, out.depth[k]);
+        for (int c = 0; c < 3; ++c) out.seg[3 * k + c] = G[3 * j + c] - G[3 * ta + c];
+    }
+    return true;
+}
+
+void fit_targets_blob(const FitTargetsTables &T, const int32_t *sj, const int32_t *tj, std::vector<float> &blob,
+                      FitTargetsView &V_)
+{
+    const int K = T.K, Jt = T.Jt;
+    V_.Js = T.Js, V_.Jt = Jt, V_.K = K, V_.F = group_frames(std::max(T.Js, Jt)), V_.levels = T.levels;
+    blob.assign((size_t)4 * K + (size_t)((Jt + 3) & ~3), 0.0f);
+    for (int k = 0; k < K; ++k) {
+        const int a = T.anchor[k] < 0 ? k : T.anchor[k];
+        const int32_t code = sj[k] | (sj[a] << 6) | (tj[k] << 12) | (tj[a] << 18) | (T.depth[k] << 24);
+        memcpy(&blob[4 * (size_t)k], &T.seg[3 * (size_t)k], sizeof(float) * 3);
+        memcpy(&blob[4 * (size_t)k + 3], &code, sizeof code);
+    }
+    int32_t *cp = reinterpret_cast<int32_t *>(blob.data() + 4 * (size_t)K);
+    for (int j = 0; j < Jt; ++j) cp[j] = tj[T.src_of[j]];
+}
+
+hipError_t launch_fit_targets(const FitTargetsView &P, const float *src_pos, int64_t B, float *target_pos, hipStream_t s)
+{
+    const size_t lds = sizeof(float) * FitTargetsImages(nullptr, P).floats;
+    group_dispatch(P.F, [&](auto f) {
+        hipLaunchKernelGGL((k_fit_targets<f()>), dim3(grid_for(B, P.F)), dim3(64), lds, s, P, src_pos, B, target_pos);
+    });
     return hipGetLastError();
 }
 

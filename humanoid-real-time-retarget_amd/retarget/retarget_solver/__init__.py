@@ -8,6 +8,7 @@ from retarget.retarget_solver.retarget_solver import HuUpperBodyFromMocapRetarge
 from retarget.retarget_solver.body_retargeter import Mocap2HuBodyRetargeter
 from retarget.retarget_solver.full_body_retargeter import VtrdynFullBodyRetargeter
 from retarget.retarget_solver.full_body_pos_retargeter import VtrdynFullBodyPosRetargeter
+from retarget.retarget_solver.full_body_fit_retargeter import VtrdynFullBodyFitRetargeter   # not in the reference
 
 __all__ = ['HuUpperBodyFromMocapRetarget', 'Mocap2HuBodyRetargeter', 'VtrdynFullBodyRetargeter',
-           'VtrdynFullBodyPosRetargeter']
+           'VtrdynFullBodyPosRetargeter', 'VtrdynFullBodyFitRetargeter']

@@ -14,8 +14,8 @@ import torch
 
 from robot_kinematics_model.base_forward_model import BaseForwardModel
 from rtg import ops
-from rtg.bridge import home_device, topology
-from rtg.runtime import DofModel
+from rtg.bridge import fit_targets_plan, home_device, topology
+from rtg.runtime import DofModel, require_gpu_rtg
 
 
 def _default_tables(num_dofs: int):
@@ -181,6 +181,55 @@ class HuForwardModel(BaseForwardModel):
                                 return_grad=want_grad and r == rounds - 1, **prior, **fit_pose_keywords)
             a, t, q, state = res[0], res[1], res[2], res[4]
         return res
+
+    def keypoint_targets(self, source_tree, joint_mapping, source_positions, dir=None, root_scale=None,
+                         root_offset=None):
+        """Where fit_pose's ``target_positions`` come from: mocap keypoints of a body of other proportions, every
+        mapped limb rescaled to this robot's length (ops.fit_targets, one launch).  ``source_tree``: the mocap
+        skeleton (node_names, parent_indices, local_translation); ``joint_mapping``: {source name: target name}, as
+        ``retarget_to`` takes it, the robot's root among the targets; ``source_positions`` (L, J_s, 3) global
+        positions.  ``dir`` (3,) flips the source axes (coord_transform), ``root_scale`` (3,) scales the root's travel
+        (ops.limb_ratio of a foot gives the leg-length ratio), ``root_offset`` (3,) is added after it.  ->
+        ((L, J, 3) targets, (J,) weight): the weight is 1 for the mapped links and 0 for the others, whose rows are
+        finite placeholders.  Plans are cached per (tree, mapping, constants)."""
+        require_gpu_rtg()
+        src_names, names = list(source_tree.node_names), list(self.node_names)
+        sj, tj = [], []
+        for s, t in joint_mapping.items():
+            if s not in src_names:
+                raise ValueError(f"joint_mapping: the source skeleton has no node named {s!r}")
+            if t not in names:
+                raise ValueError(f"joint_mapping: the skeleton has no node named {t!r}")
+            sj.append(src_names.index(s))
+            tj.append(names.index(t))
+        plan = fit_targets_plan((source_tree.parent_indices, source_tree.local_translation),
+                                (self.parent_indices, self.sk_local_translation), sj, tj, dir, root_scale, root_offset)
+        targets = ops.fit_targets(plan, source_positions)
+        return targets, torch.from_numpy(plan.weight.copy()).to(targets.device)
+
+    def fit_mocap(self, source_tree, joint_mapping, source_positions, motion_root_rotation=None,
+                  motion_joint_angles=None, smooth_weight=0.0, dir=None, root_scale=None, root_offset=None, weight=None,
+                  **fit_keywords):
+        """Mocap keypoints to a pose in two launches: keypoint_targets, then fit_pose -- or fit_motion when
+        ``smooth_weight > 0`` -- on them.  The root translation starts at the root's target row, the root rotation at
+        ``motion_root_rotation`` (L, 1, 4) or the identity, the angles at ``motion_joint_angles`` or fit_pose's
+        default; the plan's weight masks the unmapped links (multiplied into ``weight`` (J,) when given).  The other
+        keywords are fit_pose's (fit_motion's with smoothing).  Returns what they return, plus the targets."""
+        targets, w = self.keypoint_targets(source_tree, joint_mapping, source_positions, dir, root_scale, root_offset)
+        lead = tuple(targets.shape[:-2])
+        t0 = targets[..., 0, :].clone()
+        q0 = motion_root_rotation
+        if q0 is None:
+            q0 = torch.zeros(lead + (1, 4), device=targets.device, dtype=torch.float32)
+            q0[..., 3] = 1.0
+        if weight is not None:
+            w = w * torch.as_tensor(weight, dtype=torch.float32).to(w.device)
+        if float(smooth_weight) > 0.0:
+            res = self.fit_motion(targets, t0, q0, motion_joint_angles, smooth_weight=smooth_weight, weight=w,
+                                  **fit_keywords)
+        else:
+            res = self.fit_pose(targets, t0, q0, motion_joint_angles, weight=w, **fit_keywords)
+        return tuple(res) + (targets,)
 
     def _clip_angles(self, motion_joint_angles):
         """:27-33, forward value: (clamp(a, lo, hi) - a) + a, elementwise on the angles' device."""

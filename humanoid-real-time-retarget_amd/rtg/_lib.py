@@ -148,6 +148,13 @@ SIGNATURES = {
     "rtg_retarget_to_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "rtg_retarget_plan_tables": (c_int, [POINTER(c_int32), c_int32, POINTER(c_int32), c_int32, POINTER(c_int32),
                                          POINTER(c_int32), c_int32] + [POINTER(c_int32)] * 6),
+    "rtg_fit_targets_plan_create": (c_int, [c_void_p, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int32,
+                                            POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_void_p)]),
+    "rtg_fit_targets_plan_destroy": (c_int, [c_void_p]),
+    "rtg_fit_targets_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rtg_fit_targets_plan_tables": (c_int, [c_int32, POINTER(c_int32), POINTER(c_float), c_int32, POINTER(c_int32),
+                                            POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_float),
+                                            POINTER(c_float), POINTER(c_int32)]),
     "rtg_rot_ingest_create": (c_int, [c_int32, c_int32, POINTER(c_int32), POINTER(c_float), POINTER(c_float),
                                       POINTER(c_void_p)]),
     "rtg_rot_ingest_destroy": (None, [c_void_p]),

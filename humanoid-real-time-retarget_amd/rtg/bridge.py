@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .runtime import RetargetPlan, Topology, require_gpu, require_gpu_rtg
+from .runtime import FitTargetsPlan, RetargetPlan, Topology, require_gpu, require_gpu_rtg
 
 
 def as_tensor(x) -> torch.Tensor:
@@ -71,6 +71,7 @@ def topology(parent_indices, local_translation, tree_quat=None) -> Topology:
 
 
 _PLAN_CACHE: dict = {}
+_FIT_PLAN_CACHE: dict = {}
 
 
 def retarget_plan(src_tree, tgt_tree, src_joint, tgt_joint, src_tpose_local_rot, src_tpose_root_t,
@@ -89,6 +90,24 @@ def retarget_plan(src_tree, tgt_tree, src_joint, tgt_joint, src_tpose_local_rot,
     if plan is None:
         plan = RetargetPlan(topology(*trees[0]), topology(*trees[1]), sj, tj, *consts, float(sc))
         _PLAN_CACHE[k] = plan
+    return plan
+
+
+def fit_targets_plan(src_tree, tgt_tree, src_joint, tgt_joint, dir=None, root_scale=None,
+                     root_offset=None) -> FitTargetsPlan:
+    """The device-resident plan of a keypoint-target launch (``ops.fit_targets``), cached by content like
+    ``retarget_plan``.  src_tree / tgt_tree: (parent_indices, local_translation[, quat]) of the two skeleton trees; the
+    mapping as joint index pairs; dir / root_scale / root_offset: 3 values each or None."""
+    require_gpu_rtg()
+    sj, tj = _np(src_joint, np.int32), _np(tgt_joint, np.int32)
+    consts = [_np(a, np.float32) for a in (dir, root_scale, root_offset)]
+    trees = [(_np(t[0], np.int32), _np(t[1], np.float32), _np(t[2], np.float32) if len(t) > 2 else None)
+             for t in (src_tree, tgt_tree)]
+    k = _key(*trees[0], *trees[1], sj, tj, *consts)
+    plan = _FIT_PLAN_CACHE.get(k)
+    if plan is None:
+        plan = FitTargetsPlan(topology(*trees[0]), topology(*trees[1]), sj, tj, *consts)
+        _FIT_PLAN_CACHE[k] = plan
     return plan
 
 

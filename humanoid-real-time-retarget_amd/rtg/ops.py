@@ -16,7 +16,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import check, lib
-from .runtime import (MotionLib, RetargetPlan, Topology, dev_f32, layout_code, ptr, require_gpu, require_gpu_rtg,
+from .runtime import (FitTargetsPlan, MotionLib, RetargetPlan, Topology, dev_f32, layout_code, ptr, require_gpu, require_gpu_rtg,
                       stream_handle)
 
 
@@ -962,6 +962,59 @@ def rescale_motion(topo: Topology, motion, dir=None):
         d = dv.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
     check(lib().rtg_rescale_motion_f32(topo.handle, ptr(m), B, d, ptr(out), stream_handle()))
     return out
+
+
+def fit_targets(plan: FitTargetsPlan, src_pos):
+    """Keypoint targets for the pose fit from mocap positions of a body of other proportions, in one launch (rtg.h
+    rtg_fit_targets_f32): source positions (..., J_s, 3) -> target positions (..., J_t, 3) on the input's device, every
+    mapped limb rescaled to the target skeleton's length and hung from its nearest mapped ancestor, the unmapped links
+    placeholders of weight 0 (``plan.weight``).  Raises RtgError without a GPU: there is no CPU fallback."""
+    require_gpu_rtg()
+    Js, Jt = plan.num_source_joints, plan.num_target_joints
+    home = src_pos.device if isinstance(src_pos, torch.Tensor) else torch.device("cpu")
+    x = dev_f32(src_pos, (Js, 3), "source_positions")
+    if x.device != plan.device:
+        raise ValueError(f"source_positions is on {x.device}; this plan lives on {plan.device}")
+    lead = tuple(x.shape[:-2])
+    B = int(torch.Size(lead).numel())
+    out = torch.empty(lead + (Jt, 3), device=x.device, dtype=torch.float32)
+    check(lib().rtg_fit_targets_f32(plan.handle, ptr(x), B, ptr(out), stream_handle()))
+    return out if out.device == home else out.to(home)
+
+
+def fit_targets_tables(num_source_joints, tgt_parents, tgt_local_translation, src_joint, tgt_joint) -> dict:
+    """The host tables of a keypoint-target plan (rtg.h rtg_fit_targets_plan_tables; no GPU needed): anchor (K), seg
+    (K, 3), weight (J_t), src_of (J_t)."""
+    from .runtime import fit_targets_tables as tables
+    return tables(num_source_joints, tgt_parents, tgt_local_translation, src_joint, tgt_joint)
+
+
+def limb_ratio(src_tree, tgt_tree, mapping, link) -> float:
+    """The root-travel scale of a keypoint-target plan (host only): over the mapped pairs on the path root -> ``link``
+    of the target tree, the summed length of the target zero pose's segments over the same sum in the source zero
+    pose -- for a foot, target leg length over source leg length.  src_tree / tgt_tree: (parent_indices,
+    local_translation[, ...]); mapping: (src_joint, tgt_joint) index arrays; link: a target joint index."""
+    import numpy as np
+    sp, tp = (np.asarray(t[0], np.int64).reshape(-1) for t in (src_tree, tgt_tree))
+    slt, tlt = (np.asarray(t[1].cpu() if isinstance(t[1], torch.Tensor) else t[1], np.float32).reshape(-1, 3)
+                for t in (src_tree, tgt_tree))
+    sj, tj = (np.asarray(a, np.int32).reshape(-1) for a in mapping)
+    tab = fit_targets_tables(len(sp), tp, tlt, sj, tj)
+    if not 0 <= int(link) < len(tp):
+        raise ValueError(f"link {link} is outside 0..{len(tp) - 1}")
+    Gs = np.zeros_like(slt)   # the source zero pose's global translations, as the plan takes the target's
+    for j in range(1, len(sp)):
+        Gs[j] = Gs[sp[j]] + slt[j]
+    k = int(tab["src_of"][int(link)])
+    num = den = 0.0
+    while tab["anchor"][k] >= 0:
+        a = int(tab["anchor"][k])
+        num += float(np.linalg.norm(tab["seg"][k].astype(np.float64)))
+        den += float(np.linalg.norm((Gs[sj[k]] - Gs[sj[a]]).astype(np.float64)))
+        k = a
+    if den == 0.0:
+        raise ValueError(f"no mapped source segment of non-zero length between the root and link {link}")
+    return num / den
 
 
 def quat_between_two_vecs(v1, v2):

@@ -188,6 +188,61 @@ class RetargetPlan(Handle):
         self.device = torch.device("cuda", torch.cuda.current_device())   # owns the constants (rtg.h)
 
 
+def fit_targets_tables(num_source_joints: int, tgt_parents, tgt_local_translation, src_joint, tgt_joint) -> dict:
+    """rtg_fit_targets_plan_tables (host only, no GPU needed): the tables of a keypoint-target plan -- anchor (K) the
+    pair of the nearest mapped proper ancestor (-1: the root pair), seg (K, 3) the target zero pose's segment between
+    the two, weight (J_t) 1 for a mapped link, src_of (J_t) the pair of a link's nearest mapped ancestor-or-self.  Pairs
+    are numbered as given.  A bad mapping raises RtgError with the reason."""
+    tp, sj, tj = (_host_i32(a).reshape(-1) for a in (tgt_parents, src_joint, tgt_joint))
+    lt = _host_f32(tgt_local_translation).reshape(-1, 3)
+    if sj.shape != tj.shape:
+        raise ValueError("src_joint / tgt_joint lengths differ")
+    if lt.shape[0] != tp.shape[0]:
+        raise ValueError("parent_indices / local_translation lengths differ")
+    K, Jt = int(sj.shape[0]), int(tp.shape[0])
+    out = {"anchor": np.zeros(max(K, 1), np.int32), "seg": np.zeros((max(K, 1), 3), np.float32),
+           "weight": np.zeros(max(Jt, 1), np.float32), "src_of": np.zeros(max(Jt, 1), np.int32)}
+    ip, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+    check(lib().rtg_fit_targets_plan_tables(int(num_source_joints), tp.ctypes.data_as(ip), lt.ctypes.data_as(fp), Jt,
+                                            sj.ctypes.data_as(ip), tj.ctypes.data_as(ip), K,
+                                            out["anchor"].ctypes.data_as(ip), out["seg"].ctypes.data_as(fp),
+                                            out["weight"].ctypes.data_as(fp), out["src_of"].ctypes.data_as(ip)))
+    return {k: v[:(K if k in ("anchor", "seg") else Jt)] for k, v in out.items()}
+
+
+class FitTargetsPlan(Handle):
+    """Everything of a keypoint-target launch that does not depend on the frame (``rtg_fit_targets_plan_t``): the two
+    trees, the joint mapping as index pairs and the constants dir / root_scale / root_offset (3 floats each or None).
+    ``weight`` (J_t,) is the pose fit's weight mask of the mapped links; ``tables`` the host tables."""
+    _destroy = "rtg_fit_targets_plan_destroy"
+
+    def __init__(self, src: Topology, tgt: Topology, src_joint, tgt_joint, dir=None, root_scale=None, root_offset=None):
+        require_gpu_rtg()
+        sj, tj = _host_i32(src_joint).reshape(-1), _host_i32(tgt_joint).reshape(-1)
+        if sj.shape != tj.shape:
+            raise ValueError("src_joint / tgt_joint lengths differ")
+        consts = []
+        for a, name in ((dir, "dir"), (root_scale, "root_scale"), (root_offset, "root_offset")):
+            a = None if a is None else _host_f32(a).reshape(-1)
+            if a is not None and a.shape[0] != 3:
+                raise ValueError(f"{name}: expected 3 values, got {a.shape[0]}")
+            consts.append(a)
+        ip, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        h = ctypes.c_void_p()
+        check(lib().rtg_fit_targets_plan_create(src.handle, tgt.handle, sj.ctypes.data_as(ip), tj.ctypes.data_as(ip),
+                                                int(sj.shape[0]),
+                                                *(None if a is None else a.ctypes.data_as(fp) for a in consts),
+                                                ctypes.byref(h)))
+        self._h = h
+        self.src, self.tgt = src, tgt
+        self.num_source_joints, self.num_target_joints = src.num_joints, tgt.num_joints
+        self.src_joint, self.tgt_joint = sj, tj
+        self.dir, self.root_scale, self.root_offset = consts
+        self.tables = fit_targets_tables(src.num_joints, tgt.parents, tgt.local_translation, sj, tj)
+        self.weight = self.tables["weight"]
+        self.device = torch.device("cuda", torch.cuda.current_device())   # owns the tables (rtg.h)
+
+
 class MotionLib(Handle):
     """The clip table of a motion library (``rtg_motion_lib_t``): per clip its first row in the packed arrays, its
     length in frames and its frame rate.  The arrays themselves stay with the caller (``ops.motion_sample``).  The

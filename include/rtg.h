@@ -405,6 +405,50 @@ int rtg_retarget_plan_tables(const int32_t *src_parents, int32_t J_s, const int3
                              int32_t *perm, int32_t *src_of);
 
 /* ------------------------------------------------------------------------
+ * Keypoint targets for the pose fit from mocap positions of a body of other proportions: the limb-wise rescale of
+ * Retarget.rescale_motion_to_standard_size (retarget/main.py:37-47) across TWO skeletons joined by a joint mapping,
+ * as ONE launch.  src_joint[K] / tgt_joint[K]: the mapping as index pairs (source joint s_k -> target link t_k).
+ *
+ * The plan, evaluated on the host: a(k) is the pair whose target link is the nearest mapped proper ancestor of t_k in
+ * the target tree; G the target zero pose's global translations, float32 sums taken parents first (G[root] = 0,
+ * G[j] = G[parent] + local_t[j]); seg[k] = G[t_k] - G[t_a(k)] in float32; weight[j] = 1 for a mapped link, else 0;
+ * src_of[j] the pair of link j's nearest mapped ancestor-or-self.
+ *
+ * The launch, per frame, every operation one float32 rounding (no FMA):
+ *   m(j) = src_pos[j], or src_pos[j] * dir per component with dir (coord_transform, transform3d.py:24-29);
+ *   the root pair:   out[t] = m(s), then * root_scale, then + root_offset (an absent operand adds no operation: with
+ *                    all three NULL the root row keeps the source row's bits);
+ *   any other pair:  d = m(s_k) - m(s_a(k)); scale = norm(d) / norm(seg[k]); out[t_k] = out[t_a(k)] + d / scale, with
+ *                    torch.linalg.norm's sqrt(fma(z, z, fma(y, y, x x))): rtg_rescale_motion_f32's expressions;
+ *   an unmapped link j: out[j] = out[t_src_of(j)], a finite placeholder whose weight is 0.
+ * With the same tree on both sides and the identity mapping this is rtg_rescale_motion_f32 wherever seg[k] has
+ * local_t[k]'s bits.  A zero-length target segment is accepted (scale = inf: the child sits on its anchor).
+ *
+ * dir, root_scale, root_offset: 3 host floats each or NULL, copied into the plan.  The tables are copied to the
+ * current device (synchronously); use the plan on that device only.  RTG_ERR_INVALID_ARGUMENT -- a NULL handle or
+ * buffer, K < 1, an index out of range, a joint named twice on either side, the target root not mapped, B < 0,
+ * overlapping buffers -- and RTG_ERR_UNSUPPORTED -- more than 64 joints on either side -- are decided before any HIP
+ * call, with the reason in rtg_last_error().
+ * ---------------------------------------------------------------------- */
+typedef struct rtg_fit_targets_plan_s *rtg_fit_targets_plan_t;
+int rtg_fit_targets_plan_create(rtg_topology_t src, rtg_topology_t tgt, const int32_t *src_joint,
+                                const int32_t *tgt_joint, int32_t K, const float *dir, const float *root_scale,
+                                const float *root_offset, rtg_fit_targets_plan_t *out);
+int rtg_fit_targets_plan_destroy(rtg_fit_targets_plan_t plan);
+/* src_pos (B,J_s,3) -> target_pos (B,J_t,3), device memory of any float alignment (16-byte aligned rows move as
+ * whole pieces).  Never allocates or synchronises; B == 0 is a no-op.  A frame's NaN / inf stays in that frame's
+ * rows, in the links hung from the segment that has it. */
+int rtg_fit_targets_f32(rtg_fit_targets_plan_t plan, const float *src_pos, int64_t B, float *target_pos,
+                        rtg_stream_t stream);
+/* The host tables of a plan (host only, no HIP call).  tgt_parents / tgt_local_t as for rtg_topology_create; of the
+ * source tree only its joint count matters.  Every output may be NULL: anchor (K) the pair a(k), -1 for the root
+ * pair; seg (K,3), zeros for the root pair; weight (J_t); src_of (J_t).  Pairs are numbered as given.  Same validation
+ * and messages as rtg_fit_targets_plan_create. */
+int rtg_fit_targets_plan_tables(int32_t J_s, const int32_t *tgt_parents, const float *tgt_local_t, int32_t J_t,
+                                const int32_t *src_joint, const int32_t *tgt_joint, int32_t K, int32_t *anchor,
+                                float *seg, float *weight, int32_t *src_of);
+
+/* ------------------------------------------------------------------------
  * VTRDyn ingest (sim_full_body_teleop.py:92, :109-112)
  * ---------------------------------------------------------------------- */
 /* Raw broadcast frames body_pos (B,23,3), left/right_hand_pos (B,20,3) -> solver inputs body (B,21,3)

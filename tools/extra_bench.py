@@ -44,9 +44,17 @@
               quat_normalize, torch blends, forward_kinematics), interleaved rounds, the results compared bit for bit
   motion_sample_traffic -- a few launches of the fused sampler and a 256 MiB copy of known bytes, for a counter run of
               its own against the algorithmic bytes that `motion_sample` prints
+  fit_targets -- the keypoint targets of the pose fit (rtg_fit_targets_f32, C ABI, preallocated outputs; VTRDyn-21 ->
+              33-link Hu, the 15 pairs of tests/golden/retarget_to_names.json's vtrdyn_full_hu, B=262144, dir on) against
+              the composition of launches that were there before it (index_select of the mapped rows,
+              rtg_rescale_motion_f32 on the reduced tree whose local translations are the plan's segments, index_select
+              through src_of), interleaved rounds, the results compared bit for bit
+  fit_targets_traffic -- a few launches of rtg_fit_targets_f32 and a 256 MiB copy of known bytes, for a counter run of
+              its own against the 12 (J_s + J_t) bytes per frame that `fit_targets` prints
 """
 from __future__ import annotations
 
+import ctypes
 import json
 import os
 import sys
@@ -1070,6 +1078,77 @@ def motion_sample_traffic(N=262144, clips=64, frames=4096):
     torch.cuda.synchronize()
     return {"N": N, "copy_bytes_each_way": 4 << 26,
             "launches": "3 x 256 MiB copy, 3 x global + vec (STATE), 3 x local only; random (clip, time)"}
+
+
+def _fit_targets_setup(B):
+    from rtg.runtime import FitTargetsPlan, fit_targets_tables
+    with open(os.path.join(G, "retarget_to_names.json")) as f:
+        c = json.load(f)["vtrdyn_full_hu"]
+    src_names = [str(n) for n in assets.load("vtrdyn")["node_names"]]
+    sj = np.array([src_names.index(s) for s in c["mapping"]], np.int32)
+    tj = np.array([c["target_names"].index(t) for t in c["mapping"].values()], np.int32)
+    S, T = topo("vtrdyn"), topo("hu")
+    dir_ = [-1.0, -1.0, 1.0]
+    plan = FitTargetsPlan(S, T, sj, tj, dir=dir_)
+    tab = fit_targets_tables(S.num_joints, T.parents, T.local_translation, sj, tj)
+    gen = torch.Generator(device="cuda").manual_seed(29)
+    x = torch.randn((B, S.num_joints, 3), device="cuda", generator=gen)
+    return plan, tab, sj, tj, dir_, x
+
+
+def fit_targets(B=262144, rounds=4):
+    from rtg.runtime import ptr, stream_handle
+    lib = _lib.lib()
+    plan, tab, sj, tj, dir_, x = _fit_targets_setup(B)
+    Js, Jt, K = plan.num_source_joints, plan.num_target_joints, len(sj)
+    order = np.argsort(tj)   # the reduced tree: the pairs by ascending target index
+    rank = np.empty_like(order)
+    rank[order] = np.arange(K)
+    red = Topology(np.array([-1 if tab["anchor"][k] < 0 else rank[tab["anchor"][k]] for k in order], np.int32),
+                   tab["seg"][order])
+    pick = torch.as_tensor(sj[order].astype(np.int64), device="cuda")
+    spread = torch.as_tensor(rank[tab["src_of"]].astype(np.int64), device="cuda")
+    d3 = (ctypes.c_float * 3)(*dir_)
+    out, rows, resc, comp = (torch.empty((B, n, 3), device="cuda") for n in (Jt, K, K, Jt))
+
+    def fused():
+        _lib.check(lib.rtg_fit_targets_f32(plan.handle, ptr(x), B, ptr(out), stream_handle()))
+
+    def composed():
+        torch.index_select(x, 1, pick, out=rows)
+        _lib.check(lib.rtg_rescale_motion_f32(red.handle, ptr(rows), B, d3, ptr(resc), stream_handle()))
+        torch.index_select(resc, 1, spread, out=comp)
+
+    fused()
+    composed()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(comp.view(torch.int32), out.view(torch.int32)))
+    f_us, c_us = [], []
+    for _ in range(rounds):   # interleaved: both see the same box state
+        f_us.append(time_events(fused, reps=30, warm=3) * 1e3)
+        c_us.append(time_events(composed, reps=10, warm=2) * 1e3)
+    nbytes = 12 * (Js + Jt)
+    return {"B": B, "J_s": Js, "J_t": Jt, "K": K, "bytes_per_frame": nbytes, "fused_us": f_us, "composed_us": c_us,
+            "fused_TBs": [B * nbytes / (u * 1e-6) / 1e12 for u in f_us], "composed_equals_fused_bits": same,
+            "every_fused_faster": max(f_us) < min(c_us)}
+
+
+def fit_targets_traffic(B=262144):
+    """Three launches of rtg_fit_targets_f32 and three 256 MiB device copies of known bytes, nothing else: for a
+    counter run of its own (FETCH_SIZE or WRITE_SIZE, one per run).  The copy calibrates the counters' unit."""
+    from rtg.runtime import ptr, stream_handle
+    lib = _lib.lib()
+    plan, _, _, _, _, x = _fit_targets_setup(B)
+    out = torch.empty((B, plan.num_target_joints, 3), device="cuda")
+    src, dst = torch.randn(1 << 26, device="cuda"), torch.empty(1 << 26, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(3):
+        dst.copy_(src)
+    for _ in range(3):
+        _lib.check(lib.rtg_fit_targets_f32(plan.handle, ptr(x), B, ptr(out), stream_handle()))
+    torch.cuda.synchronize()
+    return {"B": B, "copy_bytes_each_way": 4 << 26, "read_bytes_per_launch": 12 * plan.num_source_joints * B,
+            "write_bytes_per_launch": 12 * plan.num_target_joints * B}
 
 
 if __name__ == "__main__":
