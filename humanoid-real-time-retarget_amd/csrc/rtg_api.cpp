@@ -357,11 +357,11 @@ int fill_fit_apart(const char *fn, const rtg_fit_apart &a, DofFitApartArgs &Z, b
 
 // rtg_dof_fit_f32 (R == nullptr), rtg_dof_fit_root_f32 (R: the root block), rtg_dof_fit_orient_f32 (O too: the
 // orientation block, rot_joint its K host-side joint indices), rtg_dof_fit_prior_f32 (H too: the posture prior and
-// the projection) and rtg_dof_fit_apart_f32 (apart too: the keep-apart spheres and the floor): one checked path,
-// seven kernels
+// the projection), rtg_dof_fit_apart_f32 (apart too: the keep-apart spheres and the floor) and rtg_dof_fit_robust_f32
+// (U too: the frame weights and the robust scale, inv_d2 filled here): one checked path, eleven kernels
 int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const DofFitRootArgs *R, rtg_stream_t stream,
                 DofFitOriArgs *O = nullptr, const int32_t *rot_joint = nullptr, const DofFitPriorArgs *H = nullptr,
-                const rtg_fit_apart *apart = nullptr)
+                const rtg_fit_apart *apart = nullptr, DofFitRobustArgs *U = nullptr)
 {
     // everything that needs no handle first
     if (A.B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)A.B);
@@ -412,6 +412,13 @@ int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const
             return fail(RTG_ERR_INVALID_ARGUMENT, "%s: prior_weight given without prior", fn);
         if (!H->prior && !H->flags) H = nullptr;   // neither term nor projection: rtg_dof_fit_orient_f32 itself
     }
+    if (U) {
+        if (!std::isfinite(U->robust_scale) || U->robust_scale < 0.0f)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: robust_scale=%g must be finite and not negative", fn,
+                        (double)U->robust_scale);
+        U->inv_d2 = U->robust_scale > 0.0f ? (float)(1.0 / ((double)U->robust_scale * (double)U->robust_scale)) : 0.0f;
+        if (!U->frame_weight && U->robust_scale == 0.0f) U = nullptr;   // neither: rtg_dof_fit_apart_f32 itself
+    }
     DofFitApartArgs Z{};
     bool keep_apart = false;   // no sphere, or neither a pair nor a floor: rtg_dof_fit_prior_f32 itself
     if (apart) RTG_CHECK(fill_fit_apart(fn, *apart, Z, keep_apart));
@@ -438,7 +445,12 @@ int run_dof_fit(const char *fn, rtg_dof_model_t m, int clip, DofFitArgs A, const
         if (!A.loss && !root_out) return RTG_OK;
         H = nullptr;   // no angles: nothing to hold or to project, and neither pointer is dereferenced
     }
-    if (keep_apart)
+    if (U)   // always the prior family's tiles, with no prior where none is given
+        RTG_TRY(launch_dof_fit_robust(m->topo->view(), m->view(), clip != 0, A, *R, *O, H ? *H : DofFitPriorArgs{}, Z,
+                                      keep_apart, *U, as_stream(stream)),
+                keep_apart ? (O->K > 0 ? "k_dof_fit_orient_apart_robust" : "k_dof_fit_apart_robust")
+                           : (O->K > 0 ? "k_dof_fit_orient_robust" : "k_dof_fit_robust"));
+    else if (keep_apart)
         RTG_TRY(launch_dof_fit_apart(m->topo->view(), m->view(), clip != 0, A, *R, *O, H ? *H : DofFitPriorArgs{}, Z,
                                      as_stream(stream)),
                 O->K > 0 ? "k_dof_fit_orient_apart" : "k_dof_fit_apart");
@@ -771,6 +783,24 @@ int rtg_dof_fit_apart_f32(rtg_dof_model_t m, const float *target_pos, const floa
     DofFitOriArgs O{target_rot, rot_weight, K, {}};
     const DofFitPriorArgs H{prior, prior_weight, flags};
     return run_dof_fit("rtg_dof_fit_apart_f32", m, clip, A, &R, stream, &O, rot_joint, &H, apart);
+}
+
+int rtg_dof_fit_robust_f32(rtg_dof_model_t m, const float *target_pos, const float *weight, const int32_t *rot_joint,
+                           const float *target_rot, const float *rot_weight, int32_t K, const float *prior,
+                           const float *prior_weight, int32_t flags, const float *root_rot, const float *root_t,
+                           const float *dof_in, int64_t B, int clip, int32_t fit_root, int32_t iters, float lr,
+                           float lr_root_t, float lr_root_rot, float beta1, float beta2, float eps, int32_t step0, float *mo,
+                           float *v, float *root_state, float *dof_out, float *root_rot_out, float *root_t_out, float *loss,
+                           float *grad, float *grad_root, const rtg_fit_apart *apart, const float *frame_weight,
+                           float robust_scale, rtg_stream_t stream)
+{
+    const DofFitArgs A{target_pos, weight, root_rot, root_t, dof_in, B, iters, step0, lr, beta1, beta2, eps,
+                       mo, v, dof_out, loss, grad};
+    const DofFitRootArgs R{fit_root, lr_root_t, lr_root_rot, root_state, root_rot_out, root_t_out, grad_root};
+    DofFitOriArgs O{target_rot, rot_weight, K, {}};
+    const DofFitPriorArgs H{prior, prior_weight, flags};
+    DofFitRobustArgs U{frame_weight, robust_scale, 0.0f};
+    return run_dof_fit("rtg_dof_fit_robust_f32", m, clip, A, &R, stream, &O, rot_joint, &H, apart, &U);
 }
 
 // ---------------------------------------------------------------- SkeletonState.retarget_to

@@ -58,6 +58,16 @@
 // Spheres, pairs and plane travel in the launch arguments (host-checked) and are read with constant indices only, on
 // their way into small LDS tables; the per-joint table holds the bit mask of a joint's spheres.
 //
+// k_dof_fit_robust_group and its three siblings (rtg_dof_fit_robust_f32) are the four PRIOR-family tiles with
+// per-frame keypoint weights and a robust keypoint loss (ROBUST): the keypoint term is sum_j e_fj rho(s) over the
+// keypoints with frame_weight[f,j] != 0, e_fj = weight[j] frame_weight[f,j], s = |P_j - T_fj|^2, rho(s) = s or, with
+// robust_scale = delta > 0, the pseudo-Huber 2 s / (sqrt(1 + s / delta^2) + 1); its adjoint 2 e_fj d / sqrt(1 + s /
+// delta^2) enters where 2 w_j d enters, fit_residual's in-place row.  The tile loads frame_weight's rows with its
+// other global loads and keeps e_fj in one more image of [F J] floats (RobustImages), a skipped keypoint as a bit
+// pattern no product has; fit_residual reads its weight there and *selects*: a skipped keypoint adds nothing to the
+// loss and leaves a +0 row whatever its target row holds.  Robust on or off is wave-uniform; 1 / delta^2 comes
+// rounded from the host's double.  Nothing else of the tile changes.
+//
 // LDS images of a tile: FitImages below (every image starts 16-byte aligned).
 // 33-link Hu, F = 16 (10 steps): 29.3 KiB; a 64-joint chain, F = 8, 64 steps: 43.9 KiB (the largest: gsteps <= J).
 // With the root image and the two more step sizes per Adam step: 31.1 KiB (still 5 tiles per CU) and 45.1 KiB.
@@ -70,6 +80,7 @@
 // bytes, each image padded to 16.  Hu with S = 16, Pn = 32: 3,072 + 256 + 64 + 144 + 256 = 3,792 B, a tile of
 // 37,808 B (K = 8: 40,128 B) -- under the 40,960 B that keep four tiles on a CU; the chain: 2,368 B, 50,784 B
 // (K = 8: 52,320 B).
+// ROBUST adds RobustImages behind those: 4 F J bytes (Hu 2,112 B, the chain 2,048 B: its largest tile 54,368 B).
 //
 // Arithmetic: as in rtg_fk_grad.hip no operation order is owed to a reference (explicit fmaf, the device sincosf,
 // -ffp-contract=fast); the forward here is the float32 restatement of rtg_dof_fk_f32's, not its bit-exact f64 sincos.
@@ -175,6 +186,22 @@ struct ApartImages {
     }
 };
 
+// ROBUST: the effective keypoint weights, carved behind the tile's other images (base: the first float after them), so
+// the tiles without the term do not see it and their code stays what it was
+struct RobustImages {
+    float *W;        // [F J] e_fj = weight[j] frame_weight[f,j]; kSkipKeypoint's bits where frame_weight[f,j] == 0
+    size_t floats;
+    __host__ __device__ RobustImages(float *base, int J, int F)
+    {
+        LdsCarve c(base);
+        W = c.take<float>((size_t)F * J);
+        floats = c.floats;
+    }
+};
+// a signalling NaN: a float32 product is never that (the multiplier quiets every NaN it passes on), so the image needs
+// no second word for "skip this keypoint"
+constexpr int kSkipKeypoint = 0x7F800001;
+
 // G_0 = q / max(|q|, 1e-9) of a fitted root rotation: no sign flip (q and -q are one rotation and the iterate stays
 // continuous); NaN passes
 RTG_DEV f4v root_unit(f4v q)
@@ -223,20 +250,46 @@ RTG_DEV void fit_forward(const FitImages &I, int J, int gsteps, bool live, int f
 // positions -> residual adjoints in place (the root's row stays where the root's adjoint is not taken; ROOT: it is
 // dL/dt's own term); returns this lane's part of the frame's loss, its joints in index order
 // APART (S spheres): the row then takes the centre gradients g_s of the link's spheres, in sphere order
-template <int F, bool ROOT, bool APART = false>
-RTG_DEV float fit_residual(const FitImages &I, int J, bool live, int fr, int sub, const ApartImages *X = nullptr, int S = 0)
+// ROBUST: the weight is e_fj from the W image, a keypoint marked there is skipped by selects (nothing to the loss, a +0
+// row before the spheres' part, whatever d holds), and with `robust` (wave-uniform) the term is e rho(s) with the
+// adjoint 2 e d / sqrt(1 + s inv_d2)
+template <int F, bool ROOT, bool APART = false, bool ROBUST = false>
+RTG_DEV float fit_residual(const FitImages &I, int J, bool live, int fr, int sub, const ApartImages *X = nullptr, int S = 0,
+                           const float *W = nullptr, bool robust = false, float inv_d2 = 0.0f)
 {
     using G = Grp<F>;
     float acc = 0.0f;
     if (live) {
         for (int j = sub; j < J; j += G::L) {
-            const float w = I.tab[j].w;
+            const float w = ROBUST ? W[fr * J + j] : I.tab[j].w;
             float *pj = I.P + 3 * (fr * J + j);
             const float *tj = I.T + 3 * (fr * J + j);
             const V d{pj[0] - tj[0], pj[1] - tj[1], pj[2] - tj[2]};
+            float w2 = 2.0f * w;
+            if constexpr (ROBUST) {
+                const bool on = __float_as_int(w) != kSkipKeypoint;
+                const float s = fdot3(d, d);
+                float rho = s;
+                if (robust) {
+                    const float q = __builtin_sqrtf(__builtin_fmaf(s, inv_d2, 1.0f));
+                    rho = (2.0f * s) / (q + 1.0f);
+                    w2 = w2 / q;
+                }
+                acc = on ? __builtin_fmaf(w, rho, acc) : acc;
+                if (ROOT || j != 0) {
+                    V r{on ? w2 * d.x : 0.0f, on ? w2 * d.y : 0.0f, on ? w2 * d.z : 0.0f};
+                    if constexpr (APART) {
+                        for (int m = X->jtab[j] & 0xFFFF; m; m &= m - 1) {
+                            const float *g = X->C + 3 * (fr * S + __builtin_ctz(m));
+                            r.x += g[0]; r.y += g[1]; r.z += g[2];
+                        }
+                    }
+                    pj[0] = r.x; pj[1] = r.y; pj[2] = r.z;
+                }
+                continue;
+            }
             acc = __builtin_fmaf(w, fdot3(d, d), acc);
             if (ROOT || j != 0) {
-                const float w2 = 2.0f * w;
                 if constexpr (APART) {
                     V r{w2 * d.x, w2 * d.y, w2 * d.z};
                     for (int m = X->jtab[j] & 0xFFFF; m; m &= m - 1) {
@@ -533,11 +586,14 @@ using OriRows = LaneRows<f4v, 2>;           // a tile's target rotations: F K <=
 // arguments, not looked at otherwise); ORI: with orientation targets (O: theirs, likewise); PRIOR: with the posture
 // prior and the projection onto the limits (H: theirs, likewise; what H asks for is wave-uniform, like fit_root);
 // APART: with keep-apart spheres and a floor (Z: theirs, likewise; S >= 1 and a pair or the plane: the host sees to it)
-template <bool CLIP, int F, bool ROOT, bool ORI, bool PRIOR = false, bool APART = false>
+// ROBUST: with per-frame keypoint weights and the robust keypoint loss (U: theirs, likewise; robust on or off is
+// wave-uniform)
+template <bool CLIP, int F, bool ROOT, bool ORI, bool PRIOR = false, bool APART = false, bool ROBUST = false>
 RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs &A, const DofFitRootArgs &R,
                           const DofFitOriArgs &O, const DofFitPriorArgs &H = DofFitPriorArgs{},
-                          const DofFitApartArgs &Z = DofFitApartArgs{})
+                          const DofFitApartArgs &Z = DofFitApartArgs{}, const DofFitRobustArgs &U = DofFitRobustArgs{})
 {
+    static_assert(PRIOR || !ROBUST, "the robust tile is the prior tile's");
     static_assert(ROOT || !ORI, "the oriented tile carries the root image");
     static_assert(ROOT || !PRIOR, "the prior tile carries the root image");
     static_assert(PRIOR || !APART, "the keep-apart tile is the prior tile's");
@@ -551,6 +607,8 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
     const FitImages I(ft_lds, J, F, T.gsteps, ROOT, ORI ? K : -1, PRIOR);
     const int NSPH = APART ? Z.S : 0;
     [[maybe_unused]] const ApartImages X(APART ? ft_lds + I.floats : nullptr, J, F, NSPH, APART ? Z.Pn : 0);
+    [[maybe_unused]] const RobustImages Y(ROBUST ? ft_lds + I.floats + (APART ? X.floats : 0) : nullptr, J, F);
+    [[maybe_unused]] const bool robust = ROBUST && U.robust_scale > 0.0f;
     float *lossp = I.lossp, *adam = I.adam;
     const int fit_root = ROOT ? R.fit_root : 0;
     const bool prior = PRIOR && H.prior != nullptr, project = PRIOR && (H.flags & RTG_FIT_PROJECT) != 0;
@@ -573,6 +631,10 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
     }
     OriRows tr = {};
     if (ORI && K > 0) tr.load(O.target_rot + f0 * K * 4, nfr * K);
+    ScalarRows<F> fw = {};   // ROBUST: the tile's frame_weight rows (no pointer: ones)
+    if constexpr (ROBUST) {
+        if (U.frame_weight) fw.load(U.frame_weight + f0 * J, nfr * J);
+    }
     const float *trow = A.target_pos + f0 * J * 3;
     PosRows<F> tp;
     tp.load(trow, npos);
@@ -644,6 +706,18 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
             X.jtab[j] = m;
         }
     }
+    if constexpr (ROBUST) {   // e_fj = weight[j] frame_weight[f,j] from the table's weights (other lanes wrote them)
+        wave_sync();
+        const float rJ = item_rcp(J);
+        const bool given = U.frame_weight != nullptr;
+        lane_items<Grp<F>::NR>([&](int k, int i) {
+            if (i < nfr * J) {
+                const float c = given ? fw.v[k] : 1.0f;
+                const float e = I.tab[item_split(i, rJ, J).j].w * c;
+                Y.W[i] = c == 0.0f ? __int_as_float(kSkipKeypoint) : e;
+            }
+        });
+    }
     if (ROOT) {   // the root image; fit_forward presets the root's rows from it
         if (lane < nfr) I.Rq[lane] = rr;
         if (lane < 3 * nfr) I.Rt[lane] = rt;
@@ -688,11 +762,11 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
         fit_forward<CLIP, F, ROOT>(I, J, T.gsteps, live, fr, sub, fit_root);
         if constexpr (APART) {
             (void)apart_pass<F>(I, X, Z, J, live, fr, sub);
-            (void)fit_residual<F, ROOT, true>(I, J, live, fr, sub, &X, NSPH);
+            (void)fit_residual<F, ROOT, true, ROBUST>(I, J, live, fr, sub, &X, NSPH, Y.W, robust, U.inv_d2);
             fit_reverse<CLIP, false, F, ROOT, ORI, PRIOR, true>(I, J, K, T.gsteps, live, fr, sub, S, fit_root, prior, project,
                                                                 &X, NSPH);
         } else {
-            (void)fit_residual<F, ROOT>(I, J, live, fr, sub);
+            (void)fit_residual<F, ROOT, false, ROBUST>(I, J, live, fr, sub, nullptr, 0, Y.W, robust, U.inv_d2);
             fit_reverse<CLIP, false, F, ROOT, ORI, PRIOR>(I, J, K, T.gsteps, live, fr, sub, S, fit_root, prior, project);
         }
     }
@@ -713,7 +787,7 @@ RTG_DEV void dof_fit_tile(const TopoView &T, const DofView &D, const DofFitArgs 
     fit_forward<CLIP, F, ROOT>(I, J, T.gsteps, live, fr, sub, fit_root);
     float apart = 0.0f;
     if constexpr (APART) apart = apart_pass<F>(I, X, Z, J, live, fr, sub);
-    float part = fit_residual<F, ROOT, APART>(I, J, live, fr, sub, &X, NSPH);
+    float part = fit_residual<F, ROOT, APART, ROBUST>(I, J, live, fr, sub, &X, NSPH, Y.W, robust, U.inv_d2);
     if constexpr (PRIOR) {
         if (prior) part += prior_loss_part<F>(I, nd, live, fr, sub);
     }
@@ -783,6 +857,37 @@ __global__ __launch_bounds__(64) void k_dof_fit_orient_apart_group(TopoView T, D
                                                                    DofFitOriArgs O, DofFitPriorArgs H, DofFitApartArgs Z)
 {
     dof_fit_tile<CLIP, F, true, true, true, true>(T, D, A, R, O, H, Z);
+}
+
+// rtg_dof_fit_robust_f32 (with frame weights or a robust scale): the four tiles above with ROBUST
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_robust_group(TopoView T, DofView D, DofFitArgs A, DofFitRootArgs R,
+                                                             DofFitPriorArgs H, DofFitRobustArgs U)
+{
+    dof_fit_tile<CLIP, F, true, false, true, false, true>(T, D, A, R, DofFitOriArgs{}, H, DofFitApartArgs{}, U);
+}
+
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_orient_robust_group(TopoView T, DofView D, DofFitArgs A, DofFitRootArgs R,
+                                                                    DofFitOriArgs O, DofFitPriorArgs H, DofFitRobustArgs U)
+{
+    dof_fit_tile<CLIP, F, true, true, true, false, true>(T, D, A, R, O, H, DofFitApartArgs{}, U);
+}
+
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_apart_robust_group(TopoView T, DofView D, DofFitArgs A, DofFitRootArgs R,
+                                                                   DofFitPriorArgs H, DofFitApartArgs Z, DofFitRobustArgs U)
+{
+    dof_fit_tile<CLIP, F, true, false, true, true, true>(T, D, A, R, DofFitOriArgs{}, H, Z, U);
+}
+
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64) void k_dof_fit_orient_apart_robust_group(TopoView T, DofView D, DofFitArgs A,
+                                                                          DofFitRootArgs R, DofFitOriArgs O,
+                                                                          DofFitPriorArgs H, DofFitApartArgs Z,
+                                                                          DofFitRobustArgs U)
+{
+    dof_fit_tile<CLIP, F, true, true, true, true, true>(T, D, A, R, O, H, Z, U);
 }
 
 template <bool ROOT>
@@ -894,6 +999,46 @@ hipError_t launch_dof_fit_apart(const TopoView &T, const DofView &D, bool clip, 
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitMaxLdsBytes);
             if (attr == hipSuccess) hipLaunchKernelGGL((k_dof_fit_apart_group<cl(), f()>), dim3(grid_for(A.B, F)), dim3(64), lds, s, T, D, A, R, H, Z);
         }
+    }, clip);
+    if (attr != hipSuccess) return attr;
+    return hipGetLastError();
+}
+
+// apart: Z holds a term (launch_dof_fit_apart's checks then); without one Z is not looked at
+hipError_t launch_dof_fit_robust(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
+                                 const DofFitRootArgs &R, const DofFitOriArgs &O, const DofFitPriorArgs &H,
+                                 const DofFitApartArgs &Z, bool apart, const DofFitRobustArgs &U, hipStream_t s)
+{
+    if (!T.gsched || O.K < 0 || O.K > RTG_FIT_MAX_ROT_LINKS) return hipErrorInvalidValue;
+    if ((H.flags & RTG_FIT_PROJECT) && (!D.lower || !D.upper)) return hipErrorInvalidValue;   // the kernel reads them
+    for (int k = 0; k < O.K; ++k)   // the kernel indexes rows with them
+        if (O.joint[k] < 0 || O.joint[k] >= T.J) return hipErrorInvalidValue;
+    if (apart) {
+        if (Z.S < 1 || Z.S > RTG_FIT_MAX_SPHERES || Z.Pn < 0 || Z.Pn > RTG_FIT_MAX_PAIRS) return hipErrorInvalidValue;
+        if (Z.S < 32 && (Z.floor_mask >> Z.S) != 0u) return hipErrorInvalidValue;
+        for (int i = 0; i < Z.S; ++i)   // likewise
+            if (Z.link[i] < 0 || Z.link[i] >= T.J) return hipErrorInvalidValue;
+        for (int p = 0; p < Z.Pn; ++p)
+            if ((Z.pair[p] & 0xFF) >= Z.S || (Z.pair[p] >> 8) < 0 || (Z.pair[p] >> 8) >= Z.S) return hipErrorInvalidValue;
+    }
+    if (!(U.robust_scale >= 0.0f) || !(U.inv_d2 >= 0.0f)) return hipErrorInvalidValue;
+    const int F = T.gF;
+    const size_t lds = sizeof(float) * (FitImages(nullptr, T.J, F, T.gsteps, true, O.K > 0 ? O.K : -1, true).floats +
+                                        (apart ? ApartImages(nullptr, T.J, F, Z.S, Z.Pn).floats : 0) +
+                                        RobustImages(nullptr, T.J, F).floats);
+    if (lds > kFitMaxLdsBytes) return hipErrorInvalidValue;
+    hipError_t attr = hipSuccess;
+    const dim3 grid(grid_for(A.B, F));
+    auto go = [&](auto kern, auto... args) {
+        attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)kFitMaxLdsBytes);
+        if (attr == hipSuccess) hipLaunchKernelGGL(kern, grid, dim3(64), lds, s, T, D, A, R, args...);
+    };
+    group_dispatch(F, [&](auto f, auto cl) {
+        if (apart && O.K > 0) go(&k_dof_fit_orient_apart_robust_group<cl(), f()>, O, H, Z, U);
+        else if (apart) go(&k_dof_fit_apart_robust_group<cl(), f()>, H, Z, U);
+        else if (O.K > 0) go(&k_dof_fit_orient_robust_group<cl(), f()>, O, H, U);
+        else go(&k_dof_fit_robust_group<cl(), f()>, H, U);
     }, clip);
     if (attr != hipSuccess) return attr;
     return hipGetLastError();

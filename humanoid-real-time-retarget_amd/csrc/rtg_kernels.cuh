@@ -149,6 +149,16 @@ struct DofFitApartArgs {
 hipError_t launch_dof_fit_apart(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
                                 const DofFitRootArgs &R, const DofFitOriArgs &O, const DofFitPriorArgs &H,
                                 const DofFitApartArgs &Z, hipStream_t s);
+// rtg_dof_fit_robust_f32: the prior or the keep-apart launch (`apart`: Z holds a term) with per-frame keypoint weights
+// and the robust keypoint loss.  frame_weight (B,J) or nullptr: ones; robust_scale 0: the quadratic loss, else delta
+// (finite, > 0) with inv_d2 = (float)(1 / delta^2), formed in double by the host
+struct DofFitRobustArgs {
+    const float *frame_weight;
+    float robust_scale, inv_d2;
+};
+hipError_t launch_dof_fit_robust(const TopoView &T, const DofView &D, bool clip, const DofFitArgs &A,
+                                 const DofFitRootArgs &R, const DofFitOriArgs &O, const DofFitPriorArgs &H,
+                                 const DofFitApartArgs &Z, bool apart, const DofFitRobustArgs &U, hipStream_t s);
 // SkeletonState.retarget_to (poselib skeleton3d.py:742-889) as one launch, rtg_retarget_to.hip.
 // The host tables of a mapping of K (source joint, target joint) pairs: S_red / T_red are the trees with only the
 // mapped joints kept, each hung from its nearest kept ancestor (drop_nodes_by_names, :226-259).

@@ -66,6 +66,11 @@ class HuForwardModel(BaseForwardModel):
             raise ValueError("project_angles needs DOF limits with one entry per DOF")
         return dict(prior=prior_angles, prior_weight=prior_weight, project=bool(project_angles))
 
+    @staticmethod
+    def _robust(keypoint_confidence, robust_scale):
+        """fit_pose's ``keypoint_confidence`` (L, J) and ``robust_scale`` as ops.pose_fit's keywords."""
+        return dict(frame_weight=keypoint_confidence, robust_scale=robust_scale)
+
     def forward_kinematics(self, motion_joint_angles, motion_root_translation, motion_root_rotation, clip_angles):
         """(L, J-1, 1) angles, (L, 3) root translation, (L, 1, 4) root rotation -> ((L, J, 4), (L, J, 3))."""
         if clip_angles and not self._model.has_limits:
@@ -78,7 +83,8 @@ class HuForwardModel(BaseForwardModel):
     def fit_keypoints(self, target_positions, motion_root_translation, motion_root_rotation,
                       motion_joint_angles=None, weight=None, iters=32, lr=0.02, betas=(0.9, 0.999), eps=1e-8,
                       clip_angles=True, state=None, return_grad=False, target_rotations=None, rotation_links=None,
-                      rotation_weight=None, prior_angles=None, prior_weight=None, project_angles=False, apart=None):
+                      rotation_weight=None, prior_angles=None, prior_weight=None, project_angles=False, apart=None,
+                      keypoint_confidence=None, robust_scale=None):
         """Not in the reference, which only ships the forward model of its optimisation-based converter: the loop that
         model is for -- a keypoint loss sum_j weight[j] |g_pos[:, j] - target_positions[:, j]|^2 minimised over the
         joint angles with torch.optim.Adam -- as one launch (ops.dof_fit).  (L, J, 3) targets, (L, 3) root translation,
@@ -89,7 +95,8 @@ class HuForwardModel(BaseForwardModel):
         ``target_rotations`` (L, K, 4), ``rotation_links`` (K node names or joint indices, K <= 8) and
         ``rotation_weight`` (K,) add fit_pose's orientation term for those links, the root given.  ``prior_angles``,
         ``prior_weight``, ``project_angles``: fit_pose's posture prior and projection.  ``apart``: its keep-apart spheres
-        and floor."""
+        and floor.  ``keypoint_confidence`` (L, J), ``robust_scale``: its per-frame keypoint weights and robust keypoint
+        loss."""
         if clip_angles and not self._model.has_limits:
             raise ValueError("clip_angles needs DOF limits with one entry per DOF")
         dev = home_device(target_positions, motion_root_translation, motion_root_rotation)
@@ -98,7 +105,8 @@ class HuForwardModel(BaseForwardModel):
                           dof0=motion_joint_angles, weight=weight, iters=iters, lr=lr, betas=betas, eps=eps,
                           clip=bool(clip_angles), state=state, return_grad=return_grad,
                           **self._rotation_targets(target_rotations, rotation_links, rotation_weight),
-                          **self._posture_prior(prior_angles, prior_weight, project_angles), apart=apart)
+                          **self._posture_prior(prior_angles, prior_weight, project_angles), apart=apart,
+                          **self._robust(keypoint_confidence, robust_scale))
         dof, loss, new_state = res[:3]
         shaped = lambda a: a.reshape(tuple(loss.shape) + (n, 1)).to(dev)
         out = (shaped(dof), loss.to(dev), new_state)
@@ -108,7 +116,7 @@ class HuForwardModel(BaseForwardModel):
                  weight=None, iters=32, lr=0.02, lr_root_t=None, lr_root_rot=None, fit_root_t=True, fit_root_rot=True,
                  betas=(0.9, 0.999), eps=1e-8, clip_angles=True, state=None, return_grad=False, target_rotations=None,
                  rotation_links=None, rotation_weight=None, prior_angles=None, prior_weight=None, project_angles=False,
-                 apart=None):
+                 apart=None, keypoint_confidence=None, robust_scale=None):
         """fit_keypoints with the floating base among the parameters (ops.pose_fit): mocap keypoints come from a body
         of other proportions, and with the root pinned the legs cannot reach them.  (L, J, 3) targets, (L, 3) root
         translation and (L, 1, 4) root rotation to start from (or given, where fit_root_t / fit_root_rot is False),
@@ -128,7 +136,13 @@ class HuForwardModel(BaseForwardModel):
         node name or joint index): spheres riding on links, pairs of them pushed apart where they overlap, and spheres
         held above a ground plane -- what keeps a wrist out of the torso, one gripper out of the other and an ankle
         above the floor when the keypoints come from a body of other proportions.  No default radii are shipped: the
-        repository holds Hu's skeleton only, no collision geometry; measure them or take them from the robot's URDF."""
+        repository holds Hu's skeleton only, no collision geometry; measure them or take them from the robot's URDF.
+        ``keypoint_confidence`` (L, J): per-frame, per-keypoint weights multiplied into ``weight`` -- a vision
+        tracker's confidences, a foot held hard in the frames where it is in contact.  A keypoint whose confidence is 0
+        is skipped in that frame: its target row may hold anything, NaN included (an occluded marker, a dropped frame).
+        ``robust_scale`` (metres, None: off) makes the keypoint term the pseudo-Huber loss of that scale: quadratic
+        for residuals well below it, linear far out, so one glitched or swapped marker no longer drags its limb and,
+        through the floating base, the body.  Both act inside the one launch (ops.pose_fit)."""
         if clip_angles and not self._model.has_limits:
             raise ValueError("clip_angles needs DOF limits with one entry per DOF")
         dev = home_device(target_positions, motion_root_translation, motion_root_rotation)
@@ -138,7 +152,8 @@ class HuForwardModel(BaseForwardModel):
                            lr_root_rot=lr_root_rot, fit_root_t=fit_root_t, fit_root_rot=fit_root_rot, betas=betas,
                            eps=eps, clip=bool(clip_angles), state=state, return_grad=return_grad,
                            **self._rotation_targets(target_rotations, rotation_links, rotation_weight),
-                           **self._posture_prior(prior_angles, prior_weight, project_angles), apart=apart)
+                           **self._posture_prior(prior_angles, prior_weight, project_angles), apart=apart,
+                           **self._robust(keypoint_confidence, robust_scale))
         lead = tuple(res.loss.shape)
         shaped = lambda a: a.reshape(lead + (n, 1)).to(dev)
         out = (shaped(res.dof), res.root_t.to(dev), res.root_rot.reshape(lead + (1, 4)).to(dev), res.loss.to(dev),
@@ -155,8 +170,11 @@ class HuForwardModel(BaseForwardModel):
         root that carries the optimiser state.  ``smooth_weight == 0`` passes no prior: that is one fit_pose of
         rounds * iters steps, bit for bit.  Only the angles are smoothed: the root can be regularised through
         weight[0] and an orientation target on link 0.  The other keywords are fit_pose's (``prior_angles`` and
-        ``state`` are this method's to set; ``prior_weight`` scales smooth_weight per DOF; ``apart`` goes to every
-        round).  Returns what fit_pose returns, after the last round."""
+        ``state`` are this method's to set; ``prior_weight`` scales smooth_weight per DOF; ``apart``,
+        ``keypoint_confidence`` and ``robust_scale`` go to every round).  A frame whose keypoints are all masked
+        (``keypoint_confidence`` 0) has only the prior left: with ``smooth_weight > 0`` it is held by its neighbours'
+        mean, round after round, so a gap of dropped frames is filled in from its ends.  Returns what fit_pose
+        returns, after the last round."""
         for k in ("prior_angles", "state"):
             if k in fit_pose_keywords:
                 raise ValueError(f"fit_motion sets {k} itself")
@@ -209,15 +227,30 @@ class HuForwardModel(BaseForwardModel):
 
     def fit_mocap(self, source_tree, joint_mapping, source_positions, motion_root_rotation=None,
                   motion_joint_angles=None, smooth_weight=0.0, dir=None, root_scale=None, root_offset=None, weight=None,
-                  **fit_keywords):
+                  source_confidence=None, valid=None, **fit_keywords):
         """Mocap keypoints to a pose in two launches: keypoint_targets, then fit_pose -- or fit_motion when
         ``smooth_weight > 0`` -- on them.  The root translation starts at the root's target row, the root rotation at
         ``motion_root_rotation`` (L, 1, 4) or the identity, the angles at ``motion_joint_angles`` or fit_pose's
         default; the plan's weight masks the unmapped links (multiplied into ``weight`` (J,) when given).  The other
-        keywords are fit_pose's (fit_motion's with smoothing).  Returns what they return, plus the targets."""
+        keywords are fit_pose's (fit_motion's with smoothing).
+        ``source_confidence`` (L, J_s) and ``valid`` (L,) bool -- what ``ingest_vtrdyn`` returns next to the positions
+        -- become fit_pose's ``keypoint_confidence`` (multiplied into one passed among the keywords): a link takes the
+        confidence of the source joint mapped to it, an unmapped link 0, and a frame that is not valid has its whole
+        row zeroed, so nothing of a dropped frame reaches the fit (its rows may be zeros or NaN).  A dropped frame is
+        then fitted to nothing: it keeps its start unless ``smooth_weight > 0``, where the neighbours' mean holds it
+        and a gap is filled in from its ends.  Where the root's own row is masked and not finite, the root translation
+        starts at zero.  Returns what they return, plus the targets."""
         targets, w = self.keypoint_targets(source_tree, joint_mapping, source_positions, dir, root_scale, root_offset)
         lead = tuple(targets.shape[:-2])
         t0 = targets[..., 0, :].clone()
+        conf = self._mocap_confidence(source_tree, joint_mapping, lead, source_confidence, valid, targets.device)
+        if conf is not None:
+            given = fit_keywords.pop("keypoint_confidence", None)
+            if given is not None:
+                conf = conf * torch.as_tensor(given, dtype=torch.float32).to(conf.device)
+            fit_keywords["keypoint_confidence"] = conf
+            lost = (conf[..., 0] == 0) & ~torch.isfinite(t0).all(dim=-1)
+            t0[lost] = 0.0
         q0 = motion_root_rotation
         if q0 is None:
             q0 = torch.zeros(lead + (1, 4), device=targets.device, dtype=torch.float32)
@@ -230,6 +263,32 @@ class HuForwardModel(BaseForwardModel):
         else:
             res = self.fit_pose(targets, t0, q0, motion_joint_angles, weight=w, **fit_keywords)
         return tuple(res) + (targets,)
+
+    def _mocap_confidence(self, source_tree, joint_mapping, lead, source_confidence, valid, device):
+        """fit_mocap's per-frame weights (L, J) from the source's: source_confidence (L, J_s) gathered through the
+        joint mapping (unmapped links 0; None: ones on every link), a frame with ``valid`` False zeroed.  None when
+        neither is given."""
+        if source_confidence is None and valid is None:
+            return None
+        J = self.num_joints
+        if source_confidence is None:
+            conf = torch.ones(lead + (J,), device=device, dtype=torch.float32)
+        else:
+            src_names, names = list(source_tree.node_names), list(self.node_names)
+            sc = torch.as_tensor(source_confidence)
+            if tuple(sc.shape) != lead + (len(src_names),):
+                raise ValueError(f"source_confidence {tuple(sc.shape)} must be {lead + (len(src_names),)}")
+            sc = sc.to(device=device, dtype=torch.float32)
+            conf = torch.zeros(lead + (J,), device=device, dtype=torch.float32)
+            sj = [src_names.index(a) for a in joint_mapping]
+            tj = [names.index(b) for b in joint_mapping.values()]
+            conf[..., tj] = sc[..., sj]
+        if valid is not None:
+            ok = torch.as_tensor(valid)
+            if tuple(ok.shape) != lead:
+                raise ValueError(f"valid {tuple(ok.shape)} must be {lead}")
+            conf = conf * (ok.to(device) != 0).to(torch.float32).unsqueeze(-1)
+        return conf
 
     def _clip_angles(self, motion_joint_angles):
         """:27-33, forward value: (clamp(a, lo, hi) - a) + a, elementwise on the angles' device."""

@@ -141,6 +141,10 @@ SIGNATURES = {
     "rtg_dof_fit_apart_f32": (c_int, [c_void_p] * 6 + [c_int32] + [c_void_p] * 2 + [c_int32] + [c_void_p] * 3 +
                                      [c_int64, c_int, c_int32, c_int32] + [c_float] * 6 + [c_int32] + [c_void_p] * 9 +
                                      [POINTER(FitApart), c_void_p]),
+    # (the same with (frame_weight, robust_scale) before the stream)
+    "rtg_dof_fit_robust_f32": (c_int, [c_void_p] * 6 + [c_int32] + [c_void_p] * 2 + [c_int32] + [c_void_p] * 3 +
+                                      [c_int64, c_int, c_int32, c_int32] + [c_float] * 6 + [c_int32] + [c_void_p] * 9 +
+                                      [POINTER(FitApart), c_void_p, c_float, c_void_p]),
     "rtg_retarget_plan_create": (c_int, [c_void_p, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int32,
                                          POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float),
                                          POINTER(c_float), c_float, POINTER(c_void_p)]),

@@ -631,6 +631,47 @@ def _apart_input(apart):
     return apart
 
 
+Robust = collections.namedtuple("Robust", "rows scale")   # rows: the (..., J) device tensor or None; scale: a float
+
+
+def _robust_inputs(model, target_pos, frame_weight, robust_scale):
+    """The per-frame keypoint weights and the robust scale of a fit, checked before anything asks for the device:
+    frame_weight (..., J) over the batch shape of target_pos (..., J, 3), real (bool and integer masks are converted);
+    robust_scale None or 0 for the quadratic loss, else a finite positive number of metres.  None when neither is given:
+    the launch without them.  _robust_rows then puts the rows on the device."""
+    import math
+    import numbers
+    lead = tuple(_as_tensor(target_pos).shape[:-2])
+    scale = 0.0 if robust_scale is None else robust_scale
+    if isinstance(scale, torch.Tensor) and scale.numel() == 1:
+        scale = scale.item()
+    if isinstance(scale, bool) or not isinstance(scale, numbers.Real):
+        raise ValueError(f"robust_scale must be a number, got {robust_scale!r}")
+    scale = float(scale)
+    if not math.isfinite(scale) or scale < 0.0:
+        raise ValueError(f"robust_scale must be 0 or a finite positive number, got {robust_scale!r}")
+    rows = None
+    if frame_weight is not None:
+        fw = _as_tensor(frame_weight)
+        if fw.is_complex():
+            raise ValueError(f"frame_weight must be real, got {fw.dtype}")
+        J = model.num_dofs + 1
+        if fw.dim() < 1 or fw.shape[-1] != J or tuple(fw.shape[:-1]) != tuple(lead):
+            raise ValueError(f"frame_weight {tuple(fw.shape)} does not match the batch shape {tuple(lead)} of target_pos "
+                             f"with {J} keypoints")
+        rows = fw.detach()
+    if rows is None and scale == 0.0:
+        return None
+    return Robust(rows, scale)
+
+
+def _robust_rows(robust):
+    """_robust_inputs' result with the rows as a contiguous float32 device tensor (never part of the graph)."""
+    if robust is None or robust.rows is None:
+        return robust
+    return Robust(dev_f32(robust.rows, (robust.rows.shape[-1],), "frame_weight"), robust.scale)
+
+
 def _fit_state(model, d, dof0, iters, state):
     """What dof_fit and pose_fit share around their launches: ``iters`` range-checked; the angles' optimiser state
     ``(m, v, step)`` -- fresh (zeros, 0) for ``state`` None, else the caller's, copied (the launch updates it in
@@ -667,7 +708,7 @@ def _fit_launch(model, clip, tp, w, rr, rt, d, iters=0, lr=0.0, betas=(0.9, 0.99
 def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: int = 32, lr: float = 0.02,
             betas=(0.9, 0.999), eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False,
             rot_joints=None, target_rot=None, rot_weight=None, prior=None, prior_weight=None, project: bool = False,
-            apart=None):
+            apart=None, frame_weight=None, robust_scale=None):
     """Fit the joint angles of a DofModel to target keypoints: ``iters`` steps of torch.optim.Adam (no weight decay, no
     amsgrad) on L_f = sum_j weight[j] |P_j(a_f) - target_pos[f, j]|^2, P the positions of dof_forward_kinematics --
     forward model, loss, gradient and optimiser in ONE launch (rtg_dof_fit_f32).
@@ -685,14 +726,17 @@ def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: 
     (rtg_dof_fit_orient_f32 with fit_root = 0; an oriented root then only adds to the loss).
     ``prior``, ``prior_weight``, ``project``: pose_fit's posture prior and projection (rtg_dof_fit_prior_f32 with
     fit_root = 0).  ``apart``: pose_fit's keep-apart spheres and floor (ops.apart; rtg_dof_fit_apart_f32 with
-    fit_root = 0).
+    fit_root = 0).  ``frame_weight``, ``robust_scale``: pose_fit's per-frame keypoint weights and robust keypoint
+    loss (rtg_dof_fit_robust_f32 with fit_root = 0).
     Raises RtgError without a GPU: there is no CPU fallback."""
+    rob = _robust_inputs(model, target_pos, frame_weight, robust_scale)
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof0, weight)
     iters, m, v, step, as_dof0 = _fit_state(model, d, dof0, iters, state)
     orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
     pri = _prior_inputs(model, d, prior, prior_weight, project)
     apart = _apart_input(apart)
-    if orient is None and pri is None and apart is None:
+    rob = _robust_rows(rob)
+    if orient is None and pri is None and apart is None and rob is None:
         out, loss, grad = _fit_launch(model, clip, tp, w, rr, rt, d.detach(), iters, lr, betas, eps, step, m, v,
                                       want_dof=True, want_grad=bool(return_grad))
     else:   # the root is given: its state is neither read nor written, the buffer only pairs with m and v
@@ -700,23 +744,34 @@ def dof_fit(model, target_pos, root_rot, root_t, dof0=None, weight=None, iters: 
         out, _, _, loss, grad, _ = _pose_launch(model, clip, 0, tp, w, rr, rt, d.detach(), iters, lr, 0.0, 0.0, betas, eps,
                                                 step, m if m.numel() else rs, v if v.numel() else rs, rs,
                                                 want_iterate=True, want_grad=bool(return_grad), orient=orient, prior=pri,
-                                                apart=apart)
+                                                apart=apart, robust=rob)
     res = (as_dof0(out), loss, (m, v, step + iters))
     return res + (as_dof0(grad),) if return_grad else res
 
 
 def keypoint_loss(model, dof, target_pos, root_rot, root_t, weight=None, clip: bool = False, rot_joints=None,
-                  target_rot=None, rot_weight=None, prior=None, prior_weight=None, apart=None):
+                  target_rot=None, rot_weight=None, prior=None, prior_weight=None, apart=None, frame_weight=None,
+                  robust_scale=None):
     """The per-frame keypoint loss L_f = sum_j weight[j] |P_j(dof_f) - target_pos[f, j]|^2 of dof_fit, (...), as the
     evaluate-only launch of rtg_dof_fit_f32.  Differentiable in ``dof`` (only): the launch computes the gradient
     along with the loss, and backward scales its rows by the upstream cotangent -- for callers who keep their own
     optimiser.  Under no_grad, or when dof does not require grad, it is the plain launch without the gradient.
     ``rot_joints``, ``target_rot``, ``rot_weight``: dof_fit's orientation targets.  ``prior``, ``prior_weight``: its
     posture term sum_d prior_weight[d] (dof_d - prior_d)^2 (the loss is not differentiable in them).  ``apart``: its
-    keep-apart spheres and floor (ops.apart; not differentiable in the spec either)."""
+    keep-apart spheres and floor (ops.apart; not differentiable in the spec either).  ``frame_weight``,
+    ``robust_scale``: its per-frame keypoint weights and robust keypoint loss (the gradient is the robust loss's; the
+    frame weights are not differentiable)."""
+    rob = _robust_inputs(model, target_pos, frame_weight, robust_scale)
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof, weight)
     orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
     pri = _prior_inputs(model, d, prior, prior_weight, False)
+    rob = _robust_rows(rob)
+    if rob is not None:
+        apart = _apart_input(apart)
+        if torch.is_grad_enabled() and d.requires_grad:
+            return _RobustPoseLoss.apply(model, bool(clip), 0, d, rr.detach(), rt.detach(), tp, w, orient, pri, apart, rob)
+        return _pose_launch(model, clip, 0, tp, w, rr, rt, d.detach(), orient=orient, prior=pri, apart=apart,
+                            robust=rob)[3]
     if _apart_input(apart) is not None:
         if torch.is_grad_enabled() and d.requires_grad:
             return _ApartPoseLoss.apply(model, bool(clip), 0, d, rr.detach(), rt.detach(), tp, w, orient, pri, apart)
@@ -756,9 +811,10 @@ PoseFitGrad = collections.namedtuple("PoseFitGrad", "dof root_rot root_t loss st
 
 def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_root_t=0.0, lr_root_rot=0.0,
                  betas=(0.9, 0.999), eps=1e-8, step0=0, m=None, v=None, root_state=None, want_iterate=False,
-                 want_loss=True, want_grad=False, orient=None, prior=None, apart=None):
+                 want_loss=True, want_grad=False, orient=None, prior=None, apart=None, robust=None):
     """rtg_dof_fit_root_f32 -- with ``orient`` (an Orient) rtg_dof_fit_orient_f32, with ``prior`` (a Prior)
-    rtg_dof_fit_prior_f32, with ``apart`` (an Apart) rtg_dof_fit_apart_f32 -- on prepared tensors; m, v, root_state are updated in place.  Returns (dof_out, root_rot_out, root_t_out, loss, grad, grad_root), None where
+    rtg_dof_fit_prior_f32, with ``apart`` (an Apart) rtg_dof_fit_apart_f32, with ``robust`` (a Robust)
+    rtg_dof_fit_robust_f32 -- on prepared tensors; m, v, root_state are updated in place.  Returns (dof_out, root_rot_out, root_t_out, loss, grad, grad_root), None where
     not asked for."""
     lead = tuple(tp.shape[:-2])
     B = int(torch.Size(lead).numel())
@@ -769,7 +825,14 @@ def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_ro
     tail = (ptr(rr), ptr(rt), ptr(d), B, int(bool(clip)), int(fit_root), int(iters), float(lr), float(lr_root_t),
             float(lr_root_rot), float(betas[0]), float(betas[1]), float(eps), int(step0), ptr(m), ptr(v), ptr(root_state),
             ptr(out), ptr(rr_out), ptr(rt_out), ptr(loss), ptr(grad), ptr(grad_root), stream_handle())
-    if apart is not None:
+    if robust is not None:
+        o = orient if orient is not None else Orient(None, 0, None, None)
+        h = prior if prior is not None else Prior(None, None, 0)
+        check(lib().rtg_dof_fit_robust_f32(model.handle, ptr(tp), ptr(w), o.joints, ptr(o.target_rot), ptr(o.rot_weight),
+                                           o.K, ptr(h.rows), ptr(h.weight), h.flags, *tail[:-1],
+                                           ctypes.byref(apart.spec) if apart is not None else None, ptr(robust.rows),
+                                           robust.scale, tail[-1]))
+    elif apart is not None:
         o = orient if orient is not None else Orient(None, 0, None, None)
         h = prior if prior is not None else Prior(None, None, 0)
         check(lib().rtg_dof_fit_apart_f32(model.handle, ptr(tp), ptr(w), o.joints, ptr(o.target_rot), ptr(o.rot_weight),
@@ -790,7 +853,8 @@ def _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, iters=0, lr=0.0, lr_ro
 def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iters: int = 32, lr: float = 0.02,
              lr_root_t=None, lr_root_rot=None, fit_root_t: bool = True, fit_root_rot: bool = True, betas=(0.9, 0.999),
              eps: float = 1e-8, clip: bool = False, state=None, return_grad: bool = False, rot_joints=None,
-             target_rot=None, rot_weight=None, prior=None, prior_weight=None, project: bool = False, apart=None):
+             target_rot=None, rot_weight=None, prior=None, prior_weight=None, project: bool = False, apart=None,
+             frame_weight=None, robust_scale=None):
     """dof_fit with the floating base among the parameters: the joint angles and -- where ``fit_root_t`` /
     ``fit_root_rot`` -- the root translation and rotation of every frame, fitted to target keypoints by ``iters`` steps
     of torch.optim.Adam with three parameter groups (``lr`` for the angles, ``lr_root_t``, ``lr_root_rot``; None: ``lr``)
@@ -826,10 +890,20 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
     out of the torso, one gripper out of the other and an ankle above the ground when the keypoints come from a body of
     other proportions.  The term acts on the iterate inside the launch; None is the launch without it, bit for bit.
 
+    Per-frame keypoint weights and a robust keypoint loss (rtg_dof_fit_robust_f32, still one launch): ``frame_weight``
+    (..., J) over target_pos's batch shape multiplies ``weight`` per frame and keypoint -- a tracker's confidences, a
+    foot held hard while it is in contact -- and a keypoint whose frame weight is 0 is skipped altogether: it adds
+    nothing and pulls nothing whatever its target row holds, NaN included (a dropped frame is a row of zeros).
+    ``robust_scale`` = delta > 0 (metres) replaces |d|^2 in the keypoint term by the pseudo-Huber
+    2 |d|^2 / (sqrt(1 + |d|^2 / delta^2) + 1): quadratic for |d| << delta, 2 delta |d| far out, so a glitched marker
+    half a metre off no longer drags its limb.  The other terms are unchanged.  The frame weights are used as given
+    (not checked, negative ones included).  With neither given this is the launch without them, bit for bit.
+
     Returns the named tuple ``(dof, root_rot, root_t, loss, state)`` -- the iterate after the last step (root_rot
     (..., 4), unit where fitted), the per-frame loss there -- plus ``grad`` (dof's shape) and ``grad_root`` (..., 7) =
     {dL/dt, dL/dq} there when ``return_grad``.  ``iters=0`` only evaluates.  Raises RtgError without a GPU: there is
     no CPU fallback."""
+    rob = _robust_inputs(model, target_pos, frame_weight, robust_scale)
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot0, root_t0, dof0, weight)
     iters, m, v, step, as_dof0 = _fit_state(model, d, dof0, iters, None if state is None else (*state[:2], state[3]))
     lead = tuple(tp.shape[:-2])
@@ -840,12 +914,13 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
     fit_root = (FIT_ROOT_T if fit_root_t else 0) | (FIT_ROOT_ROT if fit_root_rot else 0)
     orient = _orient_inputs(model, lead, rot_joints, target_rot, rot_weight)
     pri = _prior_inputs(model, d, prior, prior_weight, project)
+    rob = _robust_rows(rob)
     # (a one-joint model has no angle moments: their arguments only say that a state is given)
     out, rr_out, rt_out, loss, grad, grad_root = _pose_launch(
         model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach(), iters, lr,
         lr if lr_root_t is None else lr_root_t, lr if lr_root_rot is None else lr_root_rot, betas, eps, step,
         m if m.numel() else rs, v if v.numel() else rs, rs, want_iterate=True, want_grad=bool(return_grad),
-        orient=orient, prior=pri, apart=_apart_input(apart))
+        orient=orient, prior=pri, apart=_apart_input(apart), robust=rob)
     new_state = (m, v, rs, step + iters)
     if return_grad:
         return PoseFitGrad(as_dof0(out), rr_out, rt_out, loss, new_state, as_dof0(grad), grad_root)
@@ -853,7 +928,8 @@ def pose_fit(model, target_pos, root_rot0, root_t0, dof0=None, weight=None, iter
 
 
 def pose_loss(model, dof, root_rot, root_t, target_pos, weight=None, clip: bool = False, normalize_root: bool = True,
-              rot_joints=None, target_rot=None, rot_weight=None, prior=None, prior_weight=None, apart=None):
+              rot_joints=None, target_rot=None, rot_weight=None, prior=None, prior_weight=None, apart=None,
+              frame_weight=None, robust_scale=None):
     """The per-frame keypoint loss of pose_fit, (...), as the evaluate-only launch of rtg_dof_fit_root_f32,
     differentiable in ``dof``, ``root_rot`` and ``root_t``: the launch computes the three gradients along with the
     loss and backward scales their rows by the upstream cotangent -- for callers who keep their own optimiser.
@@ -861,11 +937,20 @@ def pose_loss(model, dof, root_rot, root_t, target_pos, weight=None, clip: bool 
     rotation); False: as given, like keypoint_loss.  Under no_grad, or when no input requires grad, it is the plain
     launch without the gradients.  ``rot_joints``, ``target_rot``, ``rot_weight``: pose_fit's orientation targets;
     ``prior``, ``prior_weight``: its posture term; ``apart``: its keep-apart spheres and floor (ops.apart) (the loss is
-    not differentiable in any of them)."""
+    not differentiable in any of them); ``frame_weight``, ``robust_scale``: its per-frame keypoint weights and robust
+    keypoint loss (the gradients are the robust loss's; the frame weights are not differentiable)."""
+    rob = _robust_inputs(model, target_pos, frame_weight, robust_scale)
     tp, d, rr, rt, w = _fit_inputs(model, target_pos, root_rot, root_t, dof, weight)
     fit_root = FIT_ROOT_ROT if normalize_root else 0   # no step is taken: the mask only selects the model
     orient = _orient_inputs(model, tuple(tp.shape[:-2]), rot_joints, target_rot, rot_weight)
     pri = _prior_inputs(model, d, prior, prior_weight, False)
+    rob = _robust_rows(rob)
+    if rob is not None:
+        apart = _apart_input(apart)
+        if torch.is_grad_enabled() and (d.requires_grad or rr.requires_grad or rt.requires_grad):
+            return _RobustPoseLoss.apply(model, bool(clip), fit_root, d, rr, rt, tp, w, orient, pri, apart, rob)
+        return _pose_launch(model, clip, fit_root, tp, w, rr.detach(), rt.detach(), d.detach(), orient=orient, prior=pri,
+                            apart=apart, robust=rob)[3]
     if _apart_input(apart) is not None:
         if torch.is_grad_enabled() and (d.requires_grad or rr.requires_grad or rt.requires_grad):
             return _ApartPoseLoss.apply(model, bool(clip), fit_root, d, rr, rt, tp, w, orient, pri, apart)
@@ -947,6 +1032,24 @@ class _ApartPoseLoss(torch.autograd.Function):
         grad, grad_root = ctx.saved_tensors
         c = grad_loss.unsqueeze(-1)
         return None, None, None, grad * c, grad_root[..., 3:] * c, grad_root[..., :3] * c, None, None, None, None, None
+
+
+class _RobustPoseLoss(torch.autograd.Function):
+    """_ApartPoseLoss (orient, prior and apart may be None) with the per-frame weights and the robust keypoint loss:
+    the evaluate-only launch of rtg_dof_fit_robust_f32."""
+    @staticmethod
+    def forward(ctx, model, clip, fit_root, d, rr, rt, tp, w, orient, prior, apart, robust):
+        _, _, _, loss, grad, grad_root = _pose_launch(model, clip, fit_root, tp, w, rr, rt, d, want_grad=True,
+                                                      orient=orient, prior=prior, apart=apart, robust=robust)
+        ctx.save_for_backward(grad, grad_root)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        grad, grad_root = ctx.saved_tensors
+        c = grad_loss.unsqueeze(-1)
+        return (None, None, None, grad * c, grad_root[..., 3:] * c, grad_root[..., :3] * c) + (None,) * 6
 
 
 def rescale_motion(topo: Topology, motion, dir=None):

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*); rtg_dof_fit_f32,
-                                  rtg_dof_fit_root_f32, rtg_dof_fit_orient_f32, rtg_dof_fit_prior_f32 and rtg_dof_fit_apart_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
+                                  rtg_dof_fit_root_f32, rtg_dof_fit_orient_f32, rtg_dof_fit_prior_f32, rtg_dof_fit_apart_f32 and rtg_dof_fit_robust_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
                                6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
                                5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
                                4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
@@ -365,6 +365,48 @@ int rtg_dof_fit_apart_f32(rtg_dof_model_t model, const float *target_pos, const 
                           float eps, int32_t step0, float *m, float *v, float *root_state, float *dof_out,
                           float *root_rot_out, float *root_t_out, float *loss, float *grad, float *grad_root,
                           const rtg_fit_apart *apart, rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * rtg_dof_fit_apart_f32 with per-frame keypoint weights and a robust keypoint loss (a new symbol under ABI 7).  Every
+ * other term assumes the keypoints are good; mocap drops frames, occludes markers and glitches.  Per frame f, with
+ * e_fj = weight[j] frame_weight[f,j], d = P_j - target_pos[f,j], s = |d|^2, the keypoint term becomes
+ *     sum over the j with frame_weight[f,j] != 0 of  e_fj rho(s),
+ *     rho(s) = s                                  robust_scale == 0 (the quadratic loss of the other entry points)
+ *     rho(s) = 2 s / (sqrt(1 + s / delta^2) + 1)  delta = robust_scale > 0
+ * -- the pseudo-Huber kernel 2 delta^2 (sqrt(1 + s / delta^2) - 1) in the form that does not cancel for small s: s to
+ * first order, 2 delta |d| far out, so one marker half a metre off pulls like one delta off does.  Its adjoint
+ * dL/dP_j = 2 e_fj d / sqrt(1 + s / delta^2) enters where 2 weight[j] d does.  1 / delta^2 is formed in double and
+ * rounded to float32 once; s / delta^2 is s times that.  The kernel applies to the keypoint term only: the
+ * orientation, prior, keep-apart and floor terms are rtg_dof_fit_apart_f32's.
+ *   frame_weight: (B,J) device memory, or NULL = all 1.  A keypoint with frame_weight[f,j] == 0 (either zero) is
+ *   SKIPPED -- a select, not a multiplication: it adds exactly nothing to the loss and its residual row is exactly +0
+ *   whatever its target row holds, NaN and inf included.  (weight[j] == 0 is still a multiplication, as in every
+ *   other entry point.)  The values are device data and are not checked: a negative frame weight is used as given.
+ *   Only a weight[j] or frame_weight[f,j] whose bits are 0x7F800001 is undefined: the tile marks a skipped keypoint
+ *   with that signalling NaN, which no float32 product has.
+ *   robust_scale: 0, or a finite positive number of metres.
+ * Guarantees: (a) frame_weight == NULL with robust_scale == 0 gives rtg_dof_fit_apart_f32's outputs bit for bit (the
+ * call runs its kernels).  (b) frame_weight all ones behaves exactly like NULL: with robust_scale == 0 and finite
+ * inputs every output equals (a)'s as a number, with robust_scale > 0 ones and NULL agree bit for bit.  (c) A masked
+ * keypoint contributes nothing whatever its target row holds; a frame with every keypoint masked has a keypoint loss
+ * of exactly 0 and its DOFs get the exact +-0 of rtg_dof_fit_f32's guarantee; a DOF whose strict subtree has no
+ * non-zero e_fj in frame f, and no oriented link or sphere below it, gets +-0 in that frame and from a zero state
+ * keeps its bits; a masked root row leaves a fitted root translation its bits when nothing else pulls.  (d) A frame
+ * depends on its own rows alone, runs are bit-identical, and n launches of one step that carry (m, v, root_state,
+ * step0) equal one launch of n steps.  (e) A NaN or inf in frame_weight[f,.] makes frame f's loss and gradient
+ * non-finite exactly where the float32 restatement of the formulas above does, and no other frame's.
+ * Errors: rtg_dof_fit_apart_f32's, and robust_scale negative or not finite -> RTG_ERR_INVALID_ARGUMENT; all before
+ * any device work.  B == 0 is a no-op.  For a one-joint model frame_weight still applies to the root's row.
+ * ---------------------------------------------------------------------- */
+int rtg_dof_fit_robust_f32(rtg_dof_model_t model, const float *target_pos, const float *weight,
+                           const int32_t *rot_joint, const float *target_rot, const float *rot_weight, int32_t K,
+                           const float *prior, const float *prior_weight, int32_t flags, const float *root_rot,
+                           const float *root_t, const float *dof_in, int64_t B, int clip, int32_t fit_root,
+                           int32_t iters, float lr, float lr_root_t, float lr_root_rot, float beta1, float beta2,
+                           float eps, int32_t step0, float *m, float *v, float *root_state, float *dof_out,
+                           float *root_rot_out, float *root_t_out, float *loss, float *grad, float *grad_root,
+                           const rtg_fit_apart *apart, const float *frame_weight, float robust_scale,
+                           rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * SkeletonState.retarget_to (poselib skeleton3d.py:742-889): the generic skeleton-to-skeleton retarget, rotations

@@ -37,6 +37,13 @@
   apart_fit -- the pose fit with keep-apart spheres and a floor (rtg_dof_fit_apart_f32, a prior and the projection on)
               per iteration with S = 8 and S = 16 spheres, against rtg_dof_fit_prior_f32 of this build and of
               RTG_PARENT_LIB, and the composed iteration with the same penalty
+  robust_fit -- the pose fit with per-frame keypoint weights and the robust keypoint loss (rtg_dof_fit_robust_f32, a
+              prior and the projection on) per iteration: neither given (the prior launch's kernel, against this
+              build's and RTG_PARENT_LIB's rtg_dof_fit_prior_f32), frame weights, the robust scale, both -- without
+              spheres, with 8 spheres, and at K = 8 with 16 spheres / 32 pairs against rtg_dof_fit_apart_f32 there --
+              and the composed iteration with the same masking and kernel
+  robust_fit_traffic -- a few launches of rtg_dof_fit_robust_f32 (frame weights and the scale on) and nothing else, for
+              a counter run of its own
   prior_fit_traffic -- a few launches of rtg_dof_fit_prior_f32 and nothing else, for a counter run of its own
   motion_sample -- the fused motion sampler (rtg_motion_sample_f32, C ABI, preallocated outputs; Hu v5, 64 clips x 4096
               frames, N=262144 queries; uniform / random / frame-instant queries, with global outputs + velocities
@@ -963,6 +970,121 @@ def _apart_lds(J, F, S, Pn):
     """rtg_dof_fit.hip ApartImages: bytes of the keep-apart images of a tile (each image padded to 16 bytes)."""
     pad = lambda n: (n + 3) // 4 * 4
     return 4 * (pad(3 * F * S) + 4 * S + pad(S) + pad(J) + 2 * pad(Pn))
+
+
+def _robust_fit_call(M, tgt, joints, trot, prior, flags, spec, fw, delta, rr0, rt0, start, B, iters, mask, outs, symbol=None):
+    """rtg_dof_fit_robust_f32; ``symbol`` "apart": rtg_dof_fit_apart_f32 with the same arguments (fw None, delta 0)."""
+    import ctypes
+    from rtg.runtime import ptr, stream_handle
+    K = len(joints)
+    jarr = (ctypes.c_int32 * max(K, 1))(*joints)
+    head = (M.handle, ptr(tgt), None, jarr if K else None, ptr(trot) if K else None, None, K, ptr(prior), None, flags, ptr(rr0),
+            ptr(rt0), ptr(start), B, 1, mask, iters, 0.02, 0.02, 0.02, 0.9, 0.999, 1e-8, 0, None, None, None,
+            *(ptr(o) for o in outs), None if spec is None else ctypes.byref(spec.spec))
+    if symbol == "apart":
+        f, args = _lib.lib().rtg_dof_fit_apart_f32, head + (stream_handle(),)
+    else:
+        f, args = _lib.lib().rtg_dof_fit_robust_f32, head + (ptr(fw), float(delta), stream_handle())
+    _lib.check(f(*args))
+    return lambda: f(*args)
+
+
+def _frame_weights(B, J=33):
+    """Confidences in 0.2-1 with one keypoint in ten masked: any finite rows cost the same."""
+    gen = torch.Generator(device="cuda").manual_seed(31)
+    fw = 0.2 + 0.8 * torch.rand((B, J), device="cuda", generator=gen)
+    fw[torch.rand((B, J), device="cuda", generator=gen) < 0.1] = 0.0
+    return fw.contiguous()
+
+
+ROBUST_DELTA = 0.05
+
+
+def robust_fit(B=262144, rounds=4, iters=32):
+    """The pose fit with per-frame keypoint weights and the robust keypoint loss (rtg_dof_fit_robust_f32, fit_root = 3, a
+    prior and the projection, C ABI, preallocated outputs, 33-link Hu, clip on, no state) per iteration; interleaved
+    rounds.  `null`: neither given -- rtg_dof_fit_prior_f32's kernel, timed next to that symbol of this build and of the
+    build RTG_PARENT_LIB names (when set); `fw`, `delta`, `both`: without spheres, with S = 8, and at K = 8 links with
+    S = 16 / 32 pairs, there against rtg_dof_fit_apart_f32 (whose kernels are the parent's instruction for
+    instruction); and the composed iteration with the same masking and kernel in torch."""
+    M, tgt, rr0, rt0, start, g_rot = _pose_fit_setup(B, want_rot=True)
+    new = lambda *s: torch.empty(s, device="cuda")
+    outs = (new(B, 32), new(B, 4), new(B, 3), new(B), None, None)
+    prior = _prior_rows(start)
+    fw = _frame_weights(B)
+    specs = {S: _apart_spec(M, S) for S in (8, 16)}
+    j8 = ORIENT_LINKS[8]
+    trot = g_rot[:, list(j8)].contiguous()
+    tail = (rr0, rt0, start, B, iters, 3, outs)
+    calls = {"prior_project_us_per_iteration": _prior_fit_call(M, tgt, (), None, prior, 1, rr0, rt0, start, B, iters, 3, outs),
+             "null_us_per_iteration": _robust_fit_call(M, tgt, (), None, prior, 1, None, None, 0.0, *tail)}
+    for name, spec, ori in (("", None, ((), None)), ("s8_", specs[8], ((), None)), ("k8_s16_", specs[16], (j8, trot))):
+        if spec is not None:
+            calls[f"{name}apart_us_per_iteration"] = _robust_fit_call(M, tgt, *ori, prior, 1, spec, None, 0.0, *tail, symbol="apart")
+        calls[f"{name}fw_us_per_iteration"] = _robust_fit_call(M, tgt, *ori, prior, 1, spec, fw, 0.0, *tail)
+        calls[f"{name}delta_us_per_iteration"] = _robust_fit_call(M, tgt, *ori, prior, 1, spec, None, ROBUST_DELTA, *tail)
+        calls[f"{name}both_us_per_iteration"] = _robust_fit_call(M, tgt, *ori, prior, 1, spec, fw, ROBUST_DELTA, *tail)
+    parent = os.environ.get("RTG_PARENT_LIB")
+    if parent:
+        calls["parent_prior_project_us_per_iteration"] = _other_build_pose_fit(parent, tgt, rr0, rt0, start, B, iters, outs,
+                                                                               prior, 1)
+    a, q, t = (x.clone().requires_grad_(True) for x in (start, rr0, rt0))
+    opt = torch.optim.Adam([dict(params=[a]), dict(params=[t]), dict(params=[q])], lr=0.02, fused=True)
+    hu = __import__("importlib").import_module("retarget.robot_config.Hu")
+    lo, hi = (torch.as_tensor(np.asarray(x), dtype=torch.float32, device="cuda") for x in (hu.Hu_DOF_LOWER, hu.Hu_DOF_UPPER))
+    on = fw != 0
+    tgt0 = torch.where(on[..., None], tgt, torch.zeros_like(tgt))
+    inv = 1.0 / ROBUST_DELTA ** 2
+
+    def composed():
+        opt.zero_grad(set_to_none=True)
+        gp = ops.dof_forward_kinematics(M, a, torch.nn.functional.normalize(q, dim=-1, eps=1e-9), t, clip=True)[1]
+        ss = (gp - tgt0).square().sum(-1)
+        rho = 2.0 * ss / (torch.sqrt(1.0 + ss * inv) + 1.0)
+        (torch.where(on, fw * rho, torch.zeros_like(rho)).sum() + (a - prior).square().sum()).backward()
+        opt.step()
+        with torch.no_grad():
+            q.copy_(torch.nn.functional.normalize(q, dim=-1, eps=1e-9))
+            a.clamp_(lo, hi)
+
+    res = {k: [] for k in calls}
+    res["composed_both_us_per_iteration"] = []
+    for _ in range(rounds):   # interleaved: all see the same box state
+        for k, call in calls.items():
+            res[k].append(time_events(call, reps=5, warm=1) * 1e3 / iters)
+        res["composed_both_us_per_iteration"].append(time_events(composed, reps=10, warm=2) * 1e3)
+    base, k8 = 34016, 36336
+    lds = {"robust_image_bytes": 4 * 16 * 33, "prior": base, "prior_robust": base + 2112,
+           "s8": base + _apart_lds(33, 16, 8, int(specs[8].spec.Pn)),
+           "s8_robust": base + _apart_lds(33, 16, 8, int(specs[8].spec.Pn)) + 2112,
+           "k8_s16": k8 + _apart_lds(33, 16, 16, int(specs[16].spec.Pn)),
+           "k8_s16_robust": k8 + _apart_lds(33, 16, 16, int(specs[16].spec.Pn)) + 2112}
+    return {"B": B, "J": 33, "iters": iters, "delta": ROBUST_DELTA, **res, "parent_lib": parent, "links": list(j8),
+            "pairs": {str(S): int(s.spec.Pn) for S, s in specs.items()}, "dynamic_lds_bytes_per_tile": lds,
+            "algorithmic_bytes_per_frame": {"read_added_by_frame_weight": 4 * 33}}
+
+
+def robust_fit_traffic(B=262144, iters=32):
+    """A few launches of rtg_dof_fit_robust_f32 (fit_root = 3, a prior and the projection, frame weights and the scale,
+    K = 0, no spheres, no state) and nothing else, for a counter run of its own (FETCH_SIZE or WRITE_SIZE, one per run)
+    against prior_fit's algorithmic bytes plus 4 J per frame read."""
+    M, tgt, rr0, rt0, start = _pose_fit_setup(B)
+    new = lambda *s: torch.empty(s, device="cuda")
+    outs = (new(B, 32), new(B, 4), new(B, 3), new(B), None, None)
+    prior = _prior_rows(start)
+    fw = _frame_weights(B)
+    src, dst = torch.randn(1 << 26, device="cuda"), torch.empty(1 << 26, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(3):   # known bytes: the counters' unit
+        dst.copy_(src)
+    call = _robust_fit_call(M, tgt, (), None, prior, 1, None, fw, ROBUST_DELTA, rr0, rt0, start, B, iters, 3, outs)
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    J = 33
+    return {"B": B, "copy_bytes_each_way": 4 << 26,
+            "algorithmic_bytes_per_frame": {"read": J * 12 + (J - 1) * 4 + 28 + (J - 1) * 4 + J * 4, "written": (J - 1) * 4 + 4 + 28},
+            "launches": "3 x 256 MiB copy, 4 x iters=%d with frame weights, the scale, a prior and the projection" % iters}
 
 
 def motion_sample(N=262144, rounds=4, clips=64, frames=4096):
