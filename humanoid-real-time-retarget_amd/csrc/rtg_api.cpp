@@ -7,7 +7,8 @@
 // Device resources live in the owner types below (DevBuf, PinnedWord, Event): a handle struct holds owners, so a
 // constructor that fails part-way just returns and `delete handle` is the whole destructor.  Argument checks whose
 // text agrees up to the function's name are written once (check_tree, check_layout, check_overlap, parse_seq, ...).
-// Every message here is pinned by tests/api_message_cases.py: a new entry point adds its cases there.
+// Every message here is pinned by tests/api_message_cases.py: a new entry point adds its cases there
+// (rtg_dof_motion_sample_f32's are written out in tests/test_dof_motion_host.py and tests/test_gpu_dof_motion.py).
 #include <immintrin.h>
 #include <hip/hip_runtime.h>
 
@@ -1123,6 +1124,78 @@ int rtg_motion_sample_f32(rtg_topology_t topo, rtg_motion_lib_t lib, const float
                                  (flags & RTG_MOTION_NORMALIZE) != 0, global, (flags & RTG_MOTION_STATE) != 0, A,
                                  as_stream(stream)),
             "k_motion_sample");
+    return RTG_OK;
+}
+
+int rtg_dof_motion_sample_f32(rtg_dof_model_t m, rtg_motion_lib_t lib, const float *dof, const float *root_rot,
+                              const float *root_t, const int32_t *clip, const float *time, int64_t N, int flags,
+                              const int32_t *key_links, int32_t K, float *dof_out, float *dof_vel_out,
+                              float *root_rot_out, float *root_t_out, float *root_vel_out, float *g_rot, float *g_pos,
+                              float *key_pos, rtg_stream_t stream)
+{
+    const char *fn = "rtg_dof_motion_sample_f32";
+    // what does not depend on the handles first: a caller (and a test on a machine without a GPU) sees these reasons
+    // whatever the handles are
+    if (N < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: N=%lld < 0", fn, (long long)N);
+    if (K < 0 || K > RTG_DOF_MOTION_MAX_KEY_LINKS)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: K=%d key links outside 0..%d", fn, K, RTG_DOF_MOTION_MAX_KEY_LINKS);
+    if (flags & ~(RTG_DOF_MOTION_NORMALIZE | RTG_DOF_MOTION_CLIP))
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: unknown flags 0x%x", fn, flags);
+    if (K > 0 && !key_links) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: K=%d with key_links NULL", fn, K);
+    DofMotionArgs A{};
+    for (int k = 0; k < K; ++k) {   // (no model has more than kGroupMaxJ joints here; its own J is checked below)
+        if (key_links[k] < 0 || key_links[k] >= kGroupMaxJ)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: key_links[%d]=%d is outside 0..J-1", fn, k, key_links[k]);
+        A.key[k] = (uint8_t)key_links[k];
+    }
+    if (N > 0) {   // empty buffers have no address to give
+        if (dof_vel_out && !root_vel_out)   // (the other half needs the model: a one-joint model has no dof_vel_out)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both dof_vel_out and root_vel_out or neither", fn);
+        if ((g_rot == nullptr) != (g_pos == nullptr))
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both g_rot and g_pos or neither", fn);
+        if ((K > 0) != (key_pos != nullptr))
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: key_pos goes with K > 0 (K=%d, key_pos %s)", fn, K,
+                        key_pos ? "given" : "NULL");
+        if (!root_rot || !root_t || !clip || !time || !root_rot_out || !root_t_out)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    }
+    if ((reinterpret_cast<uintptr_t>(root_rot) | reinterpret_cast<uintptr_t>(root_rot_out) |
+         reinterpret_cast<uintptr_t>(g_rot)) & 15)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: root_rot / root_rot_out / g_rot not 16-byte aligned", fn);
+    if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL model", fn);
+    if (!lib) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL library", fn);
+    const int J = m->topo->J;
+    if (J > kGroupMaxJ || !m->topo->gsched.get())
+        return fail(RTG_ERR_UNSUPPORTED, "%s: serves models of 1..%d joints (this one has %d)", fn, kGroupMaxJ, J);
+    if ((flags & RTG_DOF_MOTION_CLIP) && !m->has_limits)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: RTG_DOF_MOTION_CLIP requested but the model has no DOF limits", fn);
+    for (int k = 0; k < K; ++k)
+        if (key_links[k] >= J)
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: key_links[%d]=%d is outside 0..%d", fn, k, key_links[k], J - 1);
+    if (N == 0) return RTG_OK;
+    // a one-joint model has no angles: the dof pointers are not looked at
+    if (J > 1 && root_vel_out && !dof_vel_out)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both dof_vel_out and root_vel_out or neither", fn);
+    if (J > 1 && (!dof || !dof_out)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    {   // no output may overlap an input (or another output)
+        const uint64_t Ft = (uint64_t)lib->F_total, n = (uint64_t)N, j = (uint64_t)J, k = (uint64_t)K;
+        const Span in[] = {{dof, Ft * (j - 1) * 4, "dof"}, {root_rot, Ft * 16, "root_rot"}, {root_t, Ft * 12, "root_t"},
+                           {clip, n * 4, "clip"}, {time, n * 4, "time"}};
+        const Span outs[] = {{dof_out, n * (j - 1) * 4, "dof_out"}, {dof_vel_out, n * (j - 1) * 4, "dof_vel_out"},
+                             {root_rot_out, n * 16, "root_rot_out"}, {root_t_out, n * 12, "root_t_out"},
+                             {root_vel_out, n * 24, "root_vel_out"}, {g_rot, n * j * 16, "g_rot"},
+                             {g_pos, n * j * 12, "g_pos"}, {key_pos, n * k * 12, "key_pos"}};
+        RTG_CHECK(check_overlap(fn, outs, 8, in, 5));
+    }
+    A.dof = dof; A.root_rot = root_rot; A.root_t = root_t;
+    A.clip = clip; A.time = time; A.N = N;
+    A.normalize = (flags & RTG_DOF_MOTION_NORMALIZE) != 0;
+    A.K = K;
+    A.dof_out = dof_out; A.dof_vel_out = dof_vel_out; A.root_rot_out = root_rot_out; A.root_t_out = root_t_out;
+    A.root_vel_out = root_vel_out; A.g_rot = g_rot; A.g_pos = g_pos; A.key_pos = key_pos;
+    RTG_TRY(launch_dof_motion_sample(m->topo->view(), m->view(), MotionLibView{lib->clips.get(), lib->C},
+                                     (flags & RTG_DOF_MOTION_CLIP) != 0, A, as_stream(stream)),
+            "k_dof_motion_sample");
     return RTG_OK;
 }
 

@@ -237,41 +237,6 @@ __global__ __launch_bounds__(64, 4) void k_lrot_group(TopoView T, const float *_
 // axis -- and writes them into the tile image where FK's local rotations would be; then FK's compose runs as is.  (A
 // first version built each joint's rotation inside its compose step: the f64 sincos sat on the chain's critical path
 // and the kernel took 128 us against FK's 88, profiles/r06/fk/.)  LDS: FkImages with the per-joint table.
-// qfrom_angle_unit_axis(angle, e_ax) for N joints, element by element the same values: qnormalize's sign flip f
-// (on cos), its |q|^2 in any component order (the zero components add +0 exactly), (n, 1/n) from the table, the two
-// nonzero components' products by 1/n, and the zero components keep the sign of f sin (0 sin, times f, times 1/n > 0).
-// A |q|^2 outside the table (NaN / inf angles) or a subnormal product: the scalar path, one rare-case branch per group.
-template <int N>
-RTG_DEV void joint_rot_n(const float (&angle)[N], const int (&ax)[N], const UnitEnt *tab, Q (&out)[N])
-{
-    double th[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) th[i] = (double)(angle[i] / 2.0f);
-    SC t[N];
-    cr_sincos_n<N>(th, t);
-    bool ok[N], all = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float f = 1.0f - 2.0f * (t[i].c < 0.0f ? 1.0f : 0.0f);
-        const float s = f * t[i].s, c = f * t[i].c;
-        const float n2 = s * s + c * c;
-        uint32_t idx;
-        const bool in = unit_tab_index(n2, idx);
-        const double r = tab[idx].r;
-        const double ps = (double)s * r, pc = (double)c * r;
-        const float qs = (float)ps, z = __builtin_copysignf(0.0f, s);
-        out[i] = Q{ax[i] == 0 ? qs : z, ax[i] == 1 ? qs : z, ax[i] == 2 ? qs : z, (float)pc};
-        ok[i] = in & !((__builtin_fabs(ps) < 0x1p-126) & (ps != 0.0)) & !((__builtin_fabs(pc) < 0x1p-126) & (pc != 0.0));
-        all &= ok[i];
-    }
-    if (__builtin_expect(!all, 0)) {
-#pragma unroll
-        for (int i = 0; i < N; ++i)
-            if (!ok[i])
-                out[i] = qfrom_angle_unit_axis(angle[i], V{ax[i] == 0 ? 1.0f : 0.0f, ax[i] == 1 ? 1.0f : 0.0f,
-                                                           ax[i] == 2 ? 1.0f : 0.0f});
-    }
-}
 template <bool CLIP, int F>
 __global__ __launch_bounds__(64, 4) void k_dof_fk_group(TopoView T, DofView D, const float *__restrict__ dof,
                                                      const float *__restrict__ root_rot,
@@ -296,40 +261,8 @@ __global__ __launch_bounds__(64, 4) void k_dof_fk_group(TopoView T, DofView D, c
     joint_tab_fill<CLIP, false>(D, J, I.ntab);
     root_preset(rot, I.pos, J, nfr, rr, rt);
     wave_sync();
-    // angle i = (frame fr, joint i mod nd + 1): its rotation into record fr J + j
     const float rnd = item_rcp(nd > 0 ? nd : 1);
-    // NW loads' rotations at a time on the N-way leaf math (one rare-case branch per group, the same bits); a lane
-    // past the angles computes a dummy rotation (its j is still a joint) and does not store it
-    auto rotations = [&](auto nw, int k0) {
-        constexpr int NW = decltype(nw)::value;
-        if (k0 * 64 >= nang) return;   // wave-uniform: no lane has an angle in this group
-        float x[NW];
-        int axi[NW], rec[NW];
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const int i = (k0 + w) * 64 + lane;
-            const Item it = item_split(i, rnd, nd);
-            const int fr = it.fr, j = it.j + 1;
-            const f4v t = ntab[j];
-            x[w] = CLIP ? clamp_st(a.v[k0 + w], t.y, t.z) : a.v[k0 + w];
-            // the axis is an exact unit vector: quat_from_angle_axis's normalisation is the identity (round 5)
-            axi[w] = __float_as_int(t.x);
-            rec[w] = i < nang ? fr * J + j : -1;
-        }
-        Q q[NW];
-#if RTG_DOF_UNIT_TAB
-        joint_rot_n<NW>(x, axi, utab, q);
-#else
-        V axv[NW];
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-            axv[w] = V{axi[w] == 0 ? 1.0f : 0.0f, axi[w] == 1 ? 1.0f : 0.0f, axi[w] == 2 ? 1.0f : 0.0f};
-        qfrom_angle_unit_axis_n<NW>(x, axv, q);
-#endif
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-            if (rec[w] >= 0) rot[rec[w]] = v_of(q[w]);
-    };
+    const DofRotations<CLIP, F> rotations{a, ntab, utab, rot, J, nd, nang, lane, rnd};
     constexpr int NW = RTG_DOF_NWAY, NFULL = G::NR - G::NR % NW;
 #pragma unroll
     for (int k = 0; k < NFULL; k += NW) rotations(std::integral_constant<int, NW>{}, k);

@@ -4,7 +4,8 @@
 // LDS images (the layout comment in rtg_fk.hip).  The parts: the LDS carve (LdsCarve: a kernel and its launcher call
 // the same carve function), the row movers (LaneRows as GroupRows: float4 records, and ScalarRows: scalars; PosRows:
 // position rows), the table fills, the root preset, the reverse sweep's child pull, the FK tile itself (FkImages,
-// group_compose, group_store: rtg_fk.hip and rtg_motion_sample.hip), the item split, the Q <-> f4v converters, the
+// group_compose, group_store: rtg_fk.hip and rtg_motion_sample.hip), the joint-angle model's rotations (joint_rot_n,
+// DofRotations: the same two), the item split, the Q <-> f4v converters, the
 // straight-through clamp and the launch dispatch.  The multi-wave tile of rtg_rot_ingest.hip takes only the
 // converters and the item split.
 #pragma once
@@ -256,6 +257,91 @@ RTG_DEV f4v child_pull(f4v a, const f4v *A, float *P, int base, int j, int first
     pj[0] = pb.x; pj[1] = pb.y; pj[2] = pb.z;
     return a;
 }
+
+// ---------------------------------------------------------------------------------------------------- joint angles
+// qfrom_angle_unit_axis(angle, e_ax) for N joints, element by element the same values: qnormalize's sign flip f
+// (on cos), its |q|^2 in any component order (the zero components add +0 exactly), (n, 1/n) from the table, the two
+// nonzero components' products by 1/n, and the zero components keep the sign of f sin (0 sin, times f, times 1/n > 0).
+// A |q|^2 outside the table (NaN / inf angles) or a subnormal product: the scalar path, one rare-case branch per group.
+template <int N>
+RTG_DEV void joint_rot_n(const float (&angle)[N], const int (&ax)[N], const UnitEnt *tab, Q (&out)[N])
+{
+    double th[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) th[i] = (double)(angle[i] / 2.0f);
+    SC t[N];
+    cr_sincos_n<N>(th, t);
+    bool ok[N], all = true;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const float f = 1.0f - 2.0f * (t[i].c < 0.0f ? 1.0f : 0.0f);
+        const float s = f * t[i].s, c = f * t[i].c;
+        const float n2 = s * s + c * c;
+        uint32_t idx;
+        const bool in = unit_tab_index(n2, idx);
+        const double r = tab[idx].r;
+        const double ps = (double)s * r, pc = (double)c * r;
+        const float qs = (float)ps, z = __builtin_copysignf(0.0f, s);
+        out[i] = Q{ax[i] == 0 ? qs : z, ax[i] == 1 ? qs : z, ax[i] == 2 ? qs : z, (float)pc};
+        ok[i] = in & !((__builtin_fabs(ps) < 0x1p-126) & (ps != 0.0)) & !((__builtin_fabs(pc) < 0x1p-126) & (pc != 0.0));
+        all &= ok[i];
+    }
+    if (__builtin_expect(!all, 0)) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (!ok[i])
+                out[i] = qfrom_angle_unit_axis(angle[i], V{ax[i] == 0 ? 1.0f : 0.0f, ax[i] == 1 ? 1.0f : 0.0f,
+                                                           ax[i] == 2 ? 1.0f : 0.0f});
+    }
+}
+// The "rotations" stage of the joint-angle kernels (k_dof_fk_group, k_dof_motion_sample): the tile's angles a (angle
+// i = 64 k + lane, nang of them, nd = J - 1 per frame) through the per-joint table ntab {axis, lower, upper} into the
+// image's local rotations.  angle i = (frame fr, joint i mod nd + 1): its rotation into record fr J + j.
+// operator(): NW loads' rotations at a time on the N-way leaf math (one rare-case branch per group, the same bits); a
+// lane past the angles computes a dummy rotation (its j is still a joint) and does not store it.  The kernel calls it
+// RTG_DOF_NWAY pieces at a time and one by one for the rest (as a closure in the kernel's own body: the device listing
+// of k_dof_fk_group is then what it was with the stage written in place).
+template <bool CLIP, int F>
+struct DofRotations {
+    const ScalarRows<F> &a;
+    const f4v *const &ntab;
+    const UnitEnt *const &utab;
+    f4v *const &rot;
+    const int &J, &nd, &nang, &lane;
+    const float &rnd;   // item_rcp(nd > 0 ? nd : 1)
+    template <typename NWay>
+    RTG_DEV void operator()(NWay, int k0) const
+    {
+        constexpr int NW = NWay::value;
+        if (k0 * 64 >= nang) return;   // wave-uniform: no lane has an angle in this group
+        float x[NW];
+        int axi[NW], rec[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const int i = (k0 + w) * 64 + lane;
+            const Item it = item_split(i, rnd, nd);
+            const int fr = it.fr, j = it.j + 1;
+            const f4v t = ntab[j];
+            x[w] = CLIP ? clamp_st(a.v[k0 + w], t.y, t.z) : a.v[k0 + w];
+            // the axis is an exact unit vector: quat_from_angle_axis's normalisation is the identity (round 5)
+            axi[w] = __float_as_int(t.x);
+            rec[w] = i < nang ? fr * J + j : -1;
+        }
+        Q q[NW];
+#if RTG_DOF_UNIT_TAB
+        joint_rot_n<NW>(x, axi, utab, q);
+#else
+        V axv[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w)
+            axv[w] = V{axi[w] == 0 ? 1.0f : 0.0f, axi[w] == 1 ? 1.0f : 0.0f, axi[w] == 2 ? 1.0f : 0.0f};
+        qfrom_angle_unit_axis_n<NW>(x, axv, q);
+#endif
+#pragma unroll
+        for (int w = 0; w < NW; ++w)
+            if (rec[w] >= 0) rot[rec[w]] = v_of(q[w]);
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------- the FK tile
 // The FK tile's images; dof: the joint-angle model's per-joint {axis, lower, upper} table behind them

@@ -256,6 +256,22 @@ struct MotionSampleArgs {
 // lane groups only (T.gsched); g_rot / g_pos are written iff `global`, as rtg_state_fk_f32 (`state`) or rtg_fk_f32
 hipError_t launch_motion_sample(const TopoView &T, const MotionLibView &L, bool normalize, bool global, bool state,
                                 const MotionSampleArgs &A, hipStream_t s);
+// rtg_dof_motion_sample_f32: a library of joint-angle clips (dof (F_total,J-1), root_rot (F_total,4), root_t
+// (F_total,3)) on the same clip table.  dof_vel_out / root_vel_out, g_rot / g_pos and key_pos nullptr when not asked
+// for; key: the K <= RTG_DOF_MOTION_MAX_KEY_LINKS link indices (host-checked: in 0..J-1), carried in the launch
+// arguments
+struct DofMotionArgs {
+    const float *dof, *root_rot, *root_t;
+    const int32_t *clip;
+    const float *time;
+    int64_t N;
+    int32_t normalize, K;
+    uint8_t key[RTG_DOF_MOTION_MAX_KEY_LINKS];
+    float *dof_out, *dof_vel_out, *root_rot_out, *root_t_out, *root_vel_out, *g_rot, *g_pos, *key_pos;
+};
+// lane groups only (T.gsched); the forward kinematics runs iff g_rot or key_pos is given
+hipError_t launch_dof_motion_sample(const TopoView &T, const DofView &D, const MotionLibView &L, bool clip,
+                                    const DofMotionArgs &A, hipStream_t s);
 hipError_t launch_rescale_motion(const TopoView &T, const float *motion, int64_t B, const float *dir, float *out,
                                  hipStream_t s);
 hipError_t launch_quat_between(const float *v1, const float *v2, int64_t n, float *out, float *ws, hipStream_t s);

@@ -80,6 +80,12 @@ class HuForwardModel(BaseForwardModel):
                                                   motion_root_translation, clip=bool(clip_angles))
         return g_rot.to(dev), g_pos.to(dev)
 
+    def motion_library(self, clips):
+        """``rtg.motion.DofMotionLibrary(self, clips)``: fitted clips -- (angles, root translation, root rotation, fps)
+        tuples, fit_pose's first three results in its order -- packed for sampling at arbitrary times."""
+        from rtg.motion import DofMotionLibrary
+        return DofMotionLibrary(self, clips)
+
     def fit_keypoints(self, target_positions, motion_root_translation, motion_root_rotation,
                       motion_joint_angles=None, weight=None, iters=32, lr=0.02, betas=(0.9, 0.999), eps=1e-8,
                       clip_angles=True, state=None, return_grad=False, target_rotations=None, rotation_links=None,

@@ -72,6 +72,11 @@ MOTION_NORMALIZE = 1
 MOTION_GLOBAL = 2
 MOTION_STATE = 4
 
+# rtg_dof_motion_flags
+DOF_MOTION_NORMALIZE = 1
+DOF_MOTION_CLIP = 2
+DOF_MOTION_MAX_KEY_LINKS = 32   # rtg.h RTG_DOF_MOTION_MAX_KEY_LINKS
+
 
 class RtgError(RuntimeError):
     """A librtg_hip call returned a non-zero rtg_status."""
@@ -167,6 +172,8 @@ SIGNATURES = {
                                       POINTER(c_void_p)]),
     "rtg_motion_lib_destroy": (None, [c_void_p]),
     "rtg_motion_sample_f32": (c_int, [c_void_p] * 5 + [c_int32, c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 6),
+    # (key_links is a host pointer: K int32 values read during the call)
+    "rtg_dof_motion_sample_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int, POINTER(c_int32), c_int32] + [c_void_p] * 9),
     "rtg_solver_create": (c_int, [c_int, POINTER(c_float), POINTER(c_float), POINTER(c_int32), c_int32, c_int,
                                   POINTER(c_void_p)]),
     "rtg_solver_destroy": (c_int, [c_void_p]),

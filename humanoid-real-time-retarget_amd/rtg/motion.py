@@ -3,8 +3,14 @@
 ``MotionLibrary(motions)`` packs ``SkeletonMotion``s of one skeleton tree once into the arrays
 ``ops.motion_sample`` reads (local rotations, root translations, ``[global_velocity | global_angular_velocity]`` rows)
 and ``.sample(clip_ids, times)`` returns the poses between the stored frames: ``quat_slerp`` of the local rotations,
-linear blends of the rest, forward kinematics of the blended pose.  Nothing here touches the device
-at import; there is no CPU fallback.
+linear blends of the rest, forward kinematics of the blended pose.
+
+``DofMotionLibrary(model, clips)`` is the same for clips in the robot's own coordinates -- joint angles, root
+translation, root rotation per frame, what ``HuForwardModel.fit_pose`` / ``fit_motion`` / ``fit_mocap`` return -- and
+``.sample`` returns the reference states a tracking controller or a simulator reads: DOF positions and velocities, the
+root's pose and velocities, link poses or a few key links' positions.
+
+Nothing here touches the device at import; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -17,7 +23,7 @@ import torch
 from . import ops
 from .runtime import MotionLib, require_gpu_rtg
 
-__all__ = ["MotionLibrary", "MotionSample"]
+__all__ = ["MotionLibrary", "MotionSample", "DofMotionLibrary", "DofMotionSample"]
 
 
 @dataclass
@@ -116,3 +122,130 @@ class MotionLibrary:
                                                     vec=self.vec if want_velocity else None, normalize=normalize,
                                                     want_global=want_global, state=state)
         return MotionSample(lr, rt, g_rot, g_pos, None if v is None else v[:, :J], None if v is None else v[:, J:])
+
+
+@dataclass
+class DofMotionSample:
+    """What ``DofMotionLibrary.sample`` returns, device tensors: dof_pos / dof_vel (N, J-1), root_translation /
+    root_velocity / root_angular_velocity (N, 3), root_rotation (N, 4), global_rotation (N, J, 4), global_translation
+    (N, J, 3), key_translation (N, K, 3); the parts not asked for are None."""
+    dof_pos: torch.Tensor
+    root_translation: torch.Tensor
+    root_rotation: torch.Tensor
+    dof_vel: Optional[torch.Tensor] = None
+    root_velocity: Optional[torch.Tensor] = None
+    root_angular_velocity: Optional[torch.Tensor] = None
+    global_rotation: Optional[torch.Tensor] = None
+    global_translation: Optional[torch.Tensor] = None
+    key_translation: Optional[torch.Tensor] = None
+
+
+def _rows(x, width: int, squeeze_axis: int):
+    """A clip's (L, width) rows from (L, width), or with the singleton axis of fit_pose's (L, J-1, 1) / (L, 1, 4)."""
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    if t.dim() == 3 and t.shape[squeeze_axis] == 1:
+        t = t.squeeze(squeeze_axis)
+    return t if t.dim() == 2 and t.shape[1] == width else None
+
+
+class DofMotionLibrary:
+    """One or many joint-angle clips of ONE model, packed frame-major on the current device.  ``model``: a
+    ``HuForwardModel`` (or an ``rtg.runtime.DofModel``); ``clips``: ``(angles, root_translation, root_rotation, fps)``
+    tuples -- the first three items of ``fit_pose``'s return in that order -- with angles (L, J-1, 1) or (L, J-1), root
+    translation (L, 3), root rotation (L, 1, 4) or (L, 4)."""
+
+    def __init__(self, model, clips):
+        if isinstance(clips, tuple) and len(clips) == 4 and not isinstance(clips[3], (tuple, list)):
+            clips = [clips]   # one clip, not a list of them
+        clips = list(clips)
+        if not clips:
+            raise ValueError("DofMotionLibrary: no clips")
+        dof_model = getattr(model, "_model", model)
+        nd = getattr(dof_model, "num_dofs", None)
+        if nd is None:
+            raise ValueError("DofMotionLibrary: expected a HuForwardModel or a DofModel")
+        J = int(nd) + 1
+        if not 1 <= J <= 64:
+            raise ValueError(f"DofMotionLibrary: serves models of 1..64 joints, this one has {J}")
+        parts, fps = [], []
+        for i, clip in enumerate(clips):
+            if not isinstance(clip, (tuple, list)) or len(clip) != 4:
+                raise ValueError(f"DofMotionLibrary: clip {i} is not (angles, root_translation, root_rotation, fps)")
+            a, t, r = _rows(clip[0], nd, 2), _rows(clip[1], 3, 1), _rows(clip[2], 4, 1)
+            if a is None or t is None or r is None:
+                raise ValueError(f"DofMotionLibrary: clip {i} must be (L, {nd}[, 1]) angles, (L, 3) root translation and "
+                                 f"(L[, 1], 4) root rotation, got "
+                                 f"{' / '.join(str(tuple(np.shape(x))) for x in clip[:3])}")
+            if not (a.shape[0] == t.shape[0] == r.shape[0]) or a.shape[0] < 1:
+                raise ValueError(f"DofMotionLibrary: clip {i} must have one length >= 1, got {a.shape[0]} / {t.shape[0]} / "
+                                 f"{r.shape[0]} frames")
+            try:
+                f = float(np.float32(clip[3]))
+            except (TypeError, ValueError):
+                f = float("nan")
+            if not (np.isfinite(f) and f > 0):
+                raise ValueError(f"DofMotionLibrary: clip {i} has fps {clip[3]!r}")
+            parts.append((a, t, r))
+            fps.append(f)
+        dev = require_gpu_rtg()
+        self.model = dof_model
+        self.node_names = list(getattr(model, "node_names", None) or [])
+        lengths = np.array([p[0].shape[0] for p in parts], np.int32)
+        start = np.concatenate([[0], np.cumsum(lengths[:-1], dtype=np.int64)]).astype(np.int64)
+
+        def pack(k):
+            return torch.cat([p[k].detach().to(device=dev, dtype=torch.float32) for p in parts], dim=0).contiguous()
+
+        self.dof, self.root_t, self.root_rot = pack(0), pack(1), pack(2)
+        self._lib = MotionLib(start, lengths, np.asarray(fps, np.float32), int(lengths.sum()))
+        self._lengths, self._fps = lengths, np.asarray(fps, np.float32)
+
+    @property
+    def num_clips(self) -> int:
+        return int(self._lengths.shape[0])
+
+    @property
+    def lengths(self) -> np.ndarray:
+        """Frames per clip (int32)."""
+        return self._lengths
+
+    @property
+    def fps(self) -> np.ndarray:
+        """Frame rate per clip (float32)."""
+        return self._fps
+
+    @property
+    def durations(self) -> np.ndarray:
+        """Seconds from each clip's first frame to its last (float64): (length - 1) / fps."""
+        return (self._lengths.astype(np.float64) - 1.0) / self._fps.astype(np.float64)
+
+    def _link_indices(self, key_links):
+        if key_links is None:
+            return None
+        out = []
+        for link in key_links:
+            if isinstance(link, str):
+                if link not in self.node_names:
+                    raise ValueError(f"key_links: the skeleton has no node named {link!r}")
+                out.append(self.node_names.index(link))
+            else:
+                out.append(int(link))
+        return out
+
+    def sample(self, clip_ids, times, key_links=None, want_velocity: bool = True, want_global: bool = True,
+               normalize: bool = True, clip_angles: bool = False) -> DofMotionSample:
+        """The library's states at ``times`` (seconds from the first frame of clip ``clip_ids[n]``; clamped to the
+        clip, no wrap-around) in one launch.  ``key_links``: up to 32 node names or joint indices whose positions come
+        back as ``key_translation`` (also with ``want_global=False``, which skips the full link poses).
+        ``want_velocity``: the forward differences of the bracketing frames (DOF and root linear velocity) and the
+        pair's angular velocity.  ``normalize``: ``quat_normalize`` after the root rotation's slerp.  ``clip_angles``:
+        the link poses from the angles clamped to the model's limits.  A clip id outside 0..num_clips-1 gives NaN
+        rows."""
+        if clip_angles and not self.model.has_limits:
+            raise ValueError("clip_angles needs DOF limits with one entry per DOF")
+        r = ops.dof_motion_sample(self.model, self._lib, self.dof, self.root_rot, self.root_t, clip_ids, times,
+                                  normalize=normalize, clip=clip_angles, want_velocity=want_velocity,
+                                  want_global=want_global, key_links=self._link_indices(key_links))
+        rv = r.root_vel
+        return DofMotionSample(r.dof, r.root_t, r.root_rot, r.dof_vel, None if rv is None else rv[:, :3],
+                               None if rv is None else rv[:, 3:], r.g_rot, r.g_pos, r.key_pos)

@@ -342,6 +342,70 @@ def motion_sample(topo: Topology, mlib: MotionLib, rot, root_t, clip_ids, times,
     return out_rot, out_root, out_vec, g_rot, g_pos
 
 
+# what dof_motion_sample returns, device tensors: dof (N, J-1), dof_vel (N, J-1), root_rot (N, 4), root_t (N, 3),
+# root_vel (N, 6) {linear, angular}, g_rot (N, J, 4), g_pos (N, J, 3), key_pos (N, K, 3); the parts not asked for are None
+DofMotionSampleResult = collections.namedtuple("DofMotionSampleResult",
+                                               "dof dof_vel root_rot root_t root_vel g_rot g_pos key_pos")
+
+
+def dof_motion_sample(model, mlib: MotionLib, dof, root_rot, root_t, clip_ids, times, normalize: bool = False,
+                      clip: bool = False, want_velocity: bool = True, want_global: bool = True, key_links=None):
+    """Sample a library of joint-angle clips at (clip, time) pairs in one launch (rtg.h rtg_dof_motion_sample_f32): per
+    query the two frames around ``time * fps`` of its clip, torch's ``(1 - b) * a + b * c`` on the joint angles and the
+    root translation, ``quat_slerp`` of the root rotation (``quat_normalize`` after it with ``normalize``), with
+    ``want_velocity`` the forward differences of the bracketing frames over the frame time (joint velocities, root
+    linear velocity) and SkeletonMotion's unfiltered angular velocity of the root pair, with ``want_global`` the
+    forward kinematics of the blended angles (clamped to the model's limits with ``clip``), and with ``key_links`` (up
+    to 32 joint indices, repeats allowed) those links' positions alone.
+
+    dof (F_total, J-1), root_rot (F_total, 4) and root_t (F_total, 3) are the library's packed arrays, clip_ids (N)
+    int32 and times (N) float32 the queries.  Returns a DofMotionSampleResult on the device.  A query whose clip id is
+    outside 0..C-1 gives NaN rows.  Raises RtgError without a GPU: there is no CPU fallback."""
+    import numpy as np
+    dev = require_gpu_rtg()
+    nd, Ft = model.num_dofs, mlib.total_frames
+    J = nd + 1
+    d = dev_f32(dof, (nd,), "dof")
+    rr = dev_f32(root_rot, (4,), "root_rot")
+    rt = dev_f32(root_t, (3,), "root_t")
+    if tuple(d.shape) != (Ft, nd) or tuple(rr.shape) != (Ft, 4) or tuple(rt.shape) != (Ft, 3):
+        raise ValueError(f"dof / root_rot / root_t must be ({Ft}, {nd}) / ({Ft}, 4) / ({Ft}, 3), got {tuple(d.shape)} / "
+                         f"{tuple(rr.shape)} / {tuple(rt.shape)}")
+    c = clip_ids if isinstance(clip_ids, torch.Tensor) else torch.as_tensor(clip_ids)
+    if c.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError(f"clip_ids must be integers, got {c.dtype}")
+    c = c.to(device=dev, dtype=torch.int32).contiguous()
+    tm = dev_f32(times)
+    if c.dim() != 1 or tm.shape != c.shape:
+        raise ValueError(f"clip_ids / times must be (N,) each, got {tuple(c.shape)} / {tuple(tm.shape)}")
+    if mlib.device != dev:
+        raise ValueError(f"the queries are on {dev}; this library lives on {mlib.device}")
+    if clip and not model.has_limits:
+        raise ValueError("clip needs a model with DOF limits")
+    keys = np.zeros(0, np.int32) if key_links is None else np.ascontiguousarray(np.asarray(key_links, np.int64).reshape(-1))
+    K = int(keys.shape[0])
+    if K > _lib.DOF_MOTION_MAX_KEY_LINKS:
+        raise ValueError(f"{K} key links, at most {_lib.DOF_MOTION_MAX_KEY_LINKS}")
+    if K and (keys.min() < 0 or keys.max() >= J):
+        raise ValueError(f"key_links must lie in 0..{J - 1}, got {keys.tolist()}")
+    keys = keys.astype(np.int32)
+    N = int(c.shape[0])
+
+    def out(*shape):
+        return torch.empty((N,) + shape, device=dev, dtype=torch.float32)
+
+    o_dof, o_rr, o_rt = out(nd), out(4), out(3)
+    o_dv, o_rv = (out(nd), out(6)) if want_velocity else (None, None)
+    g_rot, g_pos = (out(J, 4), out(J, 3)) if want_global else (None, None)
+    key_pos = out(K, 3) if K else None
+    flags = (_lib.DOF_MOTION_NORMALIZE if normalize else 0) | (_lib.DOF_MOTION_CLIP if clip else 0)
+    check(lib().rtg_dof_motion_sample_f32(model.handle, mlib.handle, ptr(d), ptr(rr), ptr(rt), ptr(c), ptr(tm), N, flags,
+                                          keys.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if K else None, K,
+                                          ptr(o_dof), ptr(o_dv), ptr(o_rr), ptr(o_rt), ptr(o_rv), ptr(g_rot), ptr(g_pos),
+                                          ptr(key_pos), stream_handle()))
+    return DofMotionSampleResult(o_dof, o_dv, o_rr, o_rt, o_rv, g_rot, g_pos, key_pos)
+
+
 def dof_forward_kinematics(model, dof, root_rot, root_t, clip: bool = False):
     """HuForwardModel.forward_kinematics (hu_forward_model.py:17-33): joint angles (..., J-1) [or (..., J-1, 1)],
     root rotation (..., 4) [or (..., 1, 4)], root translation (..., 3) -> g_rot (..., J, 4), g_pos (..., J, 3)."""

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*); rtg_dof_fit_f32,
-                                  rtg_dof_fit_root_f32, rtg_dof_fit_orient_f32, rtg_dof_fit_prior_f32, rtg_dof_fit_apart_f32 and rtg_dof_fit_robust_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
+                                  rtg_dof_fit_root_f32, rtg_dof_fit_orient_f32, rtg_dof_fit_prior_f32, rtg_dof_fit_apart_f32, rtg_dof_fit_robust_f32 and rtg_dof_motion_sample_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
                                6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
                                5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
                                4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
@@ -564,6 +564,50 @@ int rtg_motion_sample_f32(rtg_topology_t topo, rtg_motion_lib_t lib, const float
                           const float *vec, int32_t K, const int32_t *clip, const float *time, int64_t N, int flags,
                           float *local_rot_out, float *root_t_out, float *vec_out, float *g_rot, float *g_pos,
                           rtg_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Motion sampling of JOINT-ANGLE clips: what rtg_dof_fit_root_f32 and its successors return -- per frame J-1 joint
+ * angles, a root rotation and a root translation -- packed frame-major as dof (F_total,J-1), root_rot (F_total,4),
+ * root_t (F_total,3) on an rtg_motion_lib_t clip table (the same handle type, index rule and validity rule as
+ * above), sampled at (clip, time) pairs in ONE launch.  Every joint of the model turns about one fixed axis, so the
+ * slerp of a joint is the linear blend of its angle.  With (i0, i1, b) of the index rule, rows r0 = start + i0,
+ * r1 = start + i1 and dt = (float)(1.0 / (double)fps[c]):
+ *   - dof_out[n, d]     = ((1.0f - b) * dof[r0, d]) + (b * dof[r1, d]): four float32 roundings, no FMA;
+ *   - dof_vel_out[n, d] = (dof[r1, d] - dof[r0, d]) / dt: one float32 subtraction, one correctly rounded float32
+ *     division -- the forward difference of the bracketing frames, constant over the bracket; at and past the clip's
+ *     last frame r0 == r1 and it is +0 for finite rows;
+ *   - root_rot_out[n]   = RTG_OP_QUAT_SLERP(root_rot[r0], root_rot[r1], b), then RTG_OP_QUAT_NORMALIZE with
+ *     RTG_DOF_MOTION_NORMALIZE; root_t_out[n] the blend of dof_out's form;
+ *   - root_vel_out[n, 0:3] = (root_t[r1] - root_t[r0]) / dt; root_vel_out[n, 3:6] = SkeletonMotion's unfiltered
+ *     angular velocity of the pair (skeleton3d.py:1137-1146; rtg_angular_velocity_f32 without taps on the two-frame
+ *     sequence [root_rot[r0], root_rot[r1]], frame 0): with d = quat_mul_norm(r1, quat_conjugate(r0)),
+ *     ((d.xyz / max(|d.xyz|, 1e-9)) * acos(clamp(2 d.w^2 - 1, -1, 1))) / dt;
+ *   - g_rot / g_pos are what rtg_dof_fk_f32 gives on dof_out[n], root_rot_out[n], root_t_out[n], with clip_angles =
+ *     RTG_DOF_MOTION_CLIP; key_pos[n, k] = g_pos[n, key_links[k]] bit for bit, and may be asked for without g_rot /
+ *     g_pos (their rows are then not written at all);
+ *   - every output element of an invalid query (clip id outside 0..C-1) is the quiet NaN 0x7FC00000.
+ * dof_out, root_rot_out, root_t_out are always given; dof_vel_out (N,J-1) and root_vel_out (N,6) together or both NULL; g_rot
+ * and g_pos together or both NULL; key_pos (N,K,3) iff K > 0, with key_links K HOST int32 values in 0..J-1 (repeats
+ * allowed, 0 <= K <= RTG_DOF_MOTION_MAX_KEY_LINKS) read before the call returns.  root_rot, root_rot_out and g_rot are
+ * 16-byte aligned; no output overlaps an input or another output.  A one-joint model has no angles: dof, dof_out and
+ * dof_vel_out are then not dereferenced and may be NULL (rtg_dof_fit_root_f32's rule).  Never allocates or
+ * synchronises; N == 0 is a no-op after the argument checks.  A model of more than 64 joints is RTG_ERR_UNSUPPORTED;
+ * every other rejection -- N < 0, K outside its range, a key link outside 0..J-1, unknown flags,
+ * RTG_DOF_MOTION_CLIP on a model without limits, a NULL handle or buffer, an unpaired optional output, key_pos
+ * without K or K without key_pos, a misaligned or overlapping buffer -- is RTG_ERR_INVALID_ARGUMENT, decided before
+ * any HIP call, with the reason in rtg_last_error().
+ * ---------------------------------------------------------------------- */
+#define RTG_DOF_MOTION_MAX_KEY_LINKS 32   /* the key links travel in the launch arguments */
+typedef enum rtg_dof_motion_flags {
+    RTG_DOF_MOTION_NORMALIZE = 1,   /* quat_normalize after the root rotation's slerp */
+    RTG_DOF_MOTION_CLIP = 2         /* the global outputs from the angles clamped to the model's limits (straight-through,
+                                       as rtg_dof_fk_f32's clip_angles); dof_out stays the blend */
+} rtg_dof_motion_flags;
+int rtg_dof_motion_sample_f32(rtg_dof_model_t model, rtg_motion_lib_t lib, const float *dof, const float *root_rot,
+                              const float *root_t, const int32_t *clip, const float *time, int64_t N, int flags,
+                              const int32_t *key_links, int32_t K, float *dof_out, float *dof_vel_out,
+                              float *root_rot_out, float *root_t_out, float *root_vel_out, float *g_rot, float *g_pos,
+                              float *key_pos, rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Motion-level prep of the legacy motion path (retarget/main.py)

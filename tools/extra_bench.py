@@ -51,6 +51,15 @@
               quat_normalize, torch blends, forward_kinematics), interleaved rounds, the results compared bit for bit
   motion_sample_traffic -- a few launches of the fused sampler and a 256 MiB copy of known bytes, for a counter run of
               its own against the algorithmic bytes that `motion_sample` prints
+  dof_motion_sample -- the fused joint-angle sampler (rtg_dof_motion_sample_f32, C ABI, preallocated outputs; Hu v5, 64
+              clips x 4096 frames, N=262144 random (clip, time) queries, velocities on; three output sets: full global
+              rows + 6 key links, 6 key links only, local only) against the same outputs composed from the launches that
+              were there before it (index rule in torch, index_select, torch blends and differences, quat_slerp,
+              quat_normalize, motion_angular_velocity, dof_forward_kinematics), interleaved rounds, the results
+              compared bit for bit; for the record rtg_motion_sample_f32 (GLOBAL, velocities) on the equivalent
+              quaternion library at the same N
+  dof_motion_sample_traffic -- a few launches of each output set and a 256 MiB copy of known bytes, for a counter run of
+              its own against the algorithmic bytes that `dof_motion_sample` prints
   fit_targets -- the keypoint targets of the pose fit (rtg_fit_targets_f32, C ABI, preallocated outputs; VTRDyn-21 ->
               33-link Hu, the 15 pairs of tests/golden/retarget_to_names.json's vtrdyn_full_hu, B=262144, dir on) against
               the composition of launches that were there before it (index_select of the mapped rows,
@@ -1200,6 +1209,154 @@ def motion_sample_traffic(N=262144, clips=64, frames=4096):
     torch.cuda.synchronize()
     return {"N": N, "copy_bytes_each_way": 4 << 26,
             "launches": "3 x 256 MiB copy, 3 x global + vec (STATE), 3 x local only; random (clip, time)"}
+
+
+DOF_MOTION_KEYS = (0, 6, 12, 17, 23, 30)   # pelvis, feet, head, hands of Hu v5 by index: any six links do
+# output set -> (global rows, key links); velocities are on in all three
+DOF_MOTION_SETS = {"full_global": (True, True), "key_links_only": (False, True), "local_only": (False, False)}
+
+
+def _dof_motion_setup(N, clips, frames, seed=29):
+    """Hu v5 with its DOF axes, a library of `clips` x `frames` joint-angle frames at 30 fps, N random queries, the
+    preallocated outputs."""
+    from retarget.robot_config import Hu_v5
+    from rtg.runtime import DofModel, MotionLib
+    J, fps, Ft = 31, 30.0, clips * frames
+    M = DofModel(Topology(assets.parents("hu_v5"), assets.local_translation("hu_v5")), list(Hu_v5.Hu_DOF_AXIS))
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    dof = (0.5 * torch.randn((clips, 1, J - 1), device="cuda", generator=gen) +
+           0.02 * torch.randn((clips, frames, J - 1), device="cuda", generator=gen).cumsum(1)).reshape(Ft, J - 1).contiguous()
+    rr = torch.nn.functional.normalize(torch.randn((clips, 1, 4), device="cuda", generator=gen) +
+                                       0.02 * torch.randn((clips, frames, 4), device="cuda", generator=gen).cumsum(1),
+                                       dim=-1).reshape(Ft, 4).contiguous()
+    rt = torch.randn((Ft, 3), device="cuda", generator=gen)
+    start = np.arange(clips, dtype=np.int64) * frames
+    ML = MotionLib(start, np.full(clips, frames, np.int32), np.full(clips, fps, np.float32), Ft)
+    clip = torch.randint(0, clips, (N,), device="cuda", generator=gen, dtype=torch.int32)
+    time_ = (torch.rand((N,), device="cuda", generator=gen) * ((frames - 1) / fps)).float()
+    K = len(DOF_MOTION_KEYS)
+    outs = {k: torch.empty((N,) + shp, device="cuda") for k, shp in (
+        ("dof", (J - 1,)), ("dof_vel", (J - 1,)), ("root_rot", (4,)), ("root_t", (3,)), ("root_vel", (6,)),
+        ("g_rot", (J, 4)), ("g_pos", (J, 3)), ("key_pos", (K, 3)))}
+    return M, ML, J, fps, dof, rr, rt, torch.as_tensor(start, device="cuda"), clip, time_, outs
+
+
+def _dof_motion_call(lib, M, ML, dof, rr, rt, clip, time_, N, outs, want_global, want_keys):
+    from rtg.runtime import ptr, stream_handle
+    keys = np.asarray(DOF_MOTION_KEYS, np.int32)
+    o = outs
+    _lib.check(lib.rtg_dof_motion_sample_f32(
+        M.handle, ML.handle, ptr(dof), ptr(rr), ptr(rt), ptr(clip), ptr(time_), N, _lib.DOF_MOTION_NORMALIZE,
+        keys.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if want_keys else None, len(keys) if want_keys else 0,
+        ptr(o["dof"]), ptr(o["dof_vel"]), ptr(o["root_rot"]), ptr(o["root_t"]), ptr(o["root_vel"]),
+        ptr(o["g_rot"]) if want_global else None, ptr(o["g_pos"]) if want_global else None,
+        ptr(o["key_pos"]) if want_keys else None, stream_handle()))
+
+
+def _dof_motion_bytes(J, want_global, want_keys):
+    """Algorithmic bytes per query: two rows of angles, root rotation and root translation plus (clip, time) read;
+    angles, their velocities, the root's pose and velocities, the key links and the global rows written."""
+    nd, K = J - 1, len(DOF_MOTION_KEYS)
+    return 2 * (4 * nd + 16 + 12) + 8, 4 * nd + 4 * nd + 28 + 24 + (12 * K if want_keys else 0) + (28 * J if want_global else 0)
+
+
+def dof_motion_sample(N=262144, rounds=4, clips=64, frames=4096):
+    """The fused joint-angle sampler against the same outputs composed from the launches that existed before it, three
+    output sets, interleaved rounds, the results compared bit for bit; then, for the record, rtg_motion_sample_f32
+    (NORMALIZE | GLOBAL | STATE, 2 J velocity rows) on a quaternion library of the same size at the same N."""
+    from rtg.runtime import MotionLib, ptr, stream_handle
+    lib = _lib.lib()
+    M, ML, J, fps, dof, rr, rt, start_d, clip, time_, outs = _dof_motion_setup(N, clips, frames)
+    keys_d = torch.as_tensor(DOF_MOTION_KEYS, device="cuda")
+    dt = float(np.float32(1.0 / np.float64(np.float32(fps))))
+    dt_d = torch.full((N, 1), dt, device="cuda")   # a tensor: torch divides by a Python scalar as a product by 1 / dt
+    res = {}
+    for name, (want_global, want_keys) in DOF_MOTION_SETS.items():
+        def fused():
+            _dof_motion_call(lib, M, ML, dof, rr, rt, clip, time_, N, outs, want_global, want_keys)
+
+        def composed():
+            p = (time_.double() * fps).clamp_min(0.0).nan_to_num(0.0)
+            end = p >= frames - 1
+            i0 = torch.where(end, frames - 1, p.long())
+            b = torch.where(end, 0.0, p - i0).float()
+            r0 = start_d[clip.long()] + i0
+            r1 = r0 + (~end).long()
+            a0, a1 = dof.index_select(0, r0), dof.index_select(0, r1)
+            q0, q1 = rr.index_select(0, r0), rr.index_select(0, r1)
+            t0, t1 = rt.index_select(0, r0), rt.index_select(0, r1)
+            d = (1 - b)[:, None] * a0 + b[:, None] * a1
+            dv = (a1 - a0) / dt_d
+            q = ops.quat_normalize(ops.quat_slerp(q0, q1, b))
+            t = (1 - b)[:, None] * t0 + b[:, None] * t1
+            w = ops.motion_angular_velocity(torch.stack([q0, q1], 1)[:, :, None, :], dt, smooth=False)[:, 0, 0]
+            rv = torch.cat([(t1 - t0) / dt_d, w], dim=1)
+            gr = gp = kp = None
+            if want_global or want_keys:
+                gr, gp = ops.dof_forward_kinematics(M, d, q, t)
+                if want_keys:
+                    kp = gp.index_select(1, keys_d)
+            return {"dof": d, "dof_vel": dv, "root_rot": q, "root_t": t, "root_vel": rv,
+                    "g_rot": gr if want_global else None, "g_pos": gp if want_global else None, "key_pos": kp}
+
+        fused()
+        c = composed()
+        torch.cuda.synchronize()
+        same = {k: bool(torch.equal(outs[k].view(torch.int32), v.contiguous().view(torch.int32)))
+                for k, v in c.items() if v is not None}
+        del c
+        f_us, c_us = [], []
+        for _ in range(rounds):   # interleaved: both see the same box state
+            f_us.append(time_events(fused, reps=20, warm=3) * 1e3)
+            c_us.append(time_events(composed, reps=5, warm=1) * 1e3)
+        rd, wr = _dof_motion_bytes(J, want_global, want_keys)
+        res[name] = {"N": N, "J": J, "K": len(DOF_MOTION_KEYS) if want_keys else 0,
+                     "algorithmic_bytes_per_query": {"read": rd, "written": wr},
+                     "fused_us": f_us, "composed_us": c_us,
+                     "composed_over_fused": [c_ / f_ for f_, c_ in zip(f_us, c_us)],
+                     "fused_TBs": [N * (rd + wr) / (u * 1e-6) / 1e12 for u in f_us],
+                     "composed_equals_fused_bits": same, "every_fused_faster": max(f_us) < min(c_us)}
+    del outs
+    # for the record: the quaternion library's launch, global rows and 2 J velocity rows, the same queries
+    T = topo("hu_v5")
+    K, Ft = 2 * J, clips * frames
+    gen = torch.Generator(device="cuda").manual_seed(23)
+    rot = torch.nn.functional.normalize(torch.randn((Ft, J, 4), device="cuda", generator=gen), dim=-1)
+    vec = torch.randn((Ft, K, 3), device="cuda", generator=gen)
+    o_lr, o_gr = torch.empty((N, J, 4), device="cuda"), torch.empty((N, J, 4), device="cuda")
+    o_rt, o_gp = torch.empty((N, 3), device="cuda"), torch.empty((N, J, 3), device="cuda")
+    o_v = torch.empty((N, K, 3), device="cuda")
+    flags = _lib.MOTION_NORMALIZE | _lib.MOTION_GLOBAL | _lib.MOTION_STATE
+
+    def quat():
+        _lib.check(lib.rtg_motion_sample_f32(T.handle, ML.handle, ptr(rot), ptr(rt), ptr(vec), K, ptr(clip), ptr(time_), N,
+                                             flags, ptr(o_lr), ptr(o_rt), ptr(o_v), ptr(o_gr), ptr(o_gp), stream_handle()))
+
+    res["quaternion_library_global_vec"] = {
+        "N": N, "J": J, "K": K, "fused_us": [time_events(quat, reps=20, warm=3) * 1e3 for _ in range(rounds)],
+        "algorithmic_bytes_per_query": {"read": 2 * (16 * J + 12 + 12 * K) + 8, "written": 16 * J + 12 + 12 * K + 28 * J}}
+    return res
+
+
+def dof_motion_sample_traffic(N=262144, clips=64, frames=4096):
+    """Three 256 MiB device copies of known bytes, then three launches of each output set of the fused joint-angle
+    sampler (full global, key links only, local only, in that order), nothing else: for a counter run of its own
+    (FETCH_SIZE or WRITE_SIZE, one per run) against the algorithmic bytes that `dof_motion_sample` prints.  The copy
+    calibrates the counters' unit."""
+    lib = _lib.lib()
+    M, ML, J, fps, dof, rr, rt, _, clip, time_, outs = _dof_motion_setup(N, clips, frames)
+    src, dst = torch.randn(1 << 26, device="cuda"), torch.empty(1 << 26, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(3):
+        dst.copy_(src)
+    for want_global, want_keys in DOF_MOTION_SETS.values():
+        for _ in range(3):
+            _dof_motion_call(lib, M, ML, dof, rr, rt, clip, time_, N, outs, want_global, want_keys)
+    torch.cuda.synchronize()
+    return {"N": N, "copy_bytes_each_way": 4 << 26,
+            "algorithmic_bytes_per_query": {k: dict(zip(("read", "written"), _dof_motion_bytes(J, *v)))
+                                            for k, v in DOF_MOTION_SETS.items()},
+            "launches": "3 x 256 MiB copy, then 3 x each of " + ", ".join(DOF_MOTION_SETS) + "; random (clip, time)"}
 
 
 def _fit_targets_setup(B):
