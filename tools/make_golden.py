@@ -31,6 +31,9 @@ Fixtures (all float32 unless noted):
   motion_sample.npz          8 queries per family of tests/motion_sample_ref.py (the hostile rotation sequences, the
                              slerp threshold pairs, the time families) through quat_slerp, quat_normalize and torch's
                              (1 - b) * a + b * c: the queries, the gathered rows and the reference's outputs
+  motion_prep_adversarial.npz  the hostile batches of tests/motion_prep_frames.py (16 or 24 frames per family) through
+                             quat_between_two_vecs, coord_transform + rescale_motion_to_standard_size and
+                             _rebuild_with_vtrdyn_zero_pose: outputs, the rebuild's raise per batch, a crc of the inputs
 """
 from __future__ import annotations
 
@@ -770,6 +773,81 @@ def gen_kinematics_adversarial(ref, torch, per_family=8):
     return out
 
 
+def gen_motion_prep_adversarial(ref, torch):
+    """The hostile batches of tests/motion_prep_frames.py through the reference's quat_between_two_vecs, coord_transform
+    + Retarget.rescale_motion_to_standard_size (with dir = [-1, -1, 1] and without) and
+    RetargetHuV5fromMocap._rebuild_with_vtrdyn_zero_pose, the rebuild on the reference's own rescaled motion and on
+    the family's raw motion (the rescale removes every short bone, so only the raw motion reaches the rebuild's
+    batch-level identity branch).  Outputs only; input_crc pins the helper's bytes.  The rebuild runs one batched SVD,
+    which raises for the whole batch when a Kabsch matrix holds a NaN: then <key>_status is 1, rows 0 and 10 are NaN and
+    the other rows are quat_between_two_vecs called per bone, a later child over an earlier one, then quat_normalize,
+    which is what the rebuild does with them (main.py:144-152, skeleton3d.py:610)."""
+    import contextlib
+    import io
+    import types
+    import zlib
+    path = list(sys.path)
+    sys.path[:0] = [os.path.join(REPO, "tests"), os.path.join(REPO, "oracle")]
+    try:
+        rh.load_rtg_module("assets")
+        import motion_prep_frames as mp
+        mp.parents()
+    finally:
+        sys.path[:] = path                  # tests/conftest.py puts the drop-in packages in front of the reference's
+    main = rh.load_main_module(ref)
+    t3, r3 = ref.transform3d, ref.rotation3d
+    zp = rh.ref_zero_pose(ref, "vtrdyn")
+    rt = main.RetargetHuV5fromMocap(zp, zp)
+    zl = t2n(zp.local_translation)
+    T = torch.from_numpy
+    out, crc = {}, 0
+
+    def rebuild(x, key, fam):
+        L = len(x)
+        try:
+            with contextlib.redirect_stdout(io.StringIO()):
+                g = t2n(rt._rebuild_with_vtrdyn_zero_pose(T(x.copy())).global_rotation)
+            status, msg = 0, ""
+        except Exception as e:  # noqa: BLE001 -- classified: only the documented SVD raise is accepted
+            status = classify(e)
+            assert status == STATUS_SVD, (fam, key, e)
+            msg = f"{type(e).__name__}: {str(e).strip().splitlines()[-1]}"
+            g = torch.tensor([[[0.0, 0.0, 0.0, 1.0]]]).repeat(L, 21, 1)
+            g[:, [0, 10]] = float("nan")
+            for j, p in enumerate(zp.parent_indices):
+                if j and p not in (0, 10):
+                    g[:, p] = t3.quat_between_two_vecs(zp.local_translation.repeat(L, 1, 1)[:, j], T(x[:, j] - x[:, p]))
+            g = t2n(r3.quat_normalize(g))
+        # the SVD raises exactly where a NaN (an inf - inf or inf * 0 included) reaches joints 0, 1, 4, 7, 10, 11, 13, 17
+        assert bool(status) == mp.svd_input_has_nan(x, zl), (fam, key, status, msg)
+        out[key], out[f"{key}_status"], out[f"{key}_message"] = g, np.array(status, np.int8), np.array(msg)
+
+    pairs = mp.fixture_pairs()
+    for name, (v1, v2) in pairs.items():
+        crc = zlib.crc32(v1.tobytes() + v2.tobytes(), crc)
+        out[f"qb_{name}"] = t2n(t3.quat_between_two_vecs(T(v1.copy()), T(v2.copy())))
+    for fam in mp.MOTION_FAMILIES:
+        m = mp.fixture_motion(fam)
+        crc = zlib.crc32(m.tobytes(), crc)
+        r = t2n(main.Retarget.rescale_motion_to_standard_size(
+            t3.coord_transform(T(m.copy()), dir=torch.Tensor([-1, -1, 1])), zp))
+        out[f"m_{fam}_rescaled"] = r
+        out[f"m_{fam}_rescaled_nodir"] = t2n(main.Retarget.rescale_motion_to_standard_size(T(m.copy()), zp))
+        rebuild(r, f"m_{fam}_rebuild", fam)
+        rebuild(m, f"m_{fam}_rebuild_raw", fam)
+    full = rh.ref_zero_pose(ref, "vtrdyn_full")
+    trees = mp.topologies({"vtrdyn": zp.parent_indices.numpy(), "vtrdyn_full": full.parent_indices.numpy()},
+                          {"vtrdyn": zl, "vtrdyn_full": t2n(full.local_translation)})
+    for name, (par, lt, m) in trees.items():
+        crc = zlib.crc32(par.tobytes() + lt.tobytes() + m.tobytes(), crc)
+        tree = types.SimpleNamespace(parent_indices=T(par.astype(np.int64)), local_translation=T(lt.copy()))
+        out[f"topo_{name}_rescaled"] = t2n(main.Retarget.rescale_motion_to_standard_size(T(m.copy()), tree))
+    out["input_crc"] = np.array(crc, np.int64)
+    out["families"] = np.array(mp.MOTION_FAMILIES)
+    out["pairs"] = np.array(list(pairs))
+    return out
+
+
 def gen_motion_sample(ref, torch):
     """The reference's quat_slerp (transform3d.py:152-174), quat_normalize (rotation3d.py:92-98) and torch's
     (1 - b) * a + b * c on the rows the index rule gathers, in chunks of 16 rows like the other fixtures.  Invalid
@@ -866,6 +944,7 @@ def main() -> None:
         "motion_adversarial": lambda: gen_motion_adversarial(ref, torch),
         "kinematics_adversarial": lambda: gen_kinematics_adversarial(ref, torch),
         "motion_sample": lambda: gen_motion_sample(ref, torch),
+        "motion_prep_adversarial": lambda: gen_motion_prep_adversarial(ref, torch),
     }
     only = set(sys.argv[1:])
     for name, fn in jobs.items():
