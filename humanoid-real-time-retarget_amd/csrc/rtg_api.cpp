@@ -676,6 +676,42 @@ int rtg_dof_fk_f32(rtg_dof_model_t m, const float *dof, const float *root_rot, c
     return RTG_OK;
 }
 
+int rtg_dof_fk_vel_f32(rtg_dof_model_t m, const float *dof, const float *root_rot, const float *root_t,
+                       const float *dof_vel, const float *root_vel, int64_t B, int clip, float *g_rot, float *g_pos,
+                       float *g_vel, rtg_stream_t stream)
+{
+    const char *fn = "rtg_dof_fk_vel_f32";
+    // what does not depend on the handle first (rtg_dof_motion_sample_f32's order)
+    if (B < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: B=%lld < 0", fn, (long long)B);
+    if (B > 0) {   // empty buffers have no address to give
+        if ((g_rot == nullptr) != (g_pos == nullptr))
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both g_rot and g_pos or neither", fn);
+        if (!root_rot || !root_t || !g_vel) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    }
+    if ((reinterpret_cast<uintptr_t>(root_rot) | reinterpret_cast<uintptr_t>(g_rot)) & 15)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: root_rot / g_rot not 16-byte aligned", fn);
+    if (!m) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL model", fn);
+    const int J = m->topo->J;
+    if (J > kGroupMaxJ || !m->topo->gsched.get())
+        return fail(RTG_ERR_UNSUPPORTED, "%s: serves models of 1..%d joints (this one has %d)", fn, kGroupMaxJ, J);
+    if (clip && !m->has_limits)
+        return fail(RTG_ERR_INVALID_ARGUMENT, "%s: clip_angles requested but the model has no DOF limits", fn);
+    if (B == 0) return RTG_OK;
+    if (J > 1 && (!dof || !dof_vel)) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
+    {   // no output may overlap an input (or another output)
+        const uint64_t n = (uint64_t)B, j = (uint64_t)J;
+        const Span in[] = {{dof, n * (j - 1) * 4, "dof"}, {dof_vel, n * (j - 1) * 4, "dof_vel"},
+                           {root_rot, n * 16, "root_rot"}, {root_t, n * 12, "root_t"}, {root_vel, n * 24, "root_vel"}};
+        const Span outs[] = {{g_rot, n * j * 16, "g_rot"}, {g_pos, n * j * 12, "g_pos"}, {g_vel, n * j * 24, "g_vel"}};
+        RTG_CHECK(check_overlap(fn, outs, 3, in, 5));
+    }
+    if (J == 1) dof = dof_vel = root_rot;   // no angles: the kernel's unconditional first-element loads get readable memory
+    RTG_TRY(launch_dof_fk_vel(m->topo->view(), m->view(), clip != 0, dof, dof_vel, root_rot, root_t, root_vel, B, g_rot,
+                              g_pos, g_vel, as_stream(stream)),
+            "k_dof_fk_vel");
+    return RTG_OK;
+}
+
 // ---------------------------------------------------------------- gradients of the kinematics
 int rtg_dof_fk_backward_f32(rtg_dof_model_t m, const float *dof, const float *g_rot, const float *grad_g_rot,
                             const float *grad_g_pos, int64_t B, int clip, float *grad_dof, float *grad_root_rot,
@@ -1127,13 +1163,16 @@ int rtg_motion_sample_f32(rtg_topology_t topo, rtg_motion_lib_t lib, const float
     return RTG_OK;
 }
 
-int rtg_dof_motion_sample_f32(rtg_dof_model_t m, rtg_motion_lib_t lib, const float *dof, const float *root_rot,
-                              const float *root_t, const int32_t *clip, const float *time, int64_t N, int flags,
-                              const int32_t *key_links, int32_t K, float *dof_out, float *dof_vel_out,
-                              float *root_rot_out, float *root_t_out, float *root_vel_out, float *g_rot, float *g_pos,
-                              float *key_pos, rtg_stream_t stream)
+// rtg_dof_motion_sample_f32 (g_vel and key_vel nullptr: its checks, its messages, its launch) and
+// rtg_dof_motion_sample_vel_f32 (at least one of the two given) on one checked path
+static int dof_motion_sample(const char *fn, rtg_dof_model_t m, rtg_motion_lib_t lib, const float *dof,
+                             const float *root_rot, const float *root_t, const int32_t *clip, const float *time,
+                             int64_t N, int flags, const int32_t *key_links, int32_t K, float *dof_out,
+                             float *dof_vel_out, float *root_rot_out, float *root_t_out, float *root_vel_out,
+                             float *g_rot, float *g_pos, float *key_pos, float *g_vel, float *key_vel,
+                             rtg_stream_t stream)
 {
-    const char *fn = "rtg_dof_motion_sample_f32";
+    const bool link_vel = g_vel != nullptr || key_vel != nullptr;
     // what does not depend on the handles first: a caller (and a test on a machine without a GPU) sees these reasons
     // whatever the handles are
     if (N < 0) return fail(RTG_ERR_INVALID_ARGUMENT, "%s: N=%lld < 0", fn, (long long)N);
@@ -1153,9 +1192,14 @@ int rtg_dof_motion_sample_f32(rtg_dof_model_t m, rtg_motion_lib_t lib, const flo
             return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both dof_vel_out and root_vel_out or neither", fn);
         if ((g_rot == nullptr) != (g_pos == nullptr))
             return fail(RTG_ERR_INVALID_ARGUMENT, "%s: give both g_rot and g_pos or neither", fn);
-        if ((K > 0) != (key_pos != nullptr))
+        if (link_vel && (K > 0) != (key_pos != nullptr || key_vel != nullptr))
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: key_pos / key_vel go with K > 0 (K=%d, key_pos %s, key_vel %s)",
+                        fn, K, key_pos ? "given" : "NULL", key_vel ? "given" : "NULL");
+        if (!link_vel && (K > 0) != (key_pos != nullptr))
             return fail(RTG_ERR_INVALID_ARGUMENT, "%s: key_pos goes with K > 0 (K=%d, key_pos %s)", fn, K,
                         key_pos ? "given" : "NULL");
+        if (link_vel && !root_vel_out)   // the sweep's tangent inputs are the launch's own velocity rows
+            return fail(RTG_ERR_INVALID_ARGUMENT, "%s: g_vel / key_vel need dof_vel_out and root_vel_out", fn);
         if (!root_rot || !root_t || !clip || !time || !root_rot_out || !root_t_out)
             return fail(RTG_ERR_INVALID_ARGUMENT, "%s: NULL buffer", fn);
     }
@@ -1184,8 +1228,9 @@ int rtg_dof_motion_sample_f32(rtg_dof_model_t m, rtg_motion_lib_t lib, const flo
         const Span outs[] = {{dof_out, n * (j - 1) * 4, "dof_out"}, {dof_vel_out, n * (j - 1) * 4, "dof_vel_out"},
                              {root_rot_out, n * 16, "root_rot_out"}, {root_t_out, n * 12, "root_t_out"},
                              {root_vel_out, n * 24, "root_vel_out"}, {g_rot, n * j * 16, "g_rot"},
-                             {g_pos, n * j * 12, "g_pos"}, {key_pos, n * k * 12, "key_pos"}};
-        RTG_CHECK(check_overlap(fn, outs, 8, in, 5));
+                             {g_pos, n * j * 12, "g_pos"}, {key_pos, n * k * 12, "key_pos"},
+                             {g_vel, n * j * 24, "g_vel"}, {key_vel, n * k * 24, "key_vel"}};
+        RTG_CHECK(check_overlap(fn, outs, 10, in, 5));
     }
     A.dof = dof; A.root_rot = root_rot; A.root_t = root_t;
     A.clip = clip; A.time = time; A.N = N;
@@ -1193,10 +1238,40 @@ int rtg_dof_motion_sample_f32(rtg_dof_model_t m, rtg_motion_lib_t lib, const flo
     A.K = K;
     A.dof_out = dof_out; A.dof_vel_out = dof_vel_out; A.root_rot_out = root_rot_out; A.root_t_out = root_t_out;
     A.root_vel_out = root_vel_out; A.g_rot = g_rot; A.g_pos = g_pos; A.key_pos = key_pos;
+    if (link_vel) {
+        RTG_TRY(launch_dof_motion_sample_vel(m->topo->view(), m->view(), MotionLibView{lib->clips.get(), lib->C},
+                                             (flags & RTG_DOF_MOTION_CLIP) != 0, DofMotionVelArgs{A, g_vel, key_vel},
+                                             as_stream(stream)),
+                "k_dof_motion_sample_vel");
+        return RTG_OK;
+    }
     RTG_TRY(launch_dof_motion_sample(m->topo->view(), m->view(), MotionLibView{lib->clips.get(), lib->C},
                                      (flags & RTG_DOF_MOTION_CLIP) != 0, A, as_stream(stream)),
             "k_dof_motion_sample");
     return RTG_OK;
+}
+
+int rtg_dof_motion_sample_f32(rtg_dof_model_t m, rtg_motion_lib_t lib, const float *dof, const float *root_rot,
+                              const float *root_t, const int32_t *clip, const float *time, int64_t N, int flags,
+                              const int32_t *key_links, int32_t K, float *dof_out, float *dof_vel_out,
+                              float *root_rot_out, float *root_t_out, float *root_vel_out, float *g_rot, float *g_pos,
+                              float *key_pos, rtg_stream_t stream)
+{
+    return dof_motion_sample("rtg_dof_motion_sample_f32", m, lib, dof, root_rot, root_t, clip, time, N, flags,
+                             key_links, K, dof_out, dof_vel_out, root_rot_out, root_t_out, root_vel_out, g_rot, g_pos,
+                             key_pos, nullptr, nullptr, stream);
+}
+
+// with g_vel and key_vel both NULL this is rtg_dof_motion_sample_f32, its messages under its name included
+int rtg_dof_motion_sample_vel_f32(rtg_dof_model_t m, rtg_motion_lib_t lib, const float *dof, const float *root_rot,
+                                  const float *root_t, const int32_t *clip, const float *time, int64_t N, int flags,
+                                  const int32_t *key_links, int32_t K, float *dof_out, float *dof_vel_out,
+                                  float *root_rot_out, float *root_t_out, float *root_vel_out, float *g_rot,
+                                  float *g_pos, float *key_pos, float *g_vel, float *key_vel, rtg_stream_t stream)
+{
+    return dof_motion_sample(g_vel || key_vel ? "rtg_dof_motion_sample_vel_f32" : "rtg_dof_motion_sample_f32", m, lib,
+                             dof, root_rot, root_t, clip, time, N, flags, key_links, K, dof_out, dof_vel_out,
+                             root_rot_out, root_t_out, root_vel_out, g_rot, g_pos, key_pos, g_vel, key_vel, stream);
 }
 
 // ---------------------------------------------------------------- motion-level prep (retarget/main.py)

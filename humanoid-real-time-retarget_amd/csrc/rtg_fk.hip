@@ -273,6 +273,82 @@ __global__ __launch_bounds__(64, 4) void k_dof_fk_group(TopoView T, DofView D, c
     group_store<F>(rot, I.pos, nrec, g_rot + f0 * J * 4, g_pos + f0 * J * 3);
 }
 
+// Link velocities from joint velocities (rtg_dof_fk_vel_f32): k_dof_fk_group's tile with a twist image [F J 6] behind
+// FkImages (24 F J bytes more: Hu v5 at F = 16, 11.6 KiB) and group_compose_vel's tangent sweep in place of the
+// compose.  The tile's joint velocities are loaded with its angles (the same row shape); after the table fill each
+// one goes, through the clip select, into the first float of its joint's twist row, where it waits for the joint's
+// step; the root twists (6 nfr consecutive floats, +0 without root_vel) are preset like the root poses.  The twist
+// rows leave as consecutive 16-byte pieces (a tile's rows start 16-byte aligned when g_vel does: F is a multiple of
+// 8); g_rot / g_pos leave as in k_dof_fk_group, or not at all (nullptr: the velocity-only call, the same g_vel).
+struct FkVelImages {
+    FkImages fk;
+    float *tw;       // [F J 6] the twists {v, w}
+    size_t floats;
+    __host__ __device__ FkVelImages(float *base, int J, int F, int steps) : fk(base, J, F, steps, true)
+    {
+        tw = base ? base + fk.floats : nullptr;
+        floats = fk.floats + pad16f((size_t)6 * F * J);
+    }
+};
+template <bool CLIP, int F>
+__global__ __launch_bounds__(64, 4) void k_dof_fk_vel_group(TopoView T, DofView D, const float *__restrict__ dof,
+                                                         const float *__restrict__ dof_vel,
+                                                         const float *__restrict__ root_rot,
+                                                         const float *__restrict__ root_t,
+                                                         const float *__restrict__ root_vel, int64_t B,
+                                                         float *__restrict__ g_rot, float *__restrict__ g_pos,
+                                                         float *__restrict__ g_vel)
+{
+    extern __shared__ __attribute__((aligned(16))) float fk_lds[];
+    using G = Grp<F>;
+    const int J = T.J, lane = (int)threadIdx.x, nd = J - 1;
+    const int64_t f0 = (int64_t)blockIdx.x * F;
+    const int nfr = tile_frames<F>(B, f0), nrec = nfr * J, nang = nfr * nd;
+    const FkVelImages IV(fk_lds, J, F, T.gsteps);
+    const FkImages &I = IV.fk;
+    f4v *rot = I.rot;
+    float *tw = IV.tw;
+    const f4v *ntab = I.ntab;
+    const UnitEnt *utab = I.utab;
+    ScalarRows<F> a, ad;
+    a.load(dof + f0 * nd, nang);
+    ad.load(dof_vel + f0 * nd, nang);
+    const f4v rr = root_rot_load(root_rot, f0, nfr);
+    const float rt = root_t_load(root_t, f0, nfr);
+    float rw[2] = {0.0f, 0.0f};   // the root twists: float 64 k + lane of the tile's 6 nfr (F <= 16: two pieces)
+    if (root_vel) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) rw[k] = root_vel[f0 * 6 + (64 * k + lane < 6 * nfr ? 64 * k + lane : 0)];
+    }
+    group_sched_fill(T, G::L, I.sch);
+    if (kUnitTab) unit_tab_fill(I.utab, (int)threadIdx.x);
+    joint_tab_fill<CLIP, false>(D, J, I.ntab);
+    root_preset(rot, I.pos, J, nfr, rr, rt);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int i = 64 * k + lane, fr = i / 6;
+        if (i < 6 * nfr) tw[6 * J * fr + (i - 6 * fr)] = rw[k];
+    }
+    wave_sync();
+    const float rnd = item_rcp(nd > 0 ? nd : 1);
+    lane_items<G::NR>([&](int k, int i) {   // the rates into their joints' twist rows
+        if (i < nang) {
+            const Item it = item_split(i, rnd, nd);
+            tw[6 * (it.fr * J + it.j + 1)] = joint_rate<CLIP>(a.v[k], ad.v[k], ntab[it.j + 1]);
+        }
+    });
+    const DofRotations<CLIP, F> rotations{a, ntab, utab, rot, J, nd, nang, lane, rnd};
+    constexpr int NW = RTG_DOF_NWAY, NFULL = G::NR - G::NR % NW;
+#pragma unroll
+    for (int k = 0; k < NFULL; k += NW) rotations(std::integral_constant<int, NW>{}, k);
+#pragma unroll
+    for (int k = NFULL; k < G::NR; ++k) rotations(std::integral_constant<int, 1>{}, k);
+    wave_sync();
+    group_compose_vel<F>(T, rot, I.pos, tw, I.sch, ntab, nfr, utab);
+    if (g_rot) group_store<F>(rot, I.pos, nrec, g_rot + f0 * J * 4, g_pos + f0 * J * 3);
+    PosRows<F>::out(tw, g_vel + f0 * J * 6, 6 * nrec);
+}
+
 // Mixed-target kinematics on the lane groups (config 5): a block is one tile of one segment; the segment's F comes
 // from its topology
 __global__ __launch_bounds__(64, 4) void k_fk_multi_group(FkMultiArgs A)
@@ -385,6 +461,20 @@ hipError_t launch_dof_fk(const TopoView &T, const DofView &D, bool clip, const f
         hipLaunchKernelGGL(k_dof_fk_walk<false>, dim3(grid_for(B, 256)), dim3(256), 0, s, T, D, dof, root_rot, root_t, B,
                            gr, gp);
     }
+    return hipGetLastError();
+}
+
+// lane groups only (T.gsched); g_rot / g_pos both nullptr: the velocity-only call
+hipError_t launch_dof_fk_vel(const TopoView &T, const DofView &D, bool clip, const float *dof, const float *dof_vel,
+                             const float *root_rot, const float *root_t, const float *root_vel, int64_t B, float *gr,
+                             float *gp, float *gv, hipStream_t s)
+{
+    const int F = T.gF;
+    const size_t lds = sizeof(float) * FkVelImages(nullptr, T.J, F, T.gsteps).floats;
+    group_dispatch(F, [&](auto f, auto cl) {
+        hipLaunchKernelGGL((k_dof_fk_vel_group<cl(), f()>), dim3(grid_for(B, F)), dim3(64), lds, s, T, D, dof, dof_vel,
+                           root_rot, root_t, root_vel, B, gr, gp, gv);
+    }, clip);
     return hipGetLastError();
 }
 

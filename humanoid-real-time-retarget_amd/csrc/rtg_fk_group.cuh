@@ -4,7 +4,8 @@
 // LDS images (the layout comment in rtg_fk.hip).  The parts: the LDS carve (LdsCarve: a kernel and its launcher call
 // the same carve function), the row movers (LaneRows as GroupRows: float4 records, and ScalarRows: scalars; PosRows:
 // position rows), the table fills, the root preset, the reverse sweep's child pull, the FK tile itself (FkImages,
-// group_compose, group_store: rtg_fk.hip and rtg_motion_sample.hip), the joint-angle model's rotations (joint_rot_n,
+// group_compose, group_store: rtg_fk.hip and rtg_motion_sample.hip; group_compose_vel, joint_rate: the same tile with a
+// twist per link, the same two), the joint-angle model's rotations (joint_rot_n,
 // DofRotations: the same two), the item split, the Q <-> f4v converters, the
 // straight-through clamp and the launch dispatch.  The multi-wave tile of rtg_rot_ingest.hip takes only the
 // converters and the item split.
@@ -401,6 +402,61 @@ RTG_DEV void group_compose(const TopoView &T, f4v *rot, float *pos, const GEnt *
         }
         wave_sync();   // this step's records before the next step's parent reads (other lanes)
     }
+}
+
+// The same steps for the joint-angle model with a twist per link (rtg_dof_fk_vel_f32, rtg_dof_motion_sample_vel_f32):
+// the forward-mode counterpart of rtg_fk_grad.hip's reverse sweep.  tw: [F J 6] {v (3), w (3)}, world frame; the root's
+// row preset to the root twist, row j >= 1 holding the joint's rate s in its first float until its step (the clip
+// select already applied).  Joint j with parent p, every operation one rounding (the TUs that use this are built with
+// -ffp-contract=off):
+//   r = qrotate(G_p, l_j) -- the value FK adds to P_p;  c = w_p x r, each component (product) - (product);
+//   v_j = v_p + c;  u = qrotate(G_j, e_j), G_j the joint's own global rotation;  w_j = w_p + (u * s).
+// rot / pos get exactly group_compose's values (the same device functions on the same operands in the same order; the
+// root's records are already in place, so its entry is passed over).  A function of its own: group_compose is shared
+// by five TUs and stays what it compiles to.
+template <int F>
+RTG_DEV void group_compose_vel(const TopoView &T, f4v *rot, float *pos, float *tw, const GEnt *sch, const f4v *ntab,
+                               int nfr, const UnitEnt *utab)
+{
+    using G = Grp<F>;
+    const int J = T.J, lane = (int)threadIdx.x;
+    const int fr = lane >> G::LOG_L, sub = lane & (G::L - 1);
+    const bool live = fr < nfr;
+    const int base = fr * J;
+    for (int s = 0; s < T.gsteps; ++s) {
+        const GEnt e = sch[s * G::L + sub];
+        const int j = e.code & 0xFF, p = (e.code >> 8) & 0xFF;
+        if (live && j != 0xFF && j != 0) {
+            const Q lq = q_of(rot[base + j]);
+            const Q g = q_of(rot[base + p]);
+            const float *tp = pos + 3 * (base + p);
+            const V t{tp[0], tp[1], tp[2]};
+            const V rv = qrotate(g, V{e.lx, e.ly, e.lz});
+            const Q ng = qmul_norm(g, lq, fk_tab(utab));
+            const V nt = V{rv.x + t.x, rv.y + t.y, rv.z + t.z};
+            const float *wp = tw + 6 * (base + p);
+            float *wj = tw + 6 * (base + j);
+            const V vp{wp[0], wp[1], wp[2]}, w{wp[3], wp[4], wp[5]};
+            const float rate = wj[0];
+            const int ax = __float_as_int(ntab[j].x);
+            const V u = qrotate(ng, V{ax == 0 ? 1.0f : 0.0f, ax == 1 ? 1.0f : 0.0f, ax == 2 ? 1.0f : 0.0f});
+            const V c{(w.y * rv.z) - (w.z * rv.y), (w.z * rv.x) - (w.x * rv.z), (w.x * rv.y) - (w.y * rv.x)};
+            rot[base + j] = v_of(ng);
+            float *op = pos + 3 * (base + j);
+            op[0] = nt.x; op[1] = nt.y; op[2] = nt.z;
+            wj[0] = vp.x + c.x; wj[1] = vp.y + c.y; wj[2] = vp.z + c.z;
+            wj[3] = w.x + (u.x * rate); wj[4] = w.y + (u.y * rate); wj[5] = w.z + (u.z * rate);
+        }
+        wave_sync();   // this step's records before the next step's parent reads (other lanes)
+    }
+}
+// a joint's rate as the sweep takes it: with CLIP a joint whose angle lies outside its limits does not turn (the twist
+// is the derivative of the pose put out, not the optimiser's straight-through gradient); a NaN angle and an angle
+// exactly at a limit keep the rate
+template <bool CLIP>
+RTG_DEV float joint_rate(float angle, float rate, f4v tab)
+{
+    return CLIP && (angle < tab.y || angle > tab.z) ? 0.0f : rate;
 }
 
 // the tile image out: rotations record-ordered, positions as consecutive pieces (PosRows)

@@ -89,6 +89,11 @@ hipError_t launch_local_rotation(const TopoView &T, bool state, const float *g, 
 hipError_t launch_fk_multi(FkMultiArgs &A, hipStream_t s);
 hipError_t launch_dof_fk(const TopoView &T, const DofView &D, bool clip, const float *dof, const float *root_rot,
                          const float *root_t, int64_t B, float *gr, float *gp, hipStream_t s);
+// rtg_dof_fk_vel_f32: launch_dof_fk with the tangent sweep (link twists gv (B,J,6) from the joint velocities and the
+// root twist; root_vel nullptr: zero).  Lane groups only (T.gsched); gr / gp both nullptr: velocities only
+hipError_t launch_dof_fk_vel(const TopoView &T, const DofView &D, bool clip, const float *dof, const float *dof_vel,
+                             const float *root_rot, const float *root_t, const float *root_vel, int64_t B, float *gr,
+                             float *gp, float *gv, hipStream_t s);
 // the adjoints of launch_dof_fk / launch_fk (rtg_fk_grad.hip); lq_in: the joint angles (B,J-1) when D, else the local
 // rotations (B,J,4); lq_grad: their gradient rows; either upstream gradient and any output may be nullptr
 hipError_t launch_fk_backward(const TopoView &T, const DofView *D, bool clip, const float *lq_in, const float *g_rot,
@@ -272,6 +277,15 @@ struct DofMotionArgs {
 // lane groups only (T.gsched); the forward kinematics runs iff g_rot or key_pos is given
 hipError_t launch_dof_motion_sample(const TopoView &T, const DofView &D, const MotionLibView &L, bool clip,
                                     const DofMotionArgs &A, hipStream_t s);
+// rtg_dof_motion_sample_vel_f32: the same launch with the link twists of the sampled state (g_vel (N,J,6) and / or
+// key_vel (N,K,6), at least one given; A.dof_vel_out / A.root_vel_out are then given too).  The forward kinematics
+// always runs
+struct DofMotionVelArgs {
+    DofMotionArgs A;
+    float *g_vel, *key_vel;
+};
+hipError_t launch_dof_motion_sample_vel(const TopoView &T, const DofView &D, const MotionLibView &L, bool clip,
+                                        const DofMotionVelArgs &A, hipStream_t s);
 hipError_t launch_rescale_motion(const TopoView &T, const float *motion, int64_t B, const float *dir, float *out,
                                  hipStream_t s);
 hipError_t launch_quat_between(const float *v1, const float *v2, int64_t n, float *out, float *ws, hipStream_t s);

@@ -213,8 +213,9 @@ struct DmImages {
     float *pos;      // FK: [F J 3] the positions, the root's preset
     GEnt *sch;       // FK: [gsteps L] the schedule
     f4v *ntab;       // FK: [J] the per-joint {axis, lower, upper} table
+    float *tw;       // VEL: [F J 6] the twists {v, w}
     size_t floats;
-    __host__ __device__ DmImages(float *base, int J, int F, int steps, bool fk)
+    __host__ __device__ DmImages(float *base, int J, int F, int steps, bool fk, bool vel = false)
     {
         LdsCarve c(base);
         qt = c.take<MsQuery>((size_t)F);
@@ -226,6 +227,7 @@ struct DmImages {
         pos = c.take<float>(fk ? (size_t)3 * F * J : 0);
         sch = c.take<GEnt>(fk ? (size_t)steps * (64 / F) : 0);
         ntab = c.take<f4v>(fk ? J : 0);
+        tw = c.take<float>(vel ? (size_t)6 * F * J : 0);
         floats = c.floats;
     }
 };
@@ -375,6 +377,161 @@ __global__ __launch_bounds__(64, 4) void k_dof_motion_sample(TopoView T, DofView
     }
 }
 
+// rtg_dof_motion_sample_vel_f32: k_dof_motion_sample with the FK always on, a twist image [F J 6] behind the others and
+// group_compose_vel's tangent sweep as step 4.  The rate of each joint is the launch's own dof_vel_out value, through
+// the clip select on its dof_out value, stored into its joint's twist row in step 3; the root twist is root_vel_out's
+// row (step 2); g_vel leaves as consecutive 16-byte pieces and key_vel is gathered from the image like key_pos.  A
+// kernel of its own and not a template argument of k_dof_motion_sample: with the body shared (one tile function, both
+// ways of passing the arguments tried) the device listings of the existing instantiations moved.
+template <int F, bool CLIP>
+__global__ __launch_bounds__(64, 4) void k_dof_motion_sample_vel(TopoView T, DofView D, MotionLibView L,
+                                                              DofMotionVelArgs AV)
+{
+    extern __shared__ __attribute__((aligned(16))) float ms_lds[];
+    const DofMotionArgs &A = AV.A;
+    float *const g_vel = AV.g_vel, *const key_vel = AV.key_vel;
+    using G = Grp<F>;
+    const int J = T.J, nd = J - 1, lane = (int)threadIdx.x;
+    const int64_t f0 = (int64_t)blockIdx.x * F;
+    const int nfr = tile_frames<F>(A.N, f0), nrec = nfr * J, nang = nfr * nd;
+    const DmImages I(ms_lds, J, F, T.gsteps, true, true);   // (dof_vel_out and root_vel_out are always given here)
+
+    // 1. the query table
+    if (lane < F) {
+        const int64_t n = lane < nfr ? f0 + lane : 0;
+        const int32_t clip = A.clip[n];
+        const float time = A.time[n];
+        const bool valid = motion_clip_valid(clip, L.C);
+        const MotionClip ce = L.clips[valid ? clip : 0];
+        const MotionIdx ix = motion_index(time, ce.fps, ce.len);
+        I.qt[lane] = valid ? MsQuery{(int32_t)(ce.start + ix.i0), (int32_t)(ce.start + ix.i1), ix.b, 1}
+                           : MsQuery{0, 0, 0.0f, 0};
+        I.dt[lane] = (float)(1.0 / (double)ce.fps);
+    }
+    group_sched_fill(T, G::L, I.sch);
+    joint_tab_fill<CLIP, false>(D, J, I.ntab);
+    if (kUnitTab) unit_tab_fill(I.utab, lane);
+    wave_sync();
+
+    // 2. the roots (a lane past the tile's queries holds query 0 and stores nothing)
+    if (lane < F) {
+        const MsQuery q = I.qt[lane];
+        const float dt = I.dt[lane];
+        const f4v *rr = reinterpret_cast<const f4v *>(A.root_rot);
+        const Q r0 = q_of(rr[q.row0]), r1 = q_of(rr[q.row1]);
+        const V t0 = ld3(A.root_t + (int64_t)q.row0 * 3), t1 = ld3(A.root_t + (int64_t)q.row1 * 3);
+        Q r = qslerp(r0, r1, q.b);
+        if (A.normalize) r = qnormalize(r, fk_tab(I.utab));
+        float t[3] = {ms_blend(t0.x, t1.x, q.b), ms_blend(t0.y, t1.y, q.b), ms_blend(t0.z, t1.z, q.b)};
+        // skeleton3d.py:1137-1146 on the pair: k_angular_raw's expression (rtg_ops.hip)
+        const Q aa = qangle_axis_abs(qmul_norm(r1, qconj(r0)));
+        float w[6] = {(t1.x - t0.x) / dt, (t1.y - t0.y) / dt, (t1.z - t0.z) / dt,
+                      (aa.y * aa.x) / dt, (aa.z * aa.x) / dt,  (aa.w * aa.x) / dt};
+        f4v rv = v_of(r);
+        if (!q.valid) {
+            rv = f4v{ms_nan(), ms_nan(), ms_nan(), ms_nan()};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) t[c] = ms_nan();
+#pragma unroll
+            for (int c = 0; c < 6; ++c) w[c] = ms_nan();
+        }
+        if (lane < nfr) {
+            reinterpret_cast<f4v *>(A.root_rot_out)[f0 + lane] = rv;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) I.rt[3 * lane + c] = t[c];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) I.rv[6 * lane + c] = I.tw[6 * J * lane + c] = w[c];   // the root twist
+            I.rot[lane * J] = rv;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) I.pos[3 * J * lane + c] = t[c];
+        }
+    }
+    const bool any_invalid = __builtin_amdgcn_ballot_w64(lane < nfr && !I.qt[lane < nfr ? lane : 0].valid) != 0;
+
+    // 3. the angles: element i = (query, dof)
+    ScalarRows<F> x;
+    {
+        const float rnd = item_rcp(nd > 0 ? nd : 1);
+        float a0[G::NR], a1[G::NR];
+#pragma unroll
+        for (int k = 0; k < G::NR; ++k) {
+            a0[k] = a1[k] = 0.0f;
+            if (k * 64 >= nang) continue;   // wave-uniform: no lane has an angle in this piece
+            const int i = k * 64 + lane;
+            const Item it = item_split(i < nang ? i : 0, rnd, nd);   // a lane past the angles repeats angle 0
+            const MsQuery q = I.qt[it.fr];
+            a0[k] = A.dof[(int64_t)q.row0 * nd + it.j];
+            a1[k] = A.dof[(int64_t)q.row1 * nd + it.j];
+        }
+#pragma unroll
+        for (int k = 0; k < G::NR; ++k) {
+            x.v[k] = 0.0f;
+            if (k * 64 >= nang) continue;
+            const int i = k * 64 + lane;
+            const Item it = item_split(i < nang ? i : 0, rnd, nd);
+            const MsQuery q = I.qt[it.fr];
+            x.v[k] = ms_blend(a0[k], a1[k], q.b);   // (an invalid query's angles stay finite for the FK: its rows are
+            if (i < nang) {                         // overwritten below)
+                A.dof_out[f0 * nd + i] = q.valid ? x.v[k] : ms_nan();
+                const float xd = (a1[k] - a0[k]) / I.dt[it.fr];
+                A.dof_vel_out[f0 * nd + i] = q.valid ? xd : ms_nan();
+                // dof_vel_out's value through the clip select on dof_out's, into the joint's twist row
+                I.tw[6 * (it.fr * J + it.j + 1)] = joint_rate<CLIP>(x.v[k], xd, I.ntab[it.j + 1]);
+            }
+        }
+    }
+
+    // the root translations and velocities out, lane = 3 query + component
+    wave_sync();
+    if (lane < 3 * nfr) A.root_t_out[f0 * 3 + lane] = I.rt[lane];
+    for (int i = lane; i < 6 * nfr; i += 64) A.root_vel_out[f0 * 6 + i] = I.rv[i];
+
+    // 4. forward kinematics and the tangent sweep of the blended angles on the launch's own roots
+    {
+        const float rnd = item_rcp(nd > 0 ? nd : 1);
+        const DofRotations<CLIP, F> rotations{x, I.ntab, I.utab, I.rot, J, nd, nang, lane, rnd};
+        constexpr int NW = RTG_DOF_NWAY, NFULL = G::NR - G::NR % NW;
+#pragma unroll
+        for (int k = 0; k < NFULL; k += NW) rotations(std::integral_constant<int, NW>{}, k);
+#pragma unroll
+        for (int k = NFULL; k < G::NR; ++k) rotations(std::integral_constant<int, 1>{}, k);
+        wave_sync();
+        group_compose_vel<F>(T, I.rot, I.pos, I.tw, I.sch, I.ntab, nfr, I.utab);
+        if (any_invalid) {   // wave-uniform
+            const float rJ = item_rcp(J);
+            const f4v nan4{ms_nan(), ms_nan(), ms_nan(), ms_nan()};
+            for (int rec = lane; rec < nrec; rec += 64) {
+                const Item it = item_split(rec, rJ, J);
+                if (!I.qt[it.fr].valid) {
+                    I.rot[rec] = nan4;
+                    I.pos[3 * rec] = I.pos[3 * rec + 1] = I.pos[3 * rec + 2] = ms_nan();
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) I.tw[6 * rec + c] = ms_nan();
+                }
+            }
+            wave_sync();
+        }
+        if (A.g_rot) group_store<F>(I.rot, I.pos, nrec, A.g_rot + f0 * J * 4, A.g_pos + f0 * J * 3);
+        if (A.key_pos) {   // element e = (query, key link, component): consecutive floats of the output
+            const int K3 = 3 * A.K, n = nfr * K3;
+            float *o = A.key_pos + f0 * K3;
+            for (int e = lane; e < n; e += 64) {
+                const int fr = e / K3, r = e - fr * K3, k = r / 3;
+                o[e] = I.pos[3 * (fr * J + (int)A.key[k]) + (r - 3 * k)];
+            }
+        }
+        if (g_vel) PosRows<F>::out(I.tw, g_vel + f0 * J * 6, 6 * nrec);
+        if (key_vel) {   // element e = (query, key link, component)
+            const int K6 = 6 * A.K, n = nfr * K6;
+            float *o = key_vel + f0 * K6;
+            for (int e = lane; e < n; e += 64) {
+                const int fr = e / K6, r = e - fr * K6, k = r / 6;
+                o[e] = I.tw[6 * (fr * J + (int)A.key[k]) + (r - 6 * k)];
+            }
+        }
+    }
+}
+
 hipError_t launch_dof_motion_sample(const TopoView &T, const DofView &D, const MotionLibView &L, bool clip,
                                     const DofMotionArgs &A, hipStream_t s)
 {
@@ -384,6 +541,17 @@ hipError_t launch_dof_motion_sample(const TopoView &T, const DofView &D, const M
     group_dispatch(F, [&](auto f, auto cl, auto k) {
         hipLaunchKernelGGL((k_dof_motion_sample<f(), cl(), k()>), dim3(grid_for(A.N, F)), dim3(64), lds, s, T, D, L, A);
     }, clip && fk, fk);
+    return hipGetLastError();
+}
+
+hipError_t launch_dof_motion_sample_vel(const TopoView &T, const DofView &D, const MotionLibView &L, bool clip,
+                                        const DofMotionVelArgs &A, hipStream_t s)
+{
+    const int F = T.gF;
+    const size_t lds = sizeof(float) * DmImages(nullptr, T.J, F, T.gsteps, true, true).floats;
+    group_dispatch(F, [&](auto f, auto cl) {
+        hipLaunchKernelGGL((k_dof_motion_sample_vel<f(), cl()>), dim3(grid_for(A.A.N, F)), dim3(64), lds, s, T, D, L, A);
+    }, clip);
     return hipGetLastError();
 }
 

@@ -80,6 +80,29 @@ class HuForwardModel(BaseForwardModel):
                                                   motion_root_translation, clip=bool(clip_angles))
         return g_rot.to(dev), g_pos.to(dev)
 
+    def link_velocities(self, angles, root_translation, root_rotation, joint_velocities, root_velocity=None,
+                        root_angular_velocity=None, clip_angles=False):
+        """Not in the reference's forward model; what its SkeletonMotion carries (skeleton3d.py:1026-1146) from joint
+        velocities instead of finite differences: (L, J-1, 1) or (L, J-1) angles and joint velocities, (L, 3) root
+        translation, (L, 1, 4) root rotation and the root's world-frame linear and angular velocity (L, 3) each (None:
+        zero) -> (global_velocity (L, J, 3), global_angular_velocity (L, J, 3)), world frame, in one launch
+        (ops.dof_link_velocity).  With ``clip_angles`` a joint whose angle lies outside its limits does not turn."""
+        if clip_angles and not self._model.has_limits:
+            raise ValueError("clip_angles needs DOF limits with one entry per DOF")
+        dev = home_device(angles, root_translation, root_rotation)
+        root_vel = None
+        if root_velocity is not None or root_angular_velocity is not None:
+            v, w = (None if x is None else torch.as_tensor(x, dtype=torch.float32)
+                    for x in (root_velocity, root_angular_velocity))
+            ref = v if v is not None else w
+            if tuple(ref.shape[-1:]) != (3,) or (v is not None and w is not None and v.shape != w.shape):
+                raise ValueError("root_velocity / root_angular_velocity must be (L, 3) each")
+            root_vel = torch.cat([torch.zeros_like(ref) if v is None else v,
+                                  torch.zeros_like(ref) if w is None else w.to(ref.device)], dim=-1)
+        _, _, g_vel = ops.dof_link_velocity(self._model, angles, root_rotation, root_translation, joint_velocities,
+                                            root_vel, clip=bool(clip_angles), want_pose=False)
+        return g_vel[..., :3].to(dev), g_vel[..., 3:].to(dev)
+
     def motion_library(self, clips):
         """``rtg.motion.DofMotionLibrary(self, clips)``: fitted clips -- (angles, root translation, root rotation, fps)
         tuples, fit_pose's first three results in its order -- packed for sampling at arbitrary times."""

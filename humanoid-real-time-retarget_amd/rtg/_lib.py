@@ -128,6 +128,7 @@ SIGNATURES = {
     "rtg_quat_between_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "rtg_rebuild_vtrdyn_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rtg_dof_fk_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "rtg_dof_fk_vel_f32": (c_int, [c_void_p] * 6 + [c_int64, c_int] + [c_void_p] * 4),
     "rtg_dof_fk_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
     "rtg_fk_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
@@ -174,6 +175,8 @@ SIGNATURES = {
     "rtg_motion_sample_f32": (c_int, [c_void_p] * 5 + [c_int32, c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 6),
     # (key_links is a host pointer: K int32 values read during the call)
     "rtg_dof_motion_sample_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int, POINTER(c_int32), c_int32] + [c_void_p] * 9),
+    "rtg_dof_motion_sample_vel_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int, POINTER(c_int32), c_int32] +
+                                      [c_void_p] * 11),
     "rtg_solver_create": (c_int, [c_int, POINTER(c_float), POINTER(c_float), POINTER(c_int32), c_int32, c_int,
                                   POINTER(c_void_p)]),
     "rtg_solver_destroy": (c_int, [c_void_p]),

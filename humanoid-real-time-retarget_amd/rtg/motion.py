@@ -128,7 +128,10 @@ class MotionLibrary:
 class DofMotionSample:
     """What ``DofMotionLibrary.sample`` returns, device tensors: dof_pos / dof_vel (N, J-1), root_translation /
     root_velocity / root_angular_velocity (N, 3), root_rotation (N, 4), global_rotation (N, J, 4), global_translation
-    (N, J, 3), key_translation (N, K, 3); the parts not asked for are None."""
+    (N, J, 3), key_translation (N, K, 3); the parts not asked for are None.  With ``link_velocities`` the sample also
+    carries global_velocity / global_angular_velocity (N, J, 3) and key_velocity / key_angular_velocity (N, K, 3), world
+    frame: plain attributes that default to None, set after construction, so that the dataclass's fields -- and every
+    positional construction -- stay what they were."""
     dof_pos: torch.Tensor
     root_translation: torch.Tensor
     root_rotation: torch.Tensor
@@ -138,6 +141,10 @@ class DofMotionSample:
     global_rotation: Optional[torch.Tensor] = None
     global_translation: Optional[torch.Tensor] = None
     key_translation: Optional[torch.Tensor] = None
+    global_velocity = None            # (not annotated: not dataclass fields, see above)
+    global_angular_velocity = None
+    key_velocity = None
+    key_angular_velocity = None
 
 
 def _rows(x, width: int, squeeze_axis: int):
@@ -233,19 +240,33 @@ class DofMotionLibrary:
         return out
 
     def sample(self, clip_ids, times, key_links=None, want_velocity: bool = True, want_global: bool = True,
-               normalize: bool = True, clip_angles: bool = False) -> DofMotionSample:
+               normalize: bool = True, clip_angles: bool = False, link_velocities: bool = False) -> DofMotionSample:
         """The library's states at ``times`` (seconds from the first frame of clip ``clip_ids[n]``; clamped to the
         clip, no wrap-around) in one launch.  ``key_links``: up to 32 node names or joint indices whose positions come
         back as ``key_translation`` (also with ``want_global=False``, which skips the full link poses).
         ``want_velocity``: the forward differences of the bracketing frames (DOF and root linear velocity) and the
         pair's angular velocity.  ``normalize``: ``quat_normalize`` after the root rotation's slerp.  ``clip_angles``:
-        the link poses from the angles clamped to the model's limits.  A clip id outside 0..num_clips-1 gives NaN
-        rows."""
+        the link poses from the angles clamped to the model's limits.  ``link_velocities`` (needs ``want_velocity``):
+        the world-frame linear and angular velocity of every link (``global_velocity``, ``global_angular_velocity``,
+        with ``want_global``) and of the key links (``key_velocity``, ``key_angular_velocity``), from the sampled joint
+        and root velocities in the same launch; with ``clip_angles`` a joint held at a limit does not turn.  A clip id
+        outside 0..num_clips-1 gives NaN rows."""
         if clip_angles and not self.model.has_limits:
             raise ValueError("clip_angles needs DOF limits with one entry per DOF")
+        if link_velocities and not want_velocity:
+            raise ValueError("link_velocities needs want_velocity: the link velocities come from the sampled joint and "
+                             "root velocities")
+        keys = self._link_indices(key_links)
         r = ops.dof_motion_sample(self.model, self._lib, self.dof, self.root_rot, self.root_t, clip_ids, times,
                                   normalize=normalize, clip=clip_angles, want_velocity=want_velocity,
-                                  want_global=want_global, key_links=self._link_indices(key_links))
+                                  want_global=want_global, key_links=keys,
+                                  want_link_velocity=bool(link_velocities and want_global),
+                                  want_key_velocity=bool(link_velocities and keys))
         rv = r.root_vel
-        return DofMotionSample(r.dof, r.root_t, r.root_rot, r.dof_vel, None if rv is None else rv[:, :3],
-                               None if rv is None else rv[:, 3:], r.g_rot, r.g_pos, r.key_pos)
+        out = DofMotionSample(r.dof, r.root_t, r.root_rot, r.dof_vel, None if rv is None else rv[:, :3],
+                              None if rv is None else rv[:, 3:], r.g_rot, r.g_pos, r.key_pos)
+        if r.g_vel is not None:
+            out.global_velocity, out.global_angular_velocity = r.g_vel[..., :3], r.g_vel[..., 3:]
+        if r.key_vel is not None:
+            out.key_velocity, out.key_angular_velocity = r.key_vel[..., :3], r.key_vel[..., 3:]
+        return out

@@ -343,25 +343,36 @@ def motion_sample(topo: Topology, mlib: MotionLib, rot, root_t, clip_ids, times,
 
 
 # what dof_motion_sample returns, device tensors: dof (N, J-1), dof_vel (N, J-1), root_rot (N, 4), root_t (N, 3),
-# root_vel (N, 6) {linear, angular}, g_rot (N, J, 4), g_pos (N, J, 3), key_pos (N, K, 3); the parts not asked for are None
+# root_vel (N, 6) {linear, angular}, g_rot (N, J, 4), g_pos (N, J, 3), key_pos (N, K, 3), g_vel (N, J, 6) and key_vel
+# (N, K, 6) {linear, angular}; the parts not asked for are None
 DofMotionSampleResult = collections.namedtuple("DofMotionSampleResult",
-                                               "dof dof_vel root_rot root_t root_vel g_rot g_pos key_pos")
+                                               "dof dof_vel root_rot root_t root_vel g_rot g_pos key_pos g_vel key_vel",
+                                               defaults=(None, None))
 
 
 def dof_motion_sample(model, mlib: MotionLib, dof, root_rot, root_t, clip_ids, times, normalize: bool = False,
-                      clip: bool = False, want_velocity: bool = True, want_global: bool = True, key_links=None):
+                      clip: bool = False, want_velocity: bool = True, want_global: bool = True, key_links=None,
+                      want_link_velocity: bool = False, want_key_velocity: bool = False):
     """Sample a library of joint-angle clips at (clip, time) pairs in one launch (rtg.h rtg_dof_motion_sample_f32): per
     query the two frames around ``time * fps`` of its clip, torch's ``(1 - b) * a + b * c`` on the joint angles and the
     root translation, ``quat_slerp`` of the root rotation (``quat_normalize`` after it with ``normalize``), with
     ``want_velocity`` the forward differences of the bracketing frames over the frame time (joint velocities, root
     linear velocity) and SkeletonMotion's unfiltered angular velocity of the root pair, with ``want_global`` the
     forward kinematics of the blended angles (clamped to the model's limits with ``clip``), and with ``key_links`` (up
-    to 32 joint indices, repeats allowed) those links' positions alone.
+    to 32 joint indices, repeats allowed) those links' positions alone.  ``want_link_velocity`` adds every link's
+    world-frame twist {linear, angular} as ``g_vel`` (N, J, 6) -- rtg.h rtg_dof_fk_vel_f32's rule on the launch's own
+    angles, joint velocities and root twist -- and ``want_key_velocity`` the key links' as ``key_vel`` (N, K, 6); both
+    need ``want_velocity``, and neither needs ``want_global``.
 
     dof (F_total, J-1), root_rot (F_total, 4) and root_t (F_total, 3) are the library's packed arrays, clip_ids (N)
     int32 and times (N) float32 the queries.  Returns a DofMotionSampleResult on the device.  A query whose clip id is
     outside 0..C-1 gives NaN rows.  Raises RtgError without a GPU: there is no CPU fallback."""
     import numpy as np
+    if (want_link_velocity or want_key_velocity) and not want_velocity:
+        raise ValueError("want_link_velocity / want_key_velocity need want_velocity: the link velocities come from the "
+                         "sampled joint and root velocities")
+    if want_key_velocity and (key_links is None or len(key_links) == 0):
+        raise ValueError("want_key_velocity needs key_links")
     dev = require_gpu_rtg()
     nd, Ft = model.num_dofs, mlib.total_frames
     J = nd + 1
@@ -398,7 +409,15 @@ def dof_motion_sample(model, mlib: MotionLib, dof, root_rot, root_t, clip_ids, t
     o_dv, o_rv = (out(nd), out(6)) if want_velocity else (None, None)
     g_rot, g_pos = (out(J, 4), out(J, 3)) if want_global else (None, None)
     key_pos = out(K, 3) if K else None
+    g_vel = out(J, 6) if want_link_velocity else None
+    key_vel = out(K, 6) if want_key_velocity else None
     flags = (_lib.DOF_MOTION_NORMALIZE if normalize else 0) | (_lib.DOF_MOTION_CLIP if clip else 0)
+    if g_vel is not None or key_vel is not None:
+        check(lib().rtg_dof_motion_sample_vel_f32(
+            model.handle, mlib.handle, ptr(d), ptr(rr), ptr(rt), ptr(c), ptr(tm), N, flags,
+            keys.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if K else None, K, ptr(o_dof), ptr(o_dv), ptr(o_rr),
+            ptr(o_rt), ptr(o_rv), ptr(g_rot), ptr(g_pos), ptr(key_pos), ptr(g_vel), ptr(key_vel), stream_handle()))
+        return DofMotionSampleResult(o_dof, o_dv, o_rr, o_rt, o_rv, g_rot, g_pos, key_pos, g_vel, key_vel)
     check(lib().rtg_dof_motion_sample_f32(model.handle, mlib.handle, ptr(d), ptr(rr), ptr(rt), ptr(c), ptr(tm), N, flags,
                                           keys.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if K else None, K,
                                           ptr(o_dof), ptr(o_dv), ptr(o_rr), ptr(o_rt), ptr(o_rv), ptr(g_rot), ptr(g_pos),
@@ -426,6 +445,53 @@ def dof_forward_kinematics(model, dof, root_rot, root_t, clip: bool = False):
     if torch.is_grad_enabled() and (d.requires_grad or rr.requires_grad or rt.requires_grad):
         return _DofFK.apply(model, bool(clip), d, rr, rt)
     return _dof_fk_launch(model, bool(clip), d, rr, rt)
+
+
+def dof_link_velocity(model, dof, root_rot, root_t, dof_vel, root_vel=None, clip: bool = False,
+                      want_pose: bool = True):
+    """Link velocities from joint velocities in one launch (rtg.h rtg_dof_fk_vel_f32): joint angles and joint
+    velocities (..., J-1) [or (..., J-1, 1)], root rotation (..., 4) [or (..., 1, 4)], root translation (..., 3) and the
+    root twist ``root_vel`` (..., 6) {linear, angular}, world frame (None: zero) -> (g_rot (..., J, 4), g_pos
+    (..., J, 3), g_vel (..., J, 6)), g_vel[..., j, :3] the world-frame linear velocity of link j's origin and
+    g_vel[..., j, 3:] its angular velocity.  g_rot / g_pos are dof_forward_kinematics' bits, or None with
+    ``want_pose=False`` (the same g_vel).  With ``clip`` a joint whose angle lies outside its limits does not turn.
+    Not differentiable."""
+    def _t(x):
+        return x if isinstance(x, torch.Tensor) else torch.as_tensor(x)
+
+    def _angles(x, name):
+        x = _t(x)
+        if x.dim() >= 2 and x.shape[-1] == 1 and x.shape[-2] == n:
+            x = x[..., 0]
+        return dev_f32(x.detach(), (n,), name)
+
+    n = model.num_dofs
+    if clip and not model.has_limits:
+        raise ValueError("clip needs a model with DOF limits")
+    d = _angles(dof, "motion_joint_angles")
+    lead = d.shape[:-1]
+    dv = _angles(dof_vel, "joint_velocities")
+    if dv.shape != d.shape:
+        raise ValueError(f"dof_vel must have dof's shape {tuple(d.shape)}, got {tuple(dv.shape)}")
+    rr = _t(root_rot)
+    if rr.dim() >= 2 and rr.shape[-2] == 1 and rr.shape[-1] == 4:
+        rr = rr[..., 0, :]
+    rr = dev_f32(rr.detach(), (4,), "motion_root_rotation").expand(*lead, 4).contiguous()
+    rt = dev_f32(_t(root_t).detach(), (3,), "motion_root_translation").expand(*lead, 3).contiguous()
+    rv = None
+    if root_vel is not None:
+        rv = dev_f32(_t(root_vel).detach(), (6,), "root_vel").expand(*lead, 6).contiguous()
+    B = int(torch.Size(lead).numel())
+    J = n + 1
+
+    def out(*shape):
+        return torch.empty(tuple(lead) + shape, device=d.device, dtype=torch.float32)
+
+    g_rot, g_pos = (out(J, 4), out(J, 3)) if want_pose else (None, None)
+    g_vel = out(J, 6)
+    check(lib().rtg_dof_fk_vel_f32(model.handle, ptr(d), ptr(rr), ptr(rt), ptr(dv), ptr(rv), B, int(bool(clip)),
+                                   ptr(g_rot), ptr(g_pos), ptr(g_vel), stream_handle()))
+    return g_rot, g_pos, g_vel
 
 
 def _dof_fk_launch(model, clip: bool, d, rr, rt):

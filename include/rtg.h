@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define RTG_ABI_VERSION 7   /* 7: the zero-pose transform of mocap rotations (rtg_rot_ingest_*); rtg_dof_fit_f32,
-                                  rtg_dof_fit_root_f32, rtg_dof_fit_orient_f32, rtg_dof_fit_prior_f32, rtg_dof_fit_apart_f32, rtg_dof_fit_robust_f32 and rtg_dof_motion_sample_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
+                                  rtg_dof_fit_root_f32, rtg_dof_fit_orient_f32, rtg_dof_fit_prior_f32, rtg_dof_fit_apart_f32, rtg_dof_fit_robust_f32, rtg_dof_motion_sample_f32, rtg_dof_fk_vel_f32 and rtg_dof_motion_sample_vel_f32 came later as new symbols only -- nothing that existed changed, so the version stays 7;
                                6: SkeletonState.retarget_to (rtg_retarget_plan_*, rtg_retarget_to_f32);
                                5: the kinematics' gradients (rtg_dof_fk_backward_f32, rtg_fk_backward_f32);
                                4: the frame server's sequence word lives in its inbox (in[RTG_SERVER_SEQ_WORD]; ctl[0]
@@ -140,6 +140,35 @@ int rtg_dof_model_destroy(rtg_dof_model_t model);
  * local[j] = quat_from_angle_axis(a'[j-1], axis[j-1]) (:21-23), local[0] = root rotation (:24). */
 int rtg_dof_fk_f32(rtg_dof_model_t model, const float *dof, const float *root_rot, const float *root_t, int64_t B,
                    int clip, float *g_rot, float *g_pos, rtg_stream_t stream);
+/* Link velocities from joint velocities: rtg_dof_fk_f32 with a tangent sweep down the tree, in one launch -- the
+ * forward-mode counterpart of rtg_dof_fk_backward_f32.  Per frame: the angles a (J-1), the joint velocities
+ * ad = dof_vel (J-1), the root rotation (used as given) and translation, and the root twist root_vel = {v0 (3), w0 (3)},
+ * linear then angular, both in the world frame (rtg_dof_motion_sample_f32's root_vel_out layout; NULL: zero).
+ * -> g_vel (B,J,6) = {v_j (3), w_j (3)}: the world-frame linear velocity of link j's origin and its angular velocity.
+ * With G, P the g_rot, g_pos of rtg_dof_fk_f32 on the same inputs and clip flag, l_j joint j's local translation,
+ * e_j the unit axis of DOF j-1 and p the parent of j, every operation ONE float32 rounding and no FMA:
+ *   - row 0 is the six floats of root_vel bit for bit (+0 when root_vel is NULL);
+ *   - r   = RTG_OP_QUAT_ROTATE(G_p, l_j): the value the FK step adds to P_p (P_j - P_p does not have these bits);
+ *   - c   = w_p x r as  c.x = (w.y r.z) - (w.z r.y),  c.y = (w.z r.x) - (w.x r.z),  c.z = (w.x r.y) - (w.y r.x):
+ *           two products and their difference per component (not torch.cross's fused form);
+ *   - v_j = v_p + c;
+ *   - u   = RTG_OP_QUAT_ROTATE(G_j, e_j), with the joint's OWN global rotation;
+ *   - w_j = w_p + (u * s), a product then a sum per component, with s = ad[j-1] -- and with clip != 0
+ *           s = (a[j-1] < lower[j-1] || a[j-1] > upper[j-1]) ? +0.0f : ad[j-1].
+ * With clip the velocity is the derivative of the pose that is put out: a joint held at a limit does not turn.  (It is
+ * not the straight-through gradient of rtg_dof_fk_backward_f32.)  A NaN angle keeps ad (its rows are NaN anyway), an
+ * angle exactly at a limit keeps ad.  For a unit root rotation this is the exact tangent of the model; a non-unit
+ * root rotation scales r exactly as it scales g_pos.  A frame's NaN / inf stays in that frame's rows.
+ * g_vel is required.  g_rot and g_pos are given together -- then they are rtg_dof_fk_f32's bits -- or both NULL: a
+ * velocity-only call with the same g_vel bits.  root_rot and g_rot rows are 16-byte aligned; no output overlaps an
+ * input or another output.  A one-joint model has no angles: dof and dof_vel are then not dereferenced and may be
+ * NULL.  Never allocates or synchronises; B == 0 is a no-op after the argument checks.  A model of more than 64 joints
+ * is RTG_ERR_UNSUPPORTED; every other rejection -- B < 0, a NULL handle or buffer, g_rot without g_pos, clip on a model
+ * without limits, a misaligned or overlapping buffer -- is RTG_ERR_INVALID_ARGUMENT, decided before any HIP call,
+ * with the reason in rtg_last_error(). */
+int rtg_dof_fk_vel_f32(rtg_dof_model_t model, const float *dof, const float *root_rot, const float *root_t,
+                       const float *dof_vel, const float *root_vel /* (B,6) or NULL */, int64_t B, int clip,
+                       float *g_rot, float *g_pos, float *g_vel, rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Gradients of the kinematics.  The reference's FK is plain torch, so a loss on its outputs back-propagates to the
@@ -608,6 +637,21 @@ int rtg_dof_motion_sample_f32(rtg_dof_model_t model, rtg_motion_lib_t lib, const
                               const int32_t *key_links, int32_t K, float *dof_out, float *dof_vel_out,
                               float *root_rot_out, float *root_t_out, float *root_vel_out, float *g_rot, float *g_pos,
                               float *key_pos, rtg_stream_t stream);
+/* The same launch with the link velocities of the sampled state, so that a full reference state -- position, rotation,
+ * linear and angular velocity of every tracked link -- leaves in one launch.  The parameters up to key_pos are
+ * rtg_dof_motion_sample_f32's.  g_vel (N,J,6) is rtg_dof_fk_vel_f32's g_vel on the launch's own outputs: angles
+ * dof_out[n] (the clip test of RTG_DOF_MOTION_CLIP runs on them), joint velocities dof_vel_out[n], root rotation and
+ * translation root_rot_out[n], root_t_out[n], root twist root_vel_out[n]; key_vel[n, k] = g_vel[n, key_links[k]] bit
+ * for bit (N,K,6).  g_vel and key_vel are each optional and need neither g_rot / g_pos nor each other; either of them
+ * requires dof_vel_out and root_vel_out.  K > 0 exactly when key_pos or key_vel is given.  An invalid query's rows
+ * are the quiet NaN in both; at and past a clip's last frame (finite rows) they are +0.  With g_vel and key_vel both
+ * NULL the call IS rtg_dof_motion_sample_f32: the same kernels, bits and messages.  Rejections as there. */
+int rtg_dof_motion_sample_vel_f32(rtg_dof_model_t model, rtg_motion_lib_t lib, const float *dof, const float *root_rot,
+                                  const float *root_t, const int32_t *clip, const float *time, int64_t N, int flags,
+                                  const int32_t *key_links, int32_t K, float *dof_out, float *dof_vel_out,
+                                  float *root_rot_out, float *root_t_out, float *root_vel_out, float *g_rot,
+                                  float *g_pos, float *key_pos, float *g_vel /* (N,J,6) */,
+                                  float *key_vel /* (N,K,6) */, rtg_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Motion-level prep of the legacy motion path (retarget/main.py)

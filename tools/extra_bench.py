@@ -58,6 +58,9 @@
               quat_normalize, motion_angular_velocity, dof_forward_kinematics), interleaved rounds, the results
               compared bit for bit; for the record rtg_motion_sample_f32 (GLOBAL, velocities) on the equivalent
               quaternion library at the same N
+  link_velocity -- link twists from joint velocities (rtg_dof_fk_vel_f32, rtg_dof_motion_sample_vel_f32; Hu v5, 262144
+              frames / queries): the pose-only launches against the ones with the twist rows, the fused sampler against
+              the sampler plus the standalone call and against a composition of ops.quat_rotate and torch ops
   dof_motion_sample_traffic -- a few launches of each output set and a 256 MiB copy of known bytes, for a counter run of
               its own against the algorithmic bytes that `dof_motion_sample` prints
   fit_targets -- the keypoint targets of the pose fit (rtg_fit_targets_f32, C ABI, preallocated outputs; VTRDyn-21 ->
@@ -1357,6 +1360,107 @@ def dof_motion_sample_traffic(N=262144, clips=64, frames=4096):
             "algorithmic_bytes_per_query": {k: dict(zip(("read", "written"), _dof_motion_bytes(J, *v)))
                                             for k, v in DOF_MOTION_SETS.items()},
             "launches": "3 x 256 MiB copy, then 3 x each of " + ", ".join(DOF_MOTION_SETS) + "; random (clip, time)"}
+
+
+def link_velocity(N=262144, rounds=4, clips=64, frames=4096):
+    """Link velocities from joint velocities (rtg_dof_fk_vel_f32, rtg_dof_motion_sample_vel_f32; Hu v5, C ABI, outputs
+    preallocated, interleaved rounds): the pose-only launches against the ones with the twist rows -- rtg_dof_fk_f32
+    against rtg_dof_fk_vel_f32 full and velocity-only; the sampler on 6 key links and on full rows with and without
+    the new outputs -- the fused sampler against the plain sampler plus the standalone velocity-only call on its
+    outputs, and against a composed baseline: the plain sampler plus the same values from ops.quat_rotate and torch
+    element-wise ops, level by level down the tree (compared bit for bit)."""
+    from retarget.robot_config import Hu_v5
+    from rtg.runtime import ptr, stream_handle
+    lib = _lib.lib()
+    M, ML, J, fps, dof, rr, rt, _, clip, time_, outs = _dof_motion_setup(N, clips, frames)
+    nd, K = J - 1, len(DOF_MOTION_KEYS)
+    keys = np.asarray(DOF_MOTION_KEYS, np.int32)
+    kp = keys.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    g_vel, key_vel = torch.empty((N, J, 6), device="cuda"), torch.empty((N, K, 6), device="cuda")
+    o = outs
+
+    def sampler(want_global, want_keys, gv=None, kv=None):
+        _lib.check(lib.rtg_dof_motion_sample_vel_f32(
+            M.handle, ML.handle, ptr(dof), ptr(rr), ptr(rt), ptr(clip), ptr(time_), N, _lib.DOF_MOTION_NORMALIZE,
+            kp if want_keys else None, K if want_keys else 0, ptr(o["dof"]), ptr(o["dof_vel"]), ptr(o["root_rot"]),
+            ptr(o["root_t"]), ptr(o["root_vel"]), ptr(o["g_rot"]) if want_global else None,
+            ptr(o["g_pos"]) if want_global else None, ptr(o["key_pos"]) if want_keys else None, ptr(gv), ptr(kv),
+            stream_handle()))
+
+    sampler(True, False)   # a sampled state as the standalone calls' input
+    torch.cuda.synchronize()
+    a, ad, q, t, tw = (o[k].clone() for k in ("dof", "dof_vel", "root_rot", "root_t", "root_vel"))
+    f_rot, f_pos, f_vel = torch.empty((N, J, 4), device="cuda"), torch.empty((N, J, 3), device="cuda"), torch.empty((N, J, 6), device="cuda")
+
+    def fk():
+        _lib.check(lib.rtg_dof_fk_f32(M.handle, ptr(a), ptr(q), ptr(t), N, 0, ptr(f_rot), ptr(f_pos), stream_handle()))
+
+    def fk_vel(pose=True, src=(a, q, t, ad, tw), dst=None):
+        _lib.check(lib.rtg_dof_fk_vel_f32(M.handle, ptr(src[0]), ptr(src[1]), ptr(src[2]), ptr(src[3]), ptr(src[4]), N, 0,
+                                          ptr(f_rot) if pose else None, ptr(f_pos) if pose else None,
+                                          ptr(f_vel if dst is None else dst), stream_handle()))
+
+    # the composed baseline's tables: the tree's levels, each level's joints, parents, local translations and axes
+    parents = assets.parents("hu_v5").astype(np.int64)
+    depth = np.zeros(J, np.int64)
+    for j in range(1, J):
+        depth[j] = depth[parents[j]] + 1
+    lt = torch.as_tensor(assets.local_translation("hu_v5").astype(np.float32), device="cuda")
+    eye = torch.eye(3, device="cuda")[list(Hu_v5.Hu_DOF_AXIS)]
+    levels = []
+    for d in range(1, int(depth.max()) + 1):
+        js = np.nonzero(depth == d)[0]
+        levels.append((torch.as_tensor(js, device="cuda"), torch.as_tensor(parents[js], device="cuda"),
+                       lt[js].expand(N, len(js), 3).contiguous(), eye[js - 1].expand(N, len(js), 3).contiguous()))
+    c_vel = torch.empty((N, J, 6), device="cuda")
+
+    def composed():
+        sampler(True, False)
+        G, s = o["g_rot"], o["dof_vel"]
+        c_vel[:, 0] = o["root_vel"]
+        for js, ps, l, e in levels:
+            Gp, twp = G.index_select(1, ps), c_vel.index_select(1, ps)
+            w = twp[..., 3:]
+            r = ops.quat_rotate(Gp.contiguous(), l)
+            u = ops.quat_rotate(G.index_select(1, js).contiguous(), e)
+            c = torch.stack([(w[..., 1] * r[..., 2]) - (w[..., 2] * r[..., 1]), (w[..., 2] * r[..., 0]) - (w[..., 0] * r[..., 2]),
+                             (w[..., 0] * r[..., 1]) - (w[..., 1] * r[..., 0])], dim=-1)
+            c_vel[:, js] = torch.cat([twp[..., :3] + c, w + (u * s.index_select(1, js - 1)[..., None])], dim=-1)
+
+    pairs = {   # name -> (the launch without the twist rows, the launch with them)
+        "dof_fk_vs_vel_full": (fk, fk_vel),
+        "dof_fk_vs_vel_only": (fk, lambda: fk_vel(pose=False)),
+        "sampler_key_links": (lambda: sampler(False, True), lambda: sampler(False, True, None, key_vel)),
+        "sampler_full_rows": (lambda: sampler(True, False), lambda: sampler(True, False, g_vel, None)),
+        "sampler_then_standalone_vs_fused": (
+            lambda: (sampler(True, False), fk_vel(False, (o["dof"], o["root_rot"], o["root_t"], o["dof_vel"], o["root_vel"]))),
+            lambda: sampler(True, False, g_vel, None)),
+        "composed_vs_fused": (composed, lambda: sampler(True, False, g_vel, None)),
+    }
+    sampler(True, False, g_vel, None)
+    composed()
+    fk_vel(False, (o["dof"], o["root_rot"], o["root_t"], o["dof_vel"], o["root_vel"]))
+    torch.cuda.synchronize()
+    same = {"composed_equals_fused_bits": bool(torch.equal(c_vel.view(torch.int32), g_vel.view(torch.int32))),
+            "standalone_on_the_samplers_outputs_equals_fused_bits": bool(torch.equal(f_vel.view(torch.int32), g_vel.view(torch.int32)))}
+    res = {"N": N, "J": J, "K": K, **same}
+    # algorithmic bytes per frame / query
+    fk_b = 4 * nd + 28 + 28 * J
+    smp_rd, smp_wr = _dof_motion_bytes(J, True, False)
+    key_rd, key_wr = _dof_motion_bytes(J, False, True)
+    res["algorithmic_bytes_per_frame"] = {
+        "rtg_dof_fk_f32": fk_b, "rtg_dof_fk_vel_f32_full": fk_b + 4 * nd + 24 + 24 * J,
+        "rtg_dof_fk_vel_f32_velocity_only": 8 * nd + 28 + 24 + 24 * J,
+        "sampler_full_rows": smp_rd + smp_wr, "sampler_full_rows_with_g_vel": smp_rd + smp_wr + 24 * J,
+        "sampler_key_links": key_rd + key_wr, "sampler_key_links_with_key_vel": key_rd + key_wr + 24 * K}
+    for name, (base, vel) in pairs.items():
+        b_us, v_us = [], []
+        slow = name == "composed_vs_fused"
+        for _ in range(rounds):   # interleaved: both see the same box state
+            b_us.append(time_events(base, reps=5 if slow else 20, warm=1 if slow else 3) * 1e3)
+            v_us.append(time_events(vel, reps=20, warm=3) * 1e3)
+        res[name] = {"without_us": b_us, "with_us": v_us, "with_over_without": [v / b for b, v in zip(b_us, v_us)]}
+    return res
 
 
 def _fit_targets_setup(B):
